@@ -474,6 +474,27 @@ def full_pipeline_leg(budget_s):
     return out
 
 
+def dump_outputs(out_dir, arrays, budget=64_000_000, seed=0):
+    """--dump-outputs: each array as <out_dir>/<name>.npy (float32 / float64).  If they exceed `budget` bytes in all, each keeps a fixed, seeded
+    sample of its leading axis (Gaussians; for the [3,H,W] image, pixels), sized so the files fit, and the sampled indices go to <name>_index.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: (np.ascontiguousarray(a.reshape(a.shape[0], -1).T) if k == "image" else a) for k, a in arrays.items()}  # image -> [H*W, 3]
+    total = sum(a.nbytes for a in flat.values())
+    room = budget - 2 * 256 * len(flat)  # (.npy headers)
+    frac = 1.0 if total <= room else room / sum(a.nbytes + 8 * a.shape[0] for a in flat.values())  # (8 bytes: a row's float64 index)
+    for k, a in flat.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, k + "_index.npy"), idx.astype(np.float64))
+        elif k == "image":
+            a = arrays[k]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -491,7 +512,11 @@ def main():
                          "every kernel launch of the run then has the chip to itself (tools/prof_r04.sh profiles that mode for the exclusive durations)")
     ap.add_argument("--no-full-pipeline", action="store_true", help="skip the `full_pipeline` leg (BASELINE configs 3 / 4 with the reference's own scripts and networks)")
     ap.add_argument("--full-pipeline-budget", type=float, default=600.0, help="seconds the full-pipeline leg may take in total; what does not fit is skipped and says so")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step of the `value` path returned (image, radii, input gradients; rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -514,7 +539,10 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execvpe(sys.executable, cmd, dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")))
+        # a child process, not an exec: this process has initialised the GPU (device_count above), and replacing such a process is not safe
+        import subprocess
+        r = subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")))
+        sys.exit(r.returncode)
     if env_world is not None and int(env_world) != args.gpus:
         raise SystemExit("bench.py: --gpus %d but the launcher started %s rank(s) (WORLD_SIZE); pass the same N to both" % (args.gpus, env_world))
 
@@ -562,15 +590,19 @@ def main():
         projmatrix=torch.from_numpy(cam["full_proj_transform"]).to(dev), sh_degree=3,
         campos=torch.from_numpy(cam["camera_center"]).to(dev), prefiltered=False, debug=False)
     rast = RZ.GaussianRasterizer(rs)
-    gout = torch.randn(3, H, W, device=dev)  # dL/dpix of a synthetic loss, random (not zero: DVFS note in the guide)
+    # dL/dpix of a synthetic loss, random (not zero: DVFS note in the guide) and seeded: the same arguments give the same inputs in every run
+    gout = torch.randn(3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(S.SEED + rank))
+    last_out = {} if args.dump_outputs else None  # --dump-outputs: what the latest fwd_bwd() returned (its gradients stay in .grad)
 
     def fwd_bwd():  # the same step through the drop-in autograd module (secondary number: adds PyTorch's per-call autograd machinery)
         for v in t.values():
             v.grad = None
         m2.grad = None
-        img, _ = rast(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=None, colors_precomp=t["colors"],
-                      scales=t["scales"], rotations=t["rotations"], cov3D_precomp=None)
+        img, radii = rast(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=None, colors_precomp=t["colors"],
+                          scales=t["scales"], rotations=t["rotations"], cov3D_precomp=None)
         img.backward(gout)
+        if last_out is not None:
+            last_out["image"], last_out["radii"] = img.detach(), radii
 
     def fwd_only():
         with torch.no_grad():
@@ -773,6 +805,12 @@ def main():
     q1, q3 = sorted(api_blocks)[REPEATS // 4], sorted(api_blocks)[(3 * REPEATS) // 4]
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.steps / elapsed
+    dumped = None
+    if last_out is not None:  # the last timed step's outputs, copied before any later leg runs the same module again
+        torch.cuda.synchronize(dev)
+        dumped = {"image": last_out["image"].cpu().numpy(), "radii": last_out["radii"].float().cpu().numpy(), "grad_means2D": m2.grad.cpu().numpy()}
+        dumped.update(("grad_" + k, t[k].grad.cpu().numpy()) for k in names)
+        last_out = None  # (fwd_bwd reads it at call time: the legs below keep nothing)
     # ... and the same blocks with the process pinned next to its GPU (one rank only; the remaining GPU legs keep the pin, the CPU legs drop it)
     el_pinned = None
     if cpu_slice is None and world == 1:
@@ -975,6 +1013,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             cpu_splat = {"error": repr(e)[:200]}
 
+    if rank == 0 and dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     if rank == 0:
         rate = lambda el: round(world * args.steps / el, 2) if el else None  # noqa: E731
         cfg_name = ("BASELINE config 2" if (args.res, args.gaussians, W) == (1024, 600000, 1024) else

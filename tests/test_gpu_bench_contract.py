@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -131,3 +132,25 @@ def test_scale_shaped_dry_run_prints_one_record_per_n():
         p = x["parsed"]
         assert x["rc"] == 0 and p["n_gpus"] == x["n"] and p["steps"] == 3 and p["value"] > 0 and p["scaling"] == "weak" and x["consistency"]["fits_in_driver_run"]
         assert p["stage2_path"]["n_gpus"] == x["n"]
+
+
+def test_dump_outputs_writes_what_the_timed_path_returned(tmp_path):
+    """--dump-outputs DIR: the last timed step's image, radii and input gradients as float32 .npy files, at most 64 MB in all."""
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000",
+           "--headline-only", "--no-cpu-baseline", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert d["steps"] == 3 and len(d["repeats_ms_per_step"]) >= 3
+    names = {"image": None, "radii": None, "grad_means3D": 3, "grad_means2D": 3, "grad_colors": 3, "grad_opacities": 1, "grad_scales": 3, "grad_rotations": 4}
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in names)
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64_000_000
+    a = {k: np.load(out / (k + ".npy")) for k in names}
+    P = a["radii"].shape[0]
+    assert a["image"].shape == (3, 256, 256) and a["radii"].shape == (P,) and P > 0
+    for k, c in names.items():
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        if c is not None:
+            assert a[k].shape == (P, c), k
+    assert (a["radii"] > 0).any() and a["image"].std() > 0 and np.abs(a["grad_means3D"]).max() > 0
