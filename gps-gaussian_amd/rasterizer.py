@@ -21,6 +21,9 @@ Host-side design notes (MI355X-first, not a translation of upstream's C++ glue):
     stream of kernel launches only, which is what a HIP graph capture (torch.cuda.graph) needs; the caller owns the
     capacity question (run the step once eagerly in sync mode first: the learnt capacity is reused), an overflowing view is
     simply not rendered (the workspace header says so).
+  * one policy for every host that launches views (this module's forward, defer_capacity_checks(), the compiled path, session.RasterSession):
+    `_plan` picks capacity, list form and flags for each attempt, `_settle` reads a notification into a `_Header` and learns from it,
+    `_repair_loop` decides what an overflow means and re-runs the view.
 """
 import ctypes as C
 import os
@@ -67,8 +70,7 @@ def set_stage_timing(on, stage=None):
 
 # ---- capacity policy --------------------------------------------------------------------------------------------
 _MIN_CAP = 1 << 16
-_early_notify = os.environ.get("GPSGS_EARLY_NOTIFY", "1") != "0"  # 0: sync mode waits for the whole forward (event after a header copy)
-_state = {}  # device index -> dict(ratio=instances per Gaussian seen so far, pending=[(event, pinned_header, P)])
+_state = {}  # device index -> dict(ratio=instances per Gaussian seen so far, floor, pending=[(note, stream, P)]: deferred-mode checks, ...)
 _lock = threading.Lock()  # the per-device capacity state and the pinned header rings may be used from several host threads
 
 
@@ -92,8 +94,8 @@ def _bin_capacity(st, W, H):
     """Per-bin capacity of DIRECT bin lists for the next view on this device, or 0 = scanned lists (include/gpsgs.h GsrViewExt.bin_capacity).
     Direct lists drop two dependent launches from the forward (scan -> scatter) but a bin holds at most `capacity` entries: they are used until
     this device sees bin lists longer than 768 entries (`big_bins`, _note_longest -- the untrained-heads regime, lists of 1,000-3,000), and for images
-    of up to 65,536 bins (2048^2).  A view that turns out to need longer lists is reported like an overflow and repaired by the callers' re-run
-    loops with scanned lists.  GPSGS_LISTS=scanned / direct forces the form (direct: still subject to the size limits)."""
+    of up to 65,536 bins (2048^2).  A view that turns out to need longer lists is reported like an overflow and repaired by _repair_loop with
+    scanned lists.  GPSGS_LISTS=scanned / direct forces the form (direct: still subject to the size limits)."""
     m = os.environ.get("GPSGS_LISTS", "auto")
     if m not in ("auto", "scanned", "direct"):
         raise ValueError("GPSGS_LISTS must be 'auto', 'scanned' or 'direct'")
@@ -106,6 +108,21 @@ def _bin_capacity(st, W, H):
     return _DIRECT_CAP if ok else 0
 
 
+def _plan(st, P, W, H, mode, scanned_only):
+    """One launch attempt of a view with P Gaussians (or a row range's estimate) -> (instance capacity, per-bin capacity, extra flags).
+    scanned_only: this view has shown a list too long for direct bins (its repair run).  The large-list sort launch is left out
+    (GSR_FLAG_NO_LARGE_SORT) as long as this device has seen no long list -- only where a repair loop exists (mode "sync": the module's sync
+    mode, also inside defer_capacity_checks(), the compiled path and RasterSession), because a surprise is reported like an overflow.
+    Deferred mode cannot re-run the view, so it always launches them (they return at once when the longest list is short: ADVICE r04)."""
+    cap = _capacity_for(st, P)
+    bin_cap = 0 if scanned_only else _bin_capacity(st, W, H)
+    flags = _capi.GSR_FLAG_NO_LARGE_SORT if (mode == "sync" and P > 0 and not st.get("big_bins", False)) else 0
+    return cap, bin_cap, flags
+
+
+_DEFAULT_FAMILY = "tiles"
+
+
 def _composite_flag():
     """GPSGS_COMPOSITE=valu: the compositing kernels that evaluate every (pixel, splat) exponent on the vector ALUs (gsr_composite.hip).
     GPSGS_COMPOSITE=tiles: the kernels that take the exponents from bf16 matrix-core tiles (gsr_composite_tiles.hip; exact split
@@ -114,9 +131,6 @@ def _composite_flag():
     if m not in ("valu", "tiles"):
         raise ValueError("GPSGS_COMPOSITE must be 'valu' or 'tiles'")
     return _capi.GSR_FLAG_COMPOSITE_TILES if m == "tiles" else 0
-
-
-_DEFAULT_FAMILY = "tiles"
 
 
 def _wave_priority_flag(st=None, stream=None, deterministic=False):
@@ -150,70 +164,32 @@ def _check_mode():
     return m
 
 
-def _drain_pending(st, block=False):
-    """Look at the capacity results of earlier GPSGS_CHECK=deferred forwards.  Two kinds of entries: ("note", ...) -- the binning scan stores the
-    header straight into a pinned slot ~40 us into the forward (round 4: deferred mode uses the early notification too; until then it copied the
-    header at the END of the forward, so the blocking drain in the backward waited for the whole forward and deferred ran SLOWER than sync) -- and
-    ("ev", ...) -- a header copy + event at the end of the forward (GPSGS_EARLY_NOTIFY=0)."""
-    keep = []
-    with _lock:  # the swap is atomic with respect to other threads' drains and appends (an autograd thread's backward drains too)
-        pending, st["pending"] = st["pending"], []
-    try:
-        for i, ent in enumerate(pending):
-            if ent[0] == "note":
-                _, (slot, hdr, w32, seq), stream, P, dev_index = ent
-                if int(w32[7]) != seq:
-                    if not block:
-                        keep.append(ent)
-                        continue
-                    try:
-                        _wait_notify(w32, seq, stream)
-                    except Exception:
-                        _rings[(dev_index, "notify")].release(slot)
-                        keep.extend(pending[i + 1:])  # the entries behind this one stay pending: their slots and capacity results are not lost
-                        raise
-                R, overflow, need = _decode(hdr)
-                npts, longest = int(w32[6]), int(w32[3])
-                _rings[(dev_index, "notify")].release(slot)
-                _learn(st, R, need, P if P is not None else npts, longest)
-                _note_longest(st, longest)
-            else:
-                _, ev, hdr, P = ent
-                if block:
-                    ev.synchronize()
-                if not ev.query():
-                    keep.append(ent)
-                    continue
-                R, overflow, need = _decode(hdr)
-                _learn(st, R, need, P if P is not None else int(hdr[3]) & 0xffffffff, (int(hdr[1]) >> 32) & 0xffffffff)
-            if overflow:
-                keep.extend(pending[i + 1:])  # (their slots are looked at -- and released -- by the next call)
-                raise RuntimeError(
-                    "gps_gaussian_amd: a previous rasteriser call (GPSGS_CHECK=deferred) was not rendered: it needed %d (Gaussian, bin) instances / "
-                    "gradient slots -- more than the capacity of its workspace -- and its longest bin list was %d entries. The capacity has been raised; re-run, "
-                    "or use GPSGS_CHECK=sync." % (need, longest if ent[0] == "note" else (int(hdr[1]) >> 32) & 0xffffffff))
-    finally:
-        with _lock:
-            st["pending"] = keep + st["pending"]
+class _Header(NamedTuple):
+    """What the host learns from a forward's header."""
+    R: int         # (Gaussian, bin) instances the view needed
+    overflow: int  # non-zero: nothing was rendered (capacity, a list too long for its direct bin, or a row range beyond its capacity)
+    need: int      # the capacity it needed: max(R, gradient-record slots)
+    longest: int   # longest bin list
+    npts: int      # Gaussians of the view (a row range's count)
 
 
-def _decode(hdr):
-    """hdr: int64[4] view of the first 32 header bytes -> (R, overflow, capacity needed = max(R, gradient-record slots))."""
-    R = int(hdr[0])
-    overflow = int(hdr[1]) & 0xffffffff
-    slots = (int(hdr[2]) >> 32) & 0xffffffff
-    return R, overflow, max(R, slots)
+def _header(w32):
+    """A notify slot's uint32[8] view (GsrHeader: u64 R, overflow, max_tile_count, num_busy_wgs, num_slots, num_points; word 7 = sequence) -> _Header."""
+    w = w32.tolist()
+    R = w[0] | w[1] << 32
+    return _Header(R, w[2], max(R, w[5]), w[3], w[6])
 
 
-def _learn(st, R, need, P, longest=None):
+def _learn(st, h, P):
+    """Learn from a view's header (P: its Gaussian count): capacity ratio and floor (monotone maxima), the work-order hint, the list-form regime."""
     with _lock:  # read-modify-write of monotone maxima
-        st["last_R"] = R
-        if P is not None and P > 0:
-            st["ratio"] = max(st["ratio"], need / P)
+        st["last_R"] = h.R
+        if P > 0:
+            st["ratio"] = max(st["ratio"], h.need / P)
             st["last_points"] = P
-        st["floor"] = max(st["floor"], min(int(need * 1.25) + 4096, 0x7fffffff))
-        if longest is not None:
-            st["longest"] = longest  # the next view's work-order hint (GsrViewExt.order_hint): longest bin list of this one
+        st["floor"] = max(st["floor"], min(int(h.need * 1.25) + 4096, 0x7fffffff))
+        st["longest"] = h.longest  # the next view's work-order hint (GsrViewExt.order_hint): longest bin list of this one
+    _note_longest(st, h.longest)
 
 
 def _note_longest(st, longest):
@@ -231,50 +207,101 @@ def _note_longest(st, longest):
             st["short_streak"] = 0
 
 
+def _settle(st, note, stream, P=None):
+    """Wait for the header of a notify `note` (ring, slot, uint32[8] view, sequence) launched on `stream`, hand its slot back to the ring
+    (also when the wait fails) and learn from it.  P: the view's Gaussian count, None = the header's (a row range).  -> _Header"""
+    ring, slot, w32, seq = note
+    try:
+        _wait_notify(w32, seq, stream)
+        h = _header(w32)
+    finally:
+        ring.release(slot)  # the host has seen the sequence word (or gave up): the slot may be reissued
+    _learn(st, h, h.npts if P is None else P)
+    return h
+
+
+def _repair_loop(st, note, stream, P, rows, cap, bin_cap, relaunch):
+    """The exact (sync-mode) capacity check of one view: settle its notification and, while the view overflowed, re-run it through
+    relaunch(scanned_only) -> (note, cap, bin_cap) of the new attempt.  An overflow means, in this order: a row range (rows: P is its row
+    capacity) holding more Gaussians than that -> raise; a list longer than the direct bins hold -> re-run with scanned lists (_learn has set
+    big_bins); a capacity already at 2^31 - 1 -> raise; otherwise -> re-run with the capacity _learn has grown.  The in-flight kernels of a failed
+    attempt exit at once on the overflow flag."""
+    scanned_only = False
+    while True:
+        h = _settle(st, note, stream, None if rows else P)
+        if not h.overflow:
+            return
+        if rows and h.npts > P:
+            raise RuntimeError("gps_gaussian_amd: the row range holds %d Gaussians, more than the capacity of %d rows the view was sized for" % (h.npts, P))
+        if bin_cap and h.longest > bin_cap:
+            scanned_only = True
+        elif cap >= 0x7fffffff:
+            raise _too_many(h.R)
+        note, cap, bin_cap = relaunch(scanned_only)
+
+
+def _drain_pending(st, block=False):
+    """Look at the capacity results of earlier GPSGS_CHECK=deferred forwards: the binning scan stores each one's header straight into a pinned slot
+    ~40 us into the forward.  block: wait for those that have not arrived yet (else they stay pending)."""
+    keep = []
+    with _lock:  # the swap is atomic with respect to other threads' drains and appends (an autograd thread's backward drains too)
+        pending, st["pending"] = st["pending"], []
+    try:
+        for i, ent in enumerate(pending):
+            note, stream, P = ent
+            if not block and int(note[2][7]) != note[3]:
+                keep.append(ent)
+                continue
+            try:
+                h = _settle(st, note, stream, P)
+            except Exception:
+                keep.extend(pending[i + 1:])  # the entries behind this one stay pending: their slots and capacity results are not lost
+                raise
+            if h.overflow:
+                keep.extend(pending[i + 1:])  # (their slots are looked at -- and released -- by the next call)
+                raise RuntimeError(
+                    "gps_gaussian_amd: a previous rasteriser call (GPSGS_CHECK=deferred) was not rendered: it needed %d (Gaussian, bin) instances / "
+                    "gradient slots -- more than the capacity of its workspace -- and its longest bin list was %d entries. The capacity has been raised; re-run, "
+                    "or use GPSGS_CHECK=sync." % (h.need, h.longest))
+    finally:
+        with _lock:
+            st["pending"] = keep + st["pending"]
+
+
 def _ptr(t):
     return t.data_ptr() if t is not None else None  # ctypes converts a Python int to the void* argument
 
 
 class _HeaderRing:
-    """Pinned 32-byte header slots + reusable events (allocating pinned memory / events per call costs tens of us).
-
-    Two uses: `next()` hands out slots round-robin for header COPIES (the caller bounds the number in flight: _drain_pending), and
-    `acquire_notify()` / `release()` hand out slots the scan kernel writes directly (gsr_forward_notify) with IN-FLIGHT ACCOUNTING: a
-    slot goes back to the free list only after the host has seen its sequence word, and when every slot is out (a batch of more forwards
-    than slots inside one defer_capacity_checks(), nested callers, many threads) the ring GROWS by another pinned chunk instead of
-    reissuing a slot that is still being polled."""
+    """Pinned 32-byte header slots the scan kernel writes directly (gsr_forward_notify), allocated in chunks (allocating pinned memory per call
+    costs tens of us).  `acquire_notify()` / `release()` hand them out with IN-FLIGHT ACCOUNTING: a slot goes back to the free list only after the
+    host has seen its sequence word, and when every slot is out (a batch of more forwards than slots inside one defer_capacity_checks(), nested
+    callers, many threads) the ring GROWS by another pinned chunk instead of reissuing a slot that is still being polled."""
 
     def __init__(self, n=64):
-        self.n, self.i = n, 0
-        self.chunks = []  # (int64 [n,4] view, uint32 [n,8] view: word 7 of a slot = sequence number, base address, the pinned tensor)
+        self.n = n
+        self.chunks = []  # (uint32 [n,8] view: word 7 of a slot = sequence number, base address, the pinned tensor)
         self.free = []
         self.seq = 0
         self._grow()
-        self.np, self.base, self.events = self.chunks[0][0], self.chunks[0][2], [torch.cuda.Event() for _ in range(n)]
-
-    def next(self):
-        with _lock:
-            i = self.i
-            self.i = (i + 1) % self.n
-        return self.np[i], C.c_void_p(self.base + 32 * i), self.events[i]
 
     def acquire_notify(self):
-        """-> (slot handle, int64[4] header view, uint32[8] view, pointer, sequence number the device will store in word 7)."""
+        """-> (note = (ring, slot handle, uint32[8] view, sequence number the device will store in word 7), pointer to the slot)."""
         while True:
             with _lock:  # slot and sequence number are handed out together: two host threads never share either
                 if self.free:
                     c, k = slot = self.free.pop()
                     seq = self.seq = self.seq % 0x7fffffff + 1  # never 0, never equal to what the slot holds from its previous use
-                    arr, a32, base, _ = self.chunks[c]
-                    return slot, arr[k], a32[k], C.c_void_p(base + 32 * k), seq
+                    a32, base, _ = self.chunks[c]
+                    return (self, slot, a32[k], seq), C.c_void_p(base + 32 * k)
             self._grow()
 
     def _grow(self):
         buf = torch.zeros((self.n, 4), dtype=torch.int64).pin_memory()  # 32-byte header prefix per slot (allocates pinned memory: outside the lock)
-        arr = buf.numpy()  # same memory; plain numpy scalars are much cheaper to read than 0-d tensors
+        a32 = buf.numpy().view("uint32")  # same memory; plain numpy scalars are much cheaper to read than 0-d tensors
         with _lock:
             c = len(self.chunks)
-            self.chunks.append((arr, arr.view("uint32"), buf.data_ptr(), buf))
+            self.chunks.append((a32, buf.data_ptr(), buf))
             self.free.extend((c, k) for k in reversed(range(self.n)))
 
     def release(self, slot):
@@ -340,15 +367,13 @@ class defer_capacity_checks:
 _rings = {}
 
 
-def _ring(dev, kind="notify"):
-    """Pinned header slots of a device.  Two rings: "notify" (slots the scan kernel writes directly, reused as soon as the host has seen
-    the sequence word) and "copy" (targets of header copies that may stay pending across calls in deferred mode) -- a slot of one
-    kind can so never be handed out while the other path still has it in flight."""
-    r = _rings.get((dev.index, kind))
+def _ring(dev):
+    """The pinned notify slots of a device."""
+    r = _rings.get(dev.index)
     if r is None:
         ring = _HeaderRing()  # (allocates pinned memory: outside the lock)
         with _lock:
-            r = _rings.setdefault((dev.index, kind), ring)
+            r = _rings.setdefault(dev.index, ring)
     return r
 
 
@@ -508,129 +533,63 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
         fwd_only = 0 if needs_grad else 1
         # a row-range view's P is only a bound: the instance capacity follows the Gaussian counts seen so far on this device
         p_est = P if rows is None else min(P, int(st.get("last_points", P) * 1.25) + 4096)
-        early = mode in ("sync", "deferred") and P > 0 and _early_notify
-        ring = _ring(dev) if early else None
+        # the device publishes the header to pinned memory right after the binning scan: the host checks capacity while scatter / sort /
+        # compositing are still running (no GPU idle time)
+        ring = _ring(dev) if (mode != "none" and P > 0) else None
+        box = [None, 0, 0]  # the workspace, capacity and per-bin capacity of the view's latest attempt
 
-        scanned_only = [False]
-
-        def launch(cap):
-            """Enqueue the whole forward against an instance capacity.  -> (workspace, bytes, notify slot or None, per-bin capacity of its lists)"""
-            # direct lists unless this device sees long bin lists -- or THIS view has just shown one (a repair run; also under GPSGS_LISTS=direct)
-            bin_cap = 0 if scanned_only[0] else _bin_capacity(st, W, H)
+        def launch(cap, bin_cap, plan_flags):
+            """Enqueue the whole forward (one _plan).  -> (notify note or None, cap, bin_cap)"""
             nbytes = lib.gsr_workspace_bytes_ex(P, W, H, cap, bin_cap, fwd_only)
             st["last_ws_bytes"] = nbytes  # reported by last_stats(): what one view in flight holds (forward-only workspaces are ~3x smaller)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            flags, note = base_flags, None
-            hdr_ptr, seq = None, 0
-            if early:
-                # the device publishes the instance count to pinned memory right after the binning scan; the host checks capacity while
-                # scatter / sort / compositing are still running (no GPU idle time).  The same header carries the longest bin list: as
-                # long as none has exceeded 1024 entries on this device, the (then idle, ~5 us) large-list sort launch is left out -- a
-                # surprise is reported like an overflow
-                slot, hdr, w32, hdr_ptr, seq = ring.acquire_notify()
-                note = (slot, hdr, w32, seq)
-                # (only where a repair loop exists: sync mode, also inside defer_capacity_checks().  Deferred mode cannot re-run the view, so it always
-                #  launches the large-list sorts -- they return at once when the view's longest list is short: ADVICE r04)
-                if mode == "sync" and not st.get("big_bins", False):
-                    flags |= _capi.GSR_FLAG_NO_LARGE_SORT
+            note, hdr_ptr = ring.acquire_notify() if ring is not None else (None, None)
             ext = _ext(rows, st.get("longest", 0), appear, bin_cap)  # work order: longest lists first, relative to the longest list seen on this device
             rc = lib.gsr_forward_ex(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier), float(rs.tanfovx),
-                                    float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap, flags,
-                                    stream, hdr_ptr, seq, C.byref(ext))
+                                    float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap,
+                                    base_flags | plan_flags, stream, hdr_ptr, note[3] if note is not None else 0, C.byref(ext))
             if rc != 0 and note is not None:
-                ring.release(note[0])
+                ring.release(note[1])
             _capi.check(rc, "gsr_forward_ex")
-            return ws, nbytes, note, bin_cap
+            box[:] = ws, cap, bin_cap
+            return note, cap, bin_cap
 
-        def settle(note, cap, bin_cap):
-            """Wait for a notification and learn from it.  -> (overflowed, R)"""
-            slot, hdr, w32, seq = note
-            try:
-                _wait_notify(w32, seq, cur_stream)
-                R, overflow, need = _decode(hdr)
-                npts, longest = int(w32[6]), int(w32[3])
-            finally:
-                ring.release(slot)  # the host has seen the sequence word (or gave up): the slot may be reissued
-            _learn(st, R, need, npts if rows is not None else P, longest)
-            _note_longest(st, longest)  # with margin: from now on the large-list sorts are launched and the lists are scanned
-            if overflow and rows is not None and npts > P:
-                raise RuntimeError("gps_gaussian_amd: the row range holds %d Gaussians, more than the capacity of %d rows the view was sized for" % (npts, P))
-            if overflow and bin_cap and longest > bin_cap:
-                scanned_only[0] = True  # a list that does not fit a direct bin: the repair run uses scanned lists (and _note_longest has set big_bins)
-            elif overflow and cap >= 0x7fffffff:
-                raise _too_many(R)
-            return bool(overflow), R
+        def relaunch(scanned_only):
+            return launch(*_plan(st, p_est, W, H, mode, scanned_only))
 
-        cap = _capacity_for(st, p_est)
-        box = None
+        plan = _plan(st, p_est, W, H, mode, False)
         dump = os.environ.get("GPSGS_DUMP_INPUTS")  # debugging aid: the inputs of the LAST forward entered, as an .npz (synchronises)
         if dump and rows is None:
             import numpy as _np
             _np.savez(dump, means3D=m3.cpu().numpy(), opacities=opa.cpu().numpy(),
                       **{k: v.cpu().numpy() for k, v in (("colors", col), ("scales", sca), ("rotations", rot), ("shs", sh), ("cov3D_precomp", cov)) if v is not None},
                       view=view.cpu().numpy(), proj=proj.cpu().numpy(), bg=bg.cpu().numpy(), W=W, H=H,
-                      tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy), scale_modifier=float(rs.scale_modifier), cap=cap, needs_grad=bool(needs_grad))
-        while True:
-            ws, nbytes, note, bin_cap = launch(cap)
-            if note is not None:
-                if _deferred_list() is not None:
-                    # checked when the enclosing defer_capacity_checks() exits (several views in flight); an overflow is repaired there, in
-                    # place: same output tensors, a larger workspace in ctx.ws_box
-                    box = [ws, cap, bin_cap]
+                      tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy), scale_modifier=float(rs.scale_modifier), cap=plan[0], needs_grad=bool(needs_grad))
+        note, cap, bin_cap = launch(*plan)
+        if note is None:
+            pass  # GPSGS_CHECK=none, or nothing to render
+        elif _deferred_list() is not None:
+            # checked when the enclosing defer_capacity_checks() exits (several views in flight); an overflow is repaired there, in place: same
+            # output tensors, a larger workspace in ctx.ws_box
+            def finish(note=note, cap=cap, bin_cap=bin_cap):
+                with torch.cuda.stream(cur_stream):
+                    _repair_loop(st, note, cur_stream, P, rows is not None, cap, bin_cap, relaunch)
 
-                    def finish(note=note):
-                        with torch.cuda.stream(cur_stream):
-                            while settle(note, box[1], box[2])[0]:
-                                box[1] = _capacity_for(st, p_est)  # the in-flight kernels of the failed attempt exit at once on the overflow flag
-                                box[0], _, note, box[2] = launch(box[1])
-
-                    _deferred_list().append(finish)
-                    break
-                if mode == "deferred":
-                    # never blocks: the notification (it lands ~40 us into this forward) is looked at by the next call on this device
-                    with _lock:
-                        st["pending"].append(("note", note, cur_stream, P if rows is None else None, dev.index))
-                    break
-                if not settle(note, cap, bin_cap)[0]:
-                    break
-                cap = _capacity_for(st, p_est)  # grown by _learn; the in-flight kernels of the failed attempt exit at once on the overflow flag
-                continue
-            if P == 0 or mode == "none":
-                break
-            cring = _ring(dev, "copy")
-            if mode == "deferred" and len(st["pending"]) >= cring.n - 1:
-                _drain_pending(st, block=True)  # never reuse a pinned slot that is still in flight
-            hdr, hdr_ptr, ev = cring.next()
-            _capi.check(lib.gsr_copy_header_async(_ptr(ws), hdr_ptr, stream), "gsr_copy_header_async")
-            ev.record(cur_stream)
-            if mode == "deferred":
-                with _lock:
-                    st["pending"].append(("ev", ev, hdr, P if rows is None else None))
-                break
-            ev.synchronize()
-            R, overflow, need = _decode(hdr)
-            npts = int(hdr[3]) & 0xffffffff
-            longest = (int(hdr[1]) >> 32) & 0xffffffff
-            _learn(st, R, need, npts if rows is not None else P, longest)
-            _note_longest(st, longest)
-            if not overflow:
-                break
-            if bin_cap and longest > bin_cap:
-                scanned_only[0] = True
-                continue  # re-run with scanned lists
-            if rows is not None and npts > P:
-                raise RuntimeError("gps_gaussian_amd: the row range holds %d Gaussians, more than the capacity of %d rows the view was sized for" % (npts, P))
-            if cap >= 0x7fffffff:
-                raise _too_many(R)
-            cap = _capacity_for(st, p_est)  # grown by _learn; re-run the whole (cheap) forward
+            _deferred_list().append(finish)
+            ctx.ws_box = box
+        elif mode == "deferred":
+            # never blocks: the notification (it lands ~40 us into this forward) is looked at by the next call on this device
+            with _lock:
+                st["pending"].append((note, cur_stream, P if rows is None else None))
+        else:
+            _repair_loop(st, note, cur_stream, P, rows is not None, cap, bin_cap, relaunch)
+        ws, cap, bin_cap = box  # (inside defer_capacity_checks(): still the first attempt's, a repair replaces them in ctx.ws_box)
     ctx.raster_settings = rs
     ctx.cap = cap
     ctx.bin_cap = bin_cap
     ctx.family = family  # the backward must repeat the forward's per-pixel decisions: same kernel family
     ctx.extra_flags = extra
     ctx.rows = rows
-    if box is not None:
-        ctx.ws_box = box
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
     return color, radii
 
@@ -703,19 +662,18 @@ def _fast_module():
     if os.environ.get("GPSGS_FAST", "1") == "0":
         return False
     if _fast is None:
-        if True:
-            import importlib.util
-            path = os.path.join(os.path.dirname(_capi.LIB_PATH), "_gpsgs_fast.so")
-            if not os.path.exists(path):
-                raise ImportError("gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` (or set GPSGS_FAST=0 "
-                                  "to use the Python host path)." % path)
-            _capi.lib()  # libgpsgs_hip.so first: the extension links against it
-            spec = importlib.util.spec_from_file_location("_gpsgs_fast", path)
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-            if mod.abi_version() != _capi.lib().gpsgs_abi_version():
-                raise ImportError("gps_gaussian_amd: %s was built against another ABI version" % path)
-            _fast = mod
+        import importlib.util
+        path = os.path.join(os.path.dirname(_capi.LIB_PATH), "_gpsgs_fast.so")
+        if not os.path.exists(path):
+            raise ImportError("gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` (or set GPSGS_FAST=0 "
+                              "to use the Python host path)." % path)
+        _capi.lib()  # libgpsgs_hip.so first: the extension links against it
+        spec = importlib.util.spec_from_file_location("_gpsgs_fast", path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        if mod.abi_version() != _capi.lib().gpsgs_abi_version():
+            raise ImportError("gps_gaussian_amd: %s was built against another ABI version" % path)
+        _fast = mod
     return _fast
 
 
@@ -724,7 +682,7 @@ def _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations
     Python path, which repairs it).  Policy decisions (capacity, list form, flags) are taken here, from the same per-device state."""
     F = _fast_module()
     env = os.environ
-    if (not F or rs.debug or _extra_flags or _deferred_list() is not None or env.get("GPSGS_CHECK", "sync") != "sync" or not _early_notify
+    if (not F or rs.debug or _extra_flags or _deferred_list() is not None or env.get("GPSGS_CHECK", "sync") != "sync"
             or env.get("GPSGS_DUMP_INPUTS") or not isinstance(means3D, torch.Tensor) or not means3D.is_cuda or torch.cuda.is_current_stream_capturing()):
         return None  # (under graph capture the Python path says what to do instead of spinning on a header that never arrives)
     dev = means3D.device
@@ -735,18 +693,14 @@ def _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations
     P = means3D.shape[0]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     flags = _composite_flag() | _wave_priority_flag(st, stream)
-    if not st.get("big_bins", False):
-        flags |= _capi.GSR_FLAG_NO_LARGE_SORT
-    cap = _capacity_for(st, P)
-    bin_cap = _bin_capacity(st, W, H)
+    cap, bin_cap, plan_flags = _plan(st, P, W, H, "sync", False)
     out = F.rasterize(means3D, means2D, colors_precomp, opacities, scales, rotations, rs.bg, rs.viewmatrix, rs.projmatrix, H, W, float(rs.tanfovx),
-                      float(rs.tanfovy), float(rs.scale_modifier), cap, bin_cap, st.get("longest", 0), flags)
+                      float(rs.tanfovy), float(rs.scale_modifier), cap, bin_cap, st.get("longest", 0), flags | plan_flags)
     if out is None:
         return None
     R, overflow, longest, slots, npts, nbytes, _wait_us = F.last_header()
     st["last_ws_bytes"] = nbytes
-    _learn(st, R, max(R, slots), P, longest)
-    _note_longest(st, longest)
+    _learn(st, _Header(R, overflow, max(R, slots), longest, npts), P)
     if overflow:
         return None  # nothing was rendered (the kernels exit on the flag): the Python path re-renders with what was just learnt
     if _debug_keep_ws:
@@ -854,8 +808,8 @@ def export_state(ws, P, W, H, cap, bin_cap=0):
     (bins x bin_cap entries, indexed by `ranges`)."""
     lib = _capi.lib()
     dev = ws.device
-    hdr = ws[:16].view(torch.int64).cpu()
-    R = int(hdr[0])
+    hdr = _header(ws[:32].cpu().numpy().view("uint32"))
+    R = hdr.R
     bx, by = ((W + 7) // 8 + 3) // 4 * 4, (H + 7) // 8   # padded bin grid (gsr_common.h)
     out = dict(
         depth=torch.empty(P, device=dev), xy=torch.empty(P, 2, device=dev), conic_opacity=torch.empty(P, 4, device=dev),
@@ -872,5 +826,5 @@ def export_state(ws, P, W, H, cap, bin_cap=0):
         out["point_list"] = out["point_list"][:R]
     out["num_rendered"] = R
     out["bx"], out["by"] = bx, by
-    out["overflow"] = int(hdr[1]) & 0xffffffff
+    out["overflow"] = hdr.overflow
     return out

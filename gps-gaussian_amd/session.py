@@ -47,7 +47,6 @@ class RasterSession:
                 self.grads[name] = self._gbuf[o:o + self.P * c].view(self.P, c)
                 o += P_ * c
         self.bin_cap = 0  # per-bin capacity of the current workspace's lists (0 = scanned lists; rasterizer._bin_capacity)
-        self._scanned_only = False  # the current view has shown a list too long for direct bins: its repair run uses scanned lists
 
     def _ensure_ws(self, cap, stream, bin_cap=0):
         """The workspace for `cap` instances, allocated on `stream` -- the stream its kernels are launched on.  (allocated under PyTorch's
@@ -89,64 +88,48 @@ class RasterSession:
         `with torch.cuda.stream(...)` saved, three times per view); default: the current stream.  The INPUTS (and, for backward(), dL_dpix)
         must already be ordered against that stream by the caller -- the session never inserts a wait; its own workspace is allocated on, and
         tied to, the streams it launches on."""
-        P, W, H, lib = self.P, self.W, self.H, self.lib
+        P = self.P
         ptrs = (self._chk(means3D, 3 * P, "means3D"), self._chk(colors, 3 * P, "colors"), self._chk(opacities, P, "opacities"),
                 self._chk(scales, 3 * P, "scales"), self._chk(rotations, 4 * P, "rotations"))
         cam = (self._chk(viewmatrix, 16, "viewmatrix"), self._chk(projmatrix, 16, "projmatrix"), self._chk(bg, 3, "bg"))
         fl = (float(scale_modifier), float(tanfovx), float(tanfovy))
         family = RZ._composite_flag() | (RZ._wave_priority_flag() if self.wave_priority else 0)
         self._in = (ptrs, fl, cam, family, (means3D, colors, opacities, scales, rotations, viewmatrix, projmatrix, bg))  # keeps the inputs alive
-        st = RZ._dev_state(self.dev)
         self._cur = stream if stream is not None else torch.cuda.current_stream(self.dev)
-        self._scanned_only = False
-        self._enqueue(max(self.cap, RZ._capacity_for(st, P)))
+        cap, bin_cap, plan_flags = self._plan(P == 0)  # (an empty view has no lists)
+        self._pending = self._enqueue(max(self.cap, cap), bin_cap, plan_flags)  # the workspace is reused while it is large enough
 
-    def _enqueue(self, cap):
+    def _plan(self, scanned_only):
+        return RZ._plan(RZ._dev_state(self.dev), self.P, self.W, self.H, "sync", scanned_only)
+
+    def _enqueue(self, cap, bin_cap, plan_flags):
+        """Enqueue the forward on self._cur.  -> its notify note (None: an empty view, nothing to check)"""
         P, W, H, lib = self.P, self.W, self.H, self.lib
         ptrs, fl, cam, family, _ = self._in
-        st = RZ._dev_state(self.dev)
         stream = self._cur.cuda_stream
-        flags = RZ._extra_flags | family
-        self._ensure_ws(cap, self._cur, 0 if (P == 0 or self._scanned_only) else RZ._bin_capacity(st, W, H))
+        flags = RZ._extra_flags | family | plan_flags
+        self._ensure_ws(cap, self._cur, bin_cap)
         if P == 0:
             _capi.check(lib.gsr_forward(P, W, H, *ptrs, *fl, *cam, self.color.data_ptr(), self.radii.data_ptr(), self.ws.data_ptr(),
                                         self.nbytes, cap, flags, stream), "gsr_forward")
-            self._pending = None
-            return
+            return None
         ring = RZ._ring(self.dev)
-        slot, hdr, w32, hdr_ptr, seq = ring.acquire_notify()
-        skip_large = not st.get("big_bins", False)
-        f = (flags & ~_capi.GSR_FLAG_NO_LARGE_SORT) | (_capi.GSR_FLAG_NO_LARGE_SORT if skip_large else 0)
-        ext = RZ._ext(None, st.get("longest", 0), None, self.bin_cap)  # work order: longest lists first, relative to the longest list seen on this device
+        note, hdr_ptr = ring.acquire_notify()
+        ext = RZ._ext(None, RZ._dev_state(self.dev).get("longest", 0), None, bin_cap)  # work order: longest lists first, relative to the longest list seen on this device
         rc = lib.gsr_forward_ex(P, W, H, *ptrs, *fl, *cam, self.color.data_ptr(), self.radii.data_ptr(), self.ws.data_ptr(),
-                                self.nbytes, cap, f, stream, hdr_ptr, seq, C.byref(ext))
+                                self.nbytes, cap, flags, stream, hdr_ptr, note[3], C.byref(ext))
         if rc != 0:
-            ring.release(slot)
+            ring.release(note[1])
         _capi.check(rc, "gsr_forward_ex")
-        self._pending = (slot, hdr, w32, seq)
+        return note
 
     def forward_end(self):
         """Second half of forward(): wait until the binning scan has published the instance count (typically well before the forward has
-        finished), re-render with a larger workspace if it overflowed.  -> (color, radii)"""
-        st = RZ._dev_state(self.dev)
-        while self._pending is not None:
-            slot, hdr, w32, seq = self._pending
-            try:
-                RZ._wait_notify(w32, seq, self._cur)
-                R, overflow, need = RZ._decode(hdr)
-                longest = int(w32[3])
-            finally:
-                RZ._ring(self.dev).release(slot)
-            RZ._learn(st, R, need, self.P, longest)
-            RZ._note_longest(st, longest)
-            if not overflow:
-                self._pending = None
-                break
-            if self.bin_cap and longest > self.bin_cap:
-                self._scanned_only = True  # a list that does not fit a direct bin: the re-run below uses scanned lists
-            elif self.cap >= 0x7fffffff:
-                raise RuntimeError("gps_gaussian_amd: this view needs %d (Gaussian, bin) instances, more than the 2^31 - 1 the workspace layout can address" % R)
-            self._enqueue(RZ._capacity_for(st, self.P))  # a larger workspace (allocated on the view's own stream); the in-flight kernels of the failed attempt exit at once on the overflow flag
+        finished), re-render with a larger workspace if it overflowed (rasterizer._repair_loop).  -> (color, radii)"""
+        note, self._pending = self._pending, None
+        if note is not None:
+            RZ._repair_loop(RZ._dev_state(self.dev), note, self._cur, self.P, False, self.cap, self.bin_cap,
+                            lambda scanned_only: (self._enqueue(*self._plan(scanned_only)), self.cap, self.bin_cap))
         return self.color, self.radii
 
     def backward(self, dL_dpix, color_grad=True, stream=None):

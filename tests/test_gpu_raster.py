@@ -307,13 +307,10 @@ def test_long_lists_with_equal_depths_come_out_in_index_order(levels, n):
     assert np.abs(img - oimg).max(0)[solid].max() <= RGB_TOL
 
 
-@pytest.mark.parametrize("early", [True, False], ids=["early-notify", "header-copy"])
-def test_capacity_overflow_is_detected_and_repaired(monkeypatch, early):
-    """Both sync-mode checks: the scan kernel's direct store to pinned memory (gsr_forward_notify, default) and the
-    end-of-forward header copy + event (GPSGS_EARLY_NOTIFY=0)."""
+def test_capacity_overflow_is_detected_and_repaired(monkeypatch):
+    """The sync-mode check: the scan kernel's direct store to pinned memory (gsr_forward_notify) reports the overflow, the view is re-run."""
     from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import synthetic as S
-    monkeypatch.setattr(RZ, "_early_notify", early)
     monkeypatch.setenv("GPSGS_LISTS", "scanned")  # (an inference view with direct lists has no instance capacity to overflow: its twin is test_direct_lists_*)
     g = S.make_uniform_cloud(5000, 128, 96, seed=9, scale_med=0.05)
     o, oimg, _ = oracle_render(g, "f32")

@@ -21,7 +21,6 @@ t0 = time.time()
 ref = {}
 for it in range(iters):
     os.environ["GPSGS_CHECK"] = "deferred" if (it // 50) % 3 == 2 else "sync"
-    RZ._early_notify = (it // 25) % 2 == 0
     k = int(rng.integers(len(scenes)))
     t, rast, gout, m2 = scenes[k]
     if it % 97 == 0 and os.environ["GPSGS_CHECK"] == "sync":

@@ -113,7 +113,12 @@ def main():
     if args.hint is not None:
         RZ._dev_state(dev)["longest"] = args.hint
         real = RZ._learn
-        RZ._learn = lambda st, R, need, P_, longest=None: real(st, R, need, P_, None)  # keep the forced hint
+
+        def keep_hint(st, h, P_):
+            real(st, h, P_)
+            st["longest"] = args.hint  # keep the forced hint
+
+        RZ._learn = keep_hint
     NB = (((rr + 7) // 8 + 3) // 4 * 4) * ((rr + 7) // 8)
     rows = torch.zeros((2 * NB, 4), dtype=torch.int64, device=dev)
     lib = _capi.lib()
