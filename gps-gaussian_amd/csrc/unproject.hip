@@ -8,24 +8,17 @@
 // Backward: d_flow = (g_depth - z^2 * g_xyz . R^T[ax, ay, 1]) * mask / Tf_x with ax = (u + 0.5 - cx) / fx.
 // HBM-bound: 8 B read + 17 B written per pixel forward.  Evaluated without FMA contraction in the reference's operation
 // order: depth and valid are bit-identical to torch's, xyz differs only by the summation order of the 3x3 product.
-#include "gsr_common.h"
+#include "unproject_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-struct UnprojCam {  // per batch element, host-filled
-    float offset, tf, fx, fy, cx, cy;
-    float Rt[9];   // R^T row-major
-    float Rtt[3];  // R^T t
-};
 constexpr int MAXB = 16;
 struct UnprojArgs {
     int B, S;
     UnprojCam cam[MAXB];
 };
-
-__device__ __forceinline__ UnprojCam cam_from_device(const float *__restrict__ cams, int b);
 
 __global__ __launch_bounds__(256) void k_unproject_fwd(UnprojArgs a, const float *__restrict__ cams_dev, const float *__restrict__ flow, const float *__restrict__ mask,
                                                       int64_t mask_bstride, float *__restrict__ depth, float *__restrict__ xyz,
@@ -34,18 +27,13 @@ __global__ __launch_bounds__(256) void k_unproject_fwd(UnprojArgs a, const float
     if (pix >= S2) return;
     const UnprojCam c = cams_dev ? cam_from_device(cams_dev, b) : a.cam[b];
     const int v = pix / a.S, u = pix - v * a.S;
-    const float disparity = c.offset - flow[(size_t)b * S2 + pix];
-    float d = -disparity / c.tf;
-    d = d * mask[(size_t)b * mask_bstride + pix];
+    const float d = up_inverse_depth(c, flow[(size_t)b * S2 + pix], mask[(size_t)b * mask_bstride + pix]);
     depth[(size_t)b * S2 + pix] = d;
     valid[(size_t)b * S2 + pix] = d != 0.0f;
-    const float z = 1.0f / (d + 1e-8f);
-    const float X = ((float)u + 0.5f - c.cx) * z / c.fx;
-    const float Y = ((float)v + 0.5f - c.cy) * z / c.fy;
+    float w[3];
+    up_world_point(c, u, v, d, w);
     float *o = xyz + ((size_t)b * S2 + pix) * 3;
-    o[0] = (c.Rt[0] * X + c.Rt[1] * Y + c.Rt[2] * z) - c.Rtt[0];
-    o[1] = (c.Rt[3] * X + c.Rt[4] * Y + c.Rt[5] * z) - c.Rtt[1];
-    o[2] = (c.Rt[6] * X + c.Rt[7] * Y + c.Rt[8] * z) - c.Rtt[2];
+    o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
 }
 
 __global__ __launch_bounds__(256) void k_unproject_bwd(UnprojArgs a, const float *__restrict__ cams_dev, const float *__restrict__ depth, const float *__restrict__ mask,
@@ -70,25 +58,10 @@ __global__ __launch_bounds__(256) void k_unproject_bwd(UnprojArgs a, const float
     d_flow[(size_t)b * S2 + pix] = g * mask[(size_t)b * mask_bstride + pix] / c.tf;
 }
 
-// The same per-sample constants from camera arrays that live in DEVICE memory: cams[b] = {ref_intr 3x3, intr 3x3, extr 3x4 row-major, Tf_x} = 31 floats
-// (wave-uniform scalar loads; the arithmetic of fill() below, operation for operation, so both forms give the same bits).  A caller whose cameras
-// already sit on the GPU (the reference moves every item of its data dict there, train_stage2.py:154-156) then never has to read them back: reading
-// them on the host costs a device synchronisation in the MIDDLE of the network forward (measured in BASELINE config 3 with the import hook: 13.4
-// instead of 17.2 views/s inside a sample, the host could no longer run ahead of the GPU).
-constexpr int CAM_FLOATS = 31;
-__device__ __forceinline__ UnprojCam cam_from_device(const float *__restrict__ cams, int b) {
-    const float *Kr = cams + (size_t)b * CAM_FLOATS, *K = Kr + 9, *E = Kr + 18;
-    UnprojCam c;
-    c.offset = Kr[2] - K[2]; c.tf = Kr[30]; c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) c.Rt[i * 3 + j] = E[j * 4 + i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) c.Rtt[i] = c.Rt[i * 3] * E[3] + c.Rt[i * 3 + 1] * E[7] + c.Rt[i * 3 + 2] * E[11];
-    return c;
-}
-
+// The per-sample constants can also come from camera arrays in DEVICE memory (cam_from_device, unproject_common.h): a caller whose cameras already
+// sit on the GPU (the reference moves every item of its data dict there, train_stage2.py:154-156) then never has to read them back: reading them on
+// the host costs a device synchronisation in the MIDDLE of the network forward (measured in BASELINE config 3 with the import hook: 13.4 instead of
+// 17.2 views/s inside a sample, the host could no longer run ahead of the GPU).
 bool fill(UnprojArgs &a, int B, int S, const float *ref_intr, const float *intr, const float *extr, const float *tf) {
     if (B < 0 || B > MAXB || S < 0) return false;
     a.B = B; a.S = S;

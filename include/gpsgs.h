@@ -27,6 +27,8 @@
  *       the per-sample flatten + boolean-mask gather + concat + rgb affine of lib/GaussianRender.py:15-34.
  *   up_unproject_forward / up_unproject_backward (+ _dev: cameras in device memory)
  *       flow2depth + depth2pc + the validity test: lib/utils.py:113-120, :88-110, lib/network.py:66-69.
+ *   up_zsplat, up_flow2render_dev (+ up_splat_scratch_bytes)
+ *       the z-buffer splat of lib/TaichiRender.py:13-24 and the whole TaichiRenderBatch.flow2render (:26-60), stage-1 validation render.
  *   fl_l1_ssim_forward / fl_l1_ssim_backward
  *       l1_loss + ssim of lib/loss.py:36-83 (and their autograd backward), called at train_stage2.py:70-72.
  */
@@ -45,7 +47,8 @@ extern "C" {
                                   inputs of the upstream module, + their gradients); zero-initialised it means what version 2 meant
                                4: + gsr_mark_visible (upstream GaussianRasterizer.markVisible); gsr_debug_count_records takes workspace_bytes;
                                   DIRECT bin lists: GsrViewExt.reserved0 became bin_capacity (0 = what version 3 did), gsr_workspace_bytes_ex,
-                                  gsr_direct_lists_ok; gsr_export_state / gsr_debug_count_records take bin_capacity */
+                                  gsr_direct_lists_ok; gsr_export_state / gsr_debug_count_records take bin_capacity
+                               still 4 after up_splat_scratch_bytes, up_zsplat, up_flow2render_dev: purely additive, nothing existing changed */
 
 enum {
     GPSGS_OK = 0,
@@ -308,6 +311,26 @@ int up_unproject_forward_dev(int B, int S, const float *flow, const float *mask,
                              uint8_t *valid, void *stream);
 int up_unproject_backward_dev(int B, int S, const float *depth, const float *mask, int64_t mask_batch_stride, const float *cams_dev, const float *g_depth,
                               const float *g_xyz, int64_t gx_batch_stride, int64_t gx_pixel_stride, int64_t gx_channel_stride, float *d_flow, void *stream);
+
+/* ---- z-buffer point splat (the stage-1 validation render, lib/TaichiRender.py) ---------------------------------------------------------
+ * Per target pixel the result of running the points in sequence (view 0 in index order, then view 1, ...) with
+ * `if z >= depth[px]: depth[px] = z; colour[px] = rgb`, px = clamp(trunc(x|y), 0, res-1) with saturating truncation (NaN -> 0); points with
+ * mask < 0.5 or NaN z are skipped.  Deterministic (the reference's separate colour write races); every view and sample in one scatter launch.
+ * Device scratch: up_splat_scratch_bytes(B, res) (one 64-bit key per target pixel).  V * N + 1 must fit in 32 bits.
+ * up_zsplat: render_respective_color; pts [V][B][N][6] = (x, y, z, r, g, b), mask [V][B][N]; depth [B][res][res] and color [B][3][res][res]
+ *   are updated IN PLACE.
+ * up_flow2render_dev: TaichiRenderBatch.flow2render fused -- per source pixel of the two views (l = lmain, r = rmain): flow2depth, valid =
+ *   depth != 0, depth2pc (the bits of up_unproject_forward_dev), perspective into the novel view with calib = intr @ extr, z <- 1 / (z + 1e-8),
+ *   then the splat; colours straight from img_l / img_r [B][3][S][S].  flow [B][S][S], mask [B][..] with mask_batch_stride; cams_dev[2][B][31] as
+ *   up_unproject_forward_dev's (all of lmain, then all of rmain); novel_dev[B][21] = {intr 3x3, extr rows 0..2 (3x4)}: nothing is read on the
+ *   host.  Writes all of img_pred [B][3][res][res] (-1 where no point lands).  pts_out (optional, NULL in normal use) [2][B][S*S][3]: each
+ *   point's projected (x, y, 1/z), NaN for invalid points. */
+size_t up_splat_scratch_bytes(int B, int res);
+int up_zsplat(int V, int B, int N, int res, const float *pts, const float *mask, float *depth, float *color, void *scratch, size_t scratch_bytes,
+              void *stream);
+int up_flow2render_dev(int B, int S, int res, const float *flow_l, const float *flow_r, const float *mask_l, const float *mask_r,
+                       int64_t mask_batch_stride, const float *img_l, const float *img_r, const float *cams_dev, const float *novel_dev, void *scratch,
+                       size_t scratch_bytes, float *img_pred, float *pts_out, void *stream);
 
 /* ---- 1-D correlation sampler ----------------------------------------------------------------------------------
  * volume[N,H1,W1,W2], coords[N,H1,W1] fp32 (channel 0 of the reference's [N,1,H1,W1]), out[N,2r+1,H1,W1].

@@ -4,6 +4,7 @@
     python tools/run_reference.py interp [--samples 2] [--views 5] [--res 1024]      test_view_interp.py   (config 3)
     python tools/run_reference.py real [--samples 2] [--ratio 0.5] [--res 1024]       test_real_data.py     (one novel view per frame)
     python tools/run_reference.py train  [--steps 12] [--batch 2] [--res 1024]       train_stage2.py       (config 4, one process)
+    python tools/run_reference.py stage1 [--steps 3] [--batch 2] [--res 1024]        train_stage1.py       (RAFT-Stereo stage + its validation render)
 
 The reference is found by tools/refenv.reference_dir(): --reference, $GPSGS_REFERENCE or /root/reference -- a CHECKOUT (nothing of the reference
 travels to the GPU box: this tool runs where a checkout and an MI355X coexist).  The script is executed as `__main__` by runpy -- the same code object
@@ -342,9 +343,52 @@ def ddp(args):
     return out
 
 
+def stage1(args):
+    """train_stage1.py as __main__: a few steps of the reference's Trainer on the synthetic set, then its run_eval, whose novel-view JPEG comes from
+    lib/TaichiRender.py -- served by this package's GPU splat (GPSGS_ACCELERATE=splat; the reference's file imports taichi, which has no ROCm build)."""
+    import glob
+
+    import torch
+
+    ref = refenv.reference_dir(args.reference)
+    if ref is None:
+        raise SystemExit("run_reference: no reference checkout (--reference, $GPSGS_REFERENCE, /root/reference)")
+    refenv.activate(ref)
+    work = os.path.abspath(args.work)
+    data_root = _dataset(work, args.res, args.train_samples, 2, args.fill)
+    steps = max(2, args.steps)
+    eval_freq = args.eval_freq or steps - 1   # run_eval after step `eval_freq` (train_stage1.py:86: total_steps % eval_freq == 0, total_steps > 0)
+    refenv.make_workdir(ref, work, {"batch_size": args.batch, "num_steps": steps, "dataset": {"src_res": args.res, "data_root": data_root},
+                                    "record": {"loss_freq": steps, "eval_freq": eval_freq}}, yaml_name="stage1.yaml")
+    os.chdir(work)
+    import lib.train_recoder as TR
+    evals = []
+    real_write = TR.Logger.write_dict
+
+    def write_dict(self, results, write_step):
+        evals.append({"step": int(write_step), **{k: float(v) for k, v in results.items()}})
+        return real_write(self, results, write_step)
+    TR.Logger.write_dict = write_dict
+    t0 = time.perf_counter()
+    runpy.run_path(refenv.script(ref, "train_stage1"), run_name="__main__")
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    TR.Logger.write_dict = real_write
+    jpegs = sorted(glob.glob(os.path.join(work, "experiments", "*", "show", "*.jpg")), key=os.path.getmtime)
+    acc = _accel_report()
+    out = {"mode": "stage1", "reference": ref, "script": os.path.basename(refenv.script(ref, "train_stage1")), "res": args.res, "batch": args.batch,
+           "steps": steps, "wall_s": round(wall, 2), "evals": evals,
+           "val_epe": evals[-1].get("val_epe") if evals else None, "val_1pix": evals[-1].get("val_1pix") if evals else None,
+           "jpeg": jpegs[-1] if jpegs else None, "accelerate": acc}
+    if not jpegs or not acc["calls"].get("splat"):
+        out["error"] = "no validation image from the GPU splat"
+    print(json.dumps(out))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("mode", choices=("interp", "real", "train", "ddp"))
+    ap.add_argument("mode", choices=("interp", "real", "train", "ddp", "stage1"))
     ap.add_argument("--reference", default=None)
     ap.add_argument("--work", default=os.environ.get("GPSGS_REF_WORK", "/tmp/gpsgs_ref_work"))
     ap.add_argument("--res", type=int, default=1024, help="source resolution (dataset.src_res); the render is 2x that (use_hr_img)")
@@ -360,9 +404,11 @@ def main():
     ap.add_argument("--accelerate", default=None, help="value for GPSGS_ACCELERATE (gps-gaussian_amd/accelerate.py: e.g. 'all' or 'pack,loss'): the opt-in "
                                                        "import hook that lets the UNMODIFIED script reach the fused pack / loss / corr / upsample / unproject kernels")
     args = ap.parse_args()
+    if args.mode == "stage1":   # the splat is what lets train_stage1.py import at all; --accelerate adds the fused features on top
+        args.accelerate = "splat" if not args.accelerate else args.accelerate + ",splat"
     if args.accelerate is not None:
         os.environ["GPSGS_ACCELERATE"] = args.accelerate   # read by the drop-in shims when the reference imports them
-    return {"interp": interp, "real": real, "train": train, "ddp": ddp}[args.mode](args)
+    return {"interp": interp, "real": real, "train": train, "ddp": ddp, "stage1": stage1}[args.mode](args)
 
 
 if __name__ == "__main__":
