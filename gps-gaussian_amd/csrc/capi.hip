@@ -156,6 +156,13 @@ extern "C" size_t gsr_workspace_bytes_ex(int P, int width, int height, int64_t i
     return forward_only ? L.total_fwd : L.total;
 }
 
+extern "C" size_t gsr_workspace_bytes_depth_alpha(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
+    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
+    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
+    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    return forward_only ? L.total_fwd : L.total_extra;
+}
+
 extern "C" size_t gsr_workspace_bytes_forward_only(int P, int width, int height, int64_t instance_capacity) {
     if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
     return gsr_layout(P, width, height, instance_capacity).total_fwd;
@@ -168,6 +175,10 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
                               void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext) {
     const uint32_t *row_range = ext ? ext->row_range : nullptr;
     const uint32_t order_hint = ext ? ext->order_hint : 0u;
+    // opt-in depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
+    float *out_depth = ext ? ext->out_depth : nullptr, *out_alpha = ext ? ext->out_alpha : nullptr;
+    if ((reinterpret_cast<uintptr_t>(out_depth) | reinterpret_cast<uintptr_t>(out_alpha)) & 3u) return GPSGS_E_INVALID;
+    if (out_depth || out_alpha) flags &= ~GSR_FLAG_COMPOSITE_TILES;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0 || instance_capacity > 0x7fffffffLL) return GPSGS_E_INVALID;
     if (width > 65535 * GSR_TILE || height > 65535 * GSR_TILE) return GPSGS_E_INVALID;
     if (!out_color || !workspace) return GPSGS_E_INVALID;
@@ -219,6 +230,8 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
     }
     if (P == 0) {  // upstream returns its zero-initialised image (NOT the background) when there is nothing to draw
         if (hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (out_depth && hipMemsetAsync(out_depth, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (out_alpha && hipMemsetAsync(out_alpha, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (hipMemsetAsync(bin_offset, 0, (size_t)(L.NB + 1) * 4, s) != hipSuccess) return GPSGS_E_LAUNCH;
         return check(s, flags);
     }
@@ -322,7 +335,8 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
             gsr_launch_composite_fwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, training,
                                            (flags & GSR_FLAG_WAVE_PRIORITY) != 0, fused_sort ? keys : nullptr, s);
         else
-            gsr_launch_composite_fwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, s);
+            gsr_launch_composite_fwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, out_depth,
+                                     out_alpha, s);
     }
     return check(s, flags);
 }
@@ -351,6 +365,11 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
                                float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
     (void)colors; (void)opacities;  // already folded into the splat records of the workspace
+    // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
+    const float *dL_ddepth = ext ? ext->dL_ddepth : nullptr, *dL_dalpha = ext ? ext->dL_dalpha : nullptr;
+    const bool extras = dL_ddepth || dL_dalpha;
+    if ((reinterpret_cast<uintptr_t>(dL_ddepth) | reinterpret_cast<uintptr_t>(dL_dalpha)) & 3u) return GPSGS_E_INVALID;
+    if (extras) flags &= ~GSR_FLAG_COMPOSITE_TILES;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
     if (P == 0) return GPSGS_OK;
     const float *shs = ext ? ext->shs : nullptr, *cov3D_precomp = ext ? ext->cov3D_precomp : nullptr;
@@ -362,7 +381,7 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     const uint32_t bin_cap = ext ? ext->bin_capacity : 0u;  // must be what the forward was given
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
-    if (workspace_bytes < L.total) return GPSGS_E_WORKSPACE;
+    if (workspace_bytes < (extras ? L.total_extra : L.total)) return GPSGS_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const GsrHeader *hdr = reinterpret_cast<const GsrHeader *>(at(workspace, L.header));
     const GsrBins bins = {reinterpret_cast<const uint32_t *>(at(workspace, L.bin_offset)), reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count)),
@@ -377,6 +396,7 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     uint8_t *inst_valid = reinterpret_cast<uint8_t *>(at(workspace, L.inst_valid));
     float *inst_dop = reinterpret_cast<float *>(at(workspace, L.inst_dop));
     GsrGradAcc *inst_grad = reinterpret_cast<GsrGradAcc *>(at(workspace, L.inst_grad));
+    float *inst_ddepth = extras ? reinterpret_cast<float *>(at(workspace, L.inst_ddepth)) : nullptr;
 
     // goff / gscan_part / cleared inst_valid were produced by the matching gsr_forward (training workspace)
     int rc;
@@ -389,7 +409,8 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
             gsr_launch_composite_bwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
                                            (flags & GSR_FLAG_NO_COLOR_GRAD) == 0, (flags & GSR_FLAG_WAVE_PRIORITY) != 0, s);
         else
-            gsr_launch_composite_bwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr, s);
+            gsr_launch_composite_bwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
+                                     dL_ddepth, dL_dalpha, inst_ddepth, s);
     }
     if ((rc = check(s, flags)) != GPSGS_OK) return rc;
     GsrBwdParams b;
@@ -403,6 +424,7 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     b.shs = shs; b.campos = shs ? ext->campos : nullptr; b.cov3D_precomp = cov3D_precomp;
     b.sh_degree = shs ? ext->sh_degree : 0u; b.sh_coeffs = shs ? ext->sh_coeffs : 0u;
     b.dL_dsh = shs ? ext->dL_dsh : nullptr; b.dL_dcov3D = cov3D_precomp ? ext->dL_dcov3D : nullptr;
+    b.inst_ddepth = inst_ddepth;
     b.dop_in_record = ((flags & GSR_FLAG_COMPOSITE_TILES) && (flags & GSR_FLAG_NO_COLOR_GRAD)) ? 1 : 0;  // what k_composite_bwd_tiles<false> just wrote
     {
         trace("preprocess_bwd", P, width, height, (long long)instance_capacity, flags);

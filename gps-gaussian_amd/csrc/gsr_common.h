@@ -37,6 +37,8 @@
 //                  The other way round -- records in sorted-list order, written coalesced and gathered per Gaussian -- made every
 //                  gather pull a 128-byte line for 48 useful bytes (measured: 253 MB fetched per launch against 127 MB
 //                  algorithmic): scattered READS are what costs on this memory system, scattered writes cost the sectors they touch.
+//   --- depth / alpha tail (only in a workspace sized with gsr_workspace_bytes_depth_alpha; every offset above is unchanged) ---
+//   inst_ddepth[cap] the tenth per-instance sum, dL/dz (the depth map's gradient reaching the view-space depth), at the same slot as inst_dop
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -90,6 +92,7 @@ struct GsrLayout {
     int64_t key_cap;   // entries of keys / point_list: the instance capacity, or NB * bin_cap
     size_t total_fwd;  // bytes a forward-only workspace needs
     size_t goff, gscan_part, gprefix, inst_valid, inst_dop, inst_grad, total;
+    size_t inst_ddepth, total_extra;  // depth / alpha backward: dL/dz per instance slot behind everything else; bytes such a workspace needs
     int gx, gy;   // 16x16 tile grid (upstream semantics)
     int bx, by;   // bin grid: bx = ceil(W/8) rounded up to a multiple of 4, by = ceil(H/8)
     int bx_real;  // ceil(W/8)
@@ -148,6 +151,8 @@ static inline GsrLayout gsr_layout(int P, int W, int H, int64_t cap, uint32_t bi
     L.inst_dop = o;   o = gsr_align_up(o + c * 4);
     L.inst_grad = o;  o = gsr_align_up(o + c * sizeof(GsrGradAcc));
     L.total = o;
+    L.inst_ddepth = o; o = gsr_align_up(o + c * 4);
+    L.total_extra = o;
     return L;
 }
 
@@ -507,11 +512,13 @@ void gsr_launch_sort_direct(int NB, GsrBins bins, const uint32_t *wg_order, uint
 #define GSR_DIRECT_MAX_CAP 1024    // ... and a bin's list is sorted by ONE wave (k_sort_wave's classes)
 void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
                               const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib, const GsrHeader *hdr,
-                              uint8_t *inst_valid /* training workspace: the record flags are cleared here; NULL otherwise */, hipStream_t s);
+                              uint8_t *inst_valid /* training workspace: the record flags are cleared here; NULL otherwise */,
+                              float *out_depth, float *out_alpha /* [H, W] each, NULL = not wanted; either set: the EXTRA instantiation */, hipStream_t s);
 void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
                               const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T, const uint32_t *n_contrib,
                               const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop, GsrGradAcc *inst_grad, const GsrHeader *hdr,
-                              hipStream_t s);
+                              const float *dL_ddepth, const float *dL_dalpha /* [H, W], NULL = zero */,
+                              float *inst_ddepth /* non-NULL: the EXTRA instantiation, which writes dL/dz per record slot */, hipStream_t s);
 // development knob: GPSGS_DEBUG_LDS_PAD=<bytes> of unused dynamic LDS per compositing workgroup (caps the waves resident per CU, to
 // measure how the kernels scale with occupancy); 0 / unset in normal use
 #include <stdlib.h>
@@ -546,6 +553,7 @@ struct GsrBwdParams {
     const float *shs, *campos, *cov3D_precomp;  // as in GsrFwdParams
     uint32_t sh_degree, sh_coeffs;
     float *dL_dsh, *dL_dcov3D;  // [rows, sh_coeffs, 3], [rows, 6]: written when the matching input is given
+    const float *inst_ddepth;   // non-NULL: the records carry dL/dz (depth / alpha backward) -> dL/dmeans3D += dL/dz * viewmatrix[:, 2]
     int dop_in_record;          // the records were written without colour sums (tile family + GSR_FLAG_NO_COLOR_GRAD): dL/dopacity is their first float, inst_dop is not read
     float fx, fy;               // as in GsrFwdParams: set by gsr_launch_preprocess_bwd
 };

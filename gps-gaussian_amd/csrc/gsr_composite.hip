@@ -25,26 +25,37 @@
 
 namespace {
 
+// EXTRA: the opt-in depth and alpha maps (GsrViewExt.out_depth / out_alpha) -- two more channels of the same blend, background 0:
+// depth = sum z_i alpha_i T_i (z_i = the view-space depth in the splat record's `depth` slot), alpha = sum alpha_i T_i.  The record already carries
+// z next to b, so the gather is the same 48-byte record; only one LDS word per staged splat and two accumulators are added.
+template <bool EXTRA>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
                                                        float *__restrict__ out_color, float *__restrict__ final_T,
-                                                       uint32_t *__restrict__ n_contrib, const GsrHeader *__restrict__ hdr, uint8_t *__restrict__ inst_valid) {
+                                                       uint32_t *__restrict__ n_contrib, const GsrHeader *__restrict__ hdr, uint8_t *__restrict__ inst_valid,
+                                                       float *__restrict__ out_depth, float *__restrict__ out_alpha) {
     __shared__ float4 sA[WAVES][WAVE];
     __shared__ float4 sB[WAVES][WAVE];
     __shared__ float sC[WAVES][WAVE];
+    __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
     const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
     const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
     if (hdr->overflow) {  // nothing can be rendered from truncated lists: a deterministic zero image instead of uninitialised memory
         fwd_write_blank(g, W, H, out_color, final_T, n_contrib);
+        if (EXTRA && g.inside) {
+            const size_t q = (size_t)g.py * W + g.px;
+            if (out_depth) out_depth[q] = 0.f;
+            if (out_alpha) out_alpha[q] = 0.f;
+        }
         return;
     }
     clear_record_flags(inst_valid, hdr, (int)threadIdx.x, 64 * WAVES);
     const float pxf = (float)g.px, pyf = (float)g.py;
     float4 *wA = sA[g.wid], *wB = sB[g.wid];
-    float *wC = sC[g.wid];
+    float *wC = sC[g.wid], *wD = sD[g.wid];
 
-    float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+    float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, CD = 0.f, CA = 0.f;
     uint32_t last = 0;      // 1-based list position of the last splat that contributed (n_contrib), up to the previous round
     uint32_t last_rnd = 0;  // ... 1-based slot of the last contributor inside the current round (0: none): an inline constant per select
     // Per-lane predicates live as wave-uniform 64-bit masks in SGPRs and are combined on the scalar unit: one v_cmp per test, never a
@@ -54,10 +65,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r0), r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r1);
 
     float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-    float nC = 0.f;
+    float nC = 0.f, nD = 0.f;
     if (r0 + g.lane < r1) {  // prefetch round 0
         const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[r0 + g.lane]);
         nA = s[0]; nB = s[1]; nC = s[2].x;
+        if (EXTRA) nD = s[2].y;
     }
     for (uint32_t base = r0; base < r1; base += WAVE) {
         if (active == 0ull) break;  // every pixel of this bin is saturated (or outside the image)
@@ -65,12 +77,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
         wA[g.lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);  // conic pre-scaled for gsr_power2
         wB[g.lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
         wC[g.lane] = nC;
+        if (EXTRA) wD[g.lane] = nD;
         wave_sync_lds();
         const uint32_t nk = base + WAVE + g.lane;
         nB.y = 0.f;  // a slot without a splat blends nothing (opacity 0 -> alpha 0 < 1/255; stale x, y, conic stay finite)
         if (nk < r1) {  // prefetch the next round while this one is blended
             const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[nk]);
             nA = s[0]; nB = s[1]; nC = s[2].x;
+            if (EXTRA) nD = s[2].y;
         }
         const int cnt = (int)min((uint32_t)WAVE, r1 - base);
         // Branch-free blend in groups of 8 (the tail group is padded by opacity-0 slots; 4 and 16 measured slower); between groups one
@@ -97,6 +111,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                     C0 += b.z * w;
                     C1 += b.w * w;
                     C2 += c2 * w;
+                    if (EXTRA) {
+                        CD += wD[j] * w;  // the same contraction as a colour channel: fma(z, w, CD)
+                        CA += w;          // alpha as the sum of the weights (its gradient then follows the colour recurrence), not 1 - T
+                    }
                     T = use ? test_T : T;
                     last_rnd = use ? (uint32_t)(j + 1) : last_rnd;
                 }
@@ -115,20 +133,32 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
         out_color[q] = C0 + T * (bgs * bg[0]);
         out_color[npix + q] = C1 + T * (bgs * bg[1]);
         out_color[2 * npix + q] = C2 + T * (bgs * bg[2]);
+        if (EXTRA) {  // background 0 (a view without Gaussians gives 0 too: CD = CA = 0)
+            if (out_depth) out_depth[q] = CD;
+            if (out_alpha) out_alpha[q] = CA;
+        }
     }
 }
 
+// EXTRA: the depth / alpha channels' upstream gradients (either may be NULL = zero).  They enter the scalar recurrence as a colour channel with
+// c = z resp. c = 1 and background 0 would: cd gains z dL/ddepth + dL/dalpha, so dL/dalpha_i -- and with it dL/dopacity, dL/dconic, dL/dmean2D
+// -- folds into the existing record's sums.  The tenth per-(pixel, splat) term, dL/dz_i = sum_p w dL/ddepth, is row-reduced (4 DPP adds) beside
+// the nine-term reduce-scatter; its 4 row sums are parked in a fourth float4 per staged splat and flushed as inst_ddepth[slot] (no atomics).
+template <bool EXTRA>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
                                                        const float *__restrict__ dL_dpix, const float *__restrict__ final_T,
                                                        const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ goff,
                                                        const uint32_t *__restrict__ gpart, uint8_t *__restrict__ inst_valid, float *__restrict__ inst_dop,
-                                                       GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr) {
+                                                       GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr,
+                                                       const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, float *__restrict__ inst_ddepth) {
+    constexpr int REC = EXTRA ? 4 : 3;  // float4s per staged splat in sAcc
     __shared__ float4 sA[WAVES][WAVE];
     __shared__ float4 sB[WAVES][WAVE];
     __shared__ float sC[WAVES][WAVE];
-    __shared__ float4 sAcc[WAVES][WAVE * 3];  // per staged splat: {dr,dg,db,dmx | dmy,cxx,cxy,cyy | 4 row sums of dop}
+    __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
+    __shared__ float4 sAcc[WAVES][WAVE * REC];  // per staged splat: {dr,dg,db,dmx | dmy,cxx,cxy,cyy | 4 row sums of dop (| 4 row sums of dz)}
     if (hdr->overflow) return;
     const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
     if (list_pos >= hdr->num_busy_wgs) return;  // idle workgroups sit at the end of wg_order
@@ -138,7 +168,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
     const float pxf = (float)g.px, pyf = (float)g.py;
     const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
     float4 *wA = sA[g.wid], *wB = sB[g.wid], *wAcc = sAcc[g.wid];
-    float *wC = sC[g.wid], *wAccF = reinterpret_cast<float *>(sAcc[g.wid]);
+    float *wC = sC[g.wid], *wD = sD[g.wid], *wAccF = reinterpret_cast<float *>(sAcc[g.wid]);
     const int slot = acc_slot(lane);
 
     const float T_final = g.inside ? final_T[q] : 0.f;
@@ -148,6 +178,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
         d0 = dL_dpix[q];
         d1 = dL_dpix[npix + q];
         d2 = dL_dpix[2 * npix + q];
+    }
+    float dd = 0.f, da = 0.f;  // dL/ddepth, dL/dalpha of this pixel
+    if (EXTRA && g.inside) {
+        if (dL_ddepth) dd = dL_ddepth[q];
+        if (dL_dalpha) da = dL_dalpha[q];
     }
     const float bg_dot = bg[0] * d0 + bg[1] * d1 + bg[2] * d2;
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
@@ -164,7 +199,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
 
     // positions are 0-based from the front of the bin list; walk from max_last-1 down to 0 in rounds of 64
     float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-    float nC = 0.f;
+    float nC = 0.f, nD = 0.f;
     uint32_t nRec = 0;  // this lane's staged instance's slot (Gaussian, cell of its bin rect) = index of its gradient record
     const int bin_x = g.bin % bx, bin_y = g.bin / bx;
     auto stage = [&](uint32_t list_pos) {
@@ -173,6 +208,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
         nA = s[0]; nB = s[1];
         const float4 c = s[2];
         nC = c.x;
+        if (EXTRA) nD = c.y;
         const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
         const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
         nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
@@ -184,6 +220,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
         wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);  // conic pre-scaled for gsr_power2 (as the forward)
         wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
         wC[lane] = nC;
+        if (EXTRA) wD[lane] = nD;
         const uint32_t curRec = nRec;
         wave_sync_lds();
         const int64_t ntop = top - WAVE;
@@ -217,7 +254,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             const float om = 1.f - ae;
             const float rcp = __builtin_amdgcn_rcpf(om);
             T = T * rcp;
-            const float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
+            float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
+            if (EXTRA) {
+                // the two extra channels' share of cd, rounded like a colour channel's product-then-accumulate (no fma of z dd + da)
+#pragma clang fp contract(off)
+                const float zd = wD[j] * dd;
+                cd = cd + (zd + da);
+            }
             const float w = ae * T;  // dchannel/dcolour
             const float dL_dalpha = (cd - A) * T + nTb * rcp;
             A = ae * cd + om * A;
@@ -232,11 +275,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             const float m_yy = m_y * dy;
             const float red[9] = {g_r, g_g, g_b, m_x, m_y, m_xx, m_xy, m_yy, m_0};
             const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
-            if (slot >= 0) wAccF[12 * j + slot] = out;  // 12 lanes, 12 distinct words of this splat's record
+            if (slot >= 0) wAccF[4 * REC * j + slot] = out;  // 12 lanes, 12 distinct words of this splat's record
+            if (EXTRA) {
+                const float rz = wave_row_sum(w * dd);  // dL/dz share of this pixel: w dL/ddepth
+                if ((lane & 15) == 7) wAccF[4 * REC * j + 12 + (lane >> 4)] = rz;
+            }
         }
         wave_sync_lds();
         if ((touched >> lane) & 1ull) {  // lane j parks staged splat j's sums as ONE 32-byte instance record + its dL/dopacity (no atomics)
-            const float4 v0 = wAcc[3 * lane], v1 = wAcc[3 * lane + 1], rs = wAcc[3 * lane + 2];
+            const float4 v0 = wAcc[REC * lane], v1 = wAcc[REC * lane + 1], rs = wAcc[REC * lane + 2];
             const float4 sa = wA[lane], sb = wB[lane];  // this lane staged splat `lane` itself: conic (sa.z, sa.w, sb.x), opacity sb.y
             const float Sx = v0.w, Sy = v1.x, Sxx = v1.y, Sxy = v1.z, Syy = v1.w;
             const float S0 = (rs.x + rs.y) + (rs.z + rs.w);  // arrives as 4 row sums
@@ -250,6 +297,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             dst[0] = make_float4(v0.x, v0.y, v0.z, g_mx);
             dst[1] = make_float4(g_my, -0.5f * Sxx, -0.5f * Sxy, -0.5f * Syy);
             inst_dop[curRec] = S0 * __builtin_amdgcn_rcpf(sb.y);
+            if (EXTRA) {
+                const float4 rz = wAcc[REC * lane + 3];
+                inst_ddepth[curRec] = (rz.x + rz.y) + (rz.z + rz.w);
+            }
             inst_valid[curRec] = 1;
         }
     }
@@ -259,19 +310,28 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
 
 void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
                               const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                              const GsrHeader *hdr, uint8_t *inst_valid, hipStream_t s) {
+                              const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, hipStream_t s) {
     const int wgs = (bx / WAVES) * by;
     if (wgs <= 0) return;
-    hipLaunchKernelGGL(k_composite_fwd, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color,
-                       final_T, n_contrib, hdr, inst_valid);
+    if (out_depth || out_alpha)
+        hipLaunchKernelGGL(k_composite_fwd<true>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color,
+                           final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha);
+    else
+        hipLaunchKernelGGL(k_composite_fwd<false>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color,
+                           final_T, n_contrib, hdr, inst_valid, nullptr, nullptr);
 }
 
 void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
                               const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
                               const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                              GsrGradAcc *inst_grad, const GsrHeader *hdr, hipStream_t s) {
+                              GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
+                              hipStream_t s) {
     const int wgs = (bx / WAVES) * by;
     if (wgs <= 0) return;
-    hipLaunchKernelGGL(k_composite_bwd, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
-                       final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
+    if (inst_ddepth)
+        hipLaunchKernelGGL(k_composite_bwd<true>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
+                           final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth);
+    else
+        hipLaunchKernelGGL(k_composite_bwd<false>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
+                           final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr, nullptr, nullptr);
 }

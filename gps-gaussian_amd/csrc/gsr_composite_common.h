@@ -141,5 +141,14 @@ __device__ __forceinline__ float wave_reduce_scatter9(const float (&v)[9], bool 
     return ((__lane_id() & 15) == 15) ? w : r;
 }
 
+// a tenth term beside the reduce-scatter (the depth channel's dL/dz): every lane receives the sum of its 16-lane row in 4 DPP adds
+// (quad butterflies, then the two mirrors); the caller takes one lane per row
+__device__ __forceinline__ float wave_row_sum(float v) {
+    v = dpp_add_row<0xB1>(v);   // quad_perm [1,0,3,2]
+    v = dpp_add_row<0x4E>(v);   // quad_perm [2,3,0,1]   -> quad sums
+    v = dpp_add_row<0x141>(v);  // row_half_mirror       -> 8-lane sums
+    v = dpp_add_row<0x140>(v);  // row_mirror            -> row sums in every lane
+    return v;
+}
 
 }  // namespace

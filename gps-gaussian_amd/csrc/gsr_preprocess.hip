@@ -370,7 +370,10 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
 // APPEAR as k_preprocess: true = SH colours and / or precomputed covariances among the inputs.  DOPREC: the records were written without colour sums
 // (GsrBwdParams::dop_in_record): dL/dopacity is their first float and inst_dop is not read -- a template parameter, not a run-time test: with the test
 // inside the four-record gather the common instantiation went 28.7 -> 32.6 us (the conditional loads split the batch of twelve into two waits).
-template <bool APPEAR, bool DOPREC>
+// EXTRA: the records carry a tenth sum, dL/dz (q.inst_ddepth: the opt-in depth map's gradient), streamed with the others in the same slot order; it
+// reaches dL/dmeans3D through the view matrix's third row (z = viewmatrix[:, 2] . (p, 1)).  Never combined with DOPREC (the depth / alpha kernels
+// are the VALU family's).
+template <bool APPEAR, bool DOPREC, bool EXTRA = false>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const GsrSplat *__restrict__ splats,
                                                         const uint32_t *__restrict__ goff, const uint32_t *__restrict__ gpart,
                                                         const uint8_t *__restrict__ inst_valid, const float *__restrict__ inst_dop,
@@ -403,7 +406,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
                          "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]));
         // gather this Gaussian's instance records in rect order: fixed summation order -> reproducible gradients
         float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
-        float g2x = 0.f;
+        float g2x = 0.f, gz = 0.f;
         // this Gaussian's slots [s0, s1): from the slot prefix alone (the splat record would cost a 48-byte-stride read for 8 bytes)
         const int gb = i >> GSR_BIN_SHIFT;
         const uint32_t gbase = gpart[gb];
@@ -444,19 +447,21 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
                         m &= m - 1u;  // (0 stays 0)
                     }
                     float4 a0[4], a1[4];
-                    float a2[4] = {0.f, 0.f, 0.f, 0.f};
+                    float a2[4] = {0.f, 0.f, 0.f, 0.f}, a3[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const float4 *r = reinterpret_cast<const float4 *>(inst_grad + ri[u]);
                         a0[u] = r[0];
                         a1[u] = r[1];
                         if (!DOPREC) a2[u] = inst_dop[ri[u]];
+                        if (EXTRA) a3[u] = q.inst_ddepth[ri[u]];
                     }
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         g0.x += ok[u] ? a0[u].x : 0.f; g0.y += ok[u] ? a0[u].y : 0.f; g0.z += ok[u] ? a0[u].z : 0.f; g0.w += ok[u] ? a0[u].w : 0.f;
                         g1.x += ok[u] ? a1[u].x : 0.f; g1.y += ok[u] ? a1[u].y : 0.f; g1.z += ok[u] ? a1[u].z : 0.f; g1.w += ok[u] ? a1[u].w : 0.f;
                         g2x += ok[u] ? a2[u] : 0.f;
+                        if (EXTRA) gz += ok[u] ? a3[u] : 0.f;
                     }
                 }
             }
@@ -546,6 +551,11 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         dm[0] += (pr[0] * mw - pr[3] * mul1) * dm2[0] + (pr[1] * mw - pr[3] * mul2) * dm2[1];
         dm[1] += (pr[4] * mw - pr[7] * mul1) * dm2[0] + (pr[5] * mw - pr[7] * mul2) * dm2[1];
         dm[2] += (pr[8] * mw - pr[11] * mul1) * dm2[0] + (pr[9] * mw - pr[11] * mul2) * dm2[1];
+        if (EXTRA) {  // the depth map: z = v[2] p0 + v[6] p1 + v[10] p2 + v[14]
+            dm[0] += v[2] * gz;
+            dm[1] += v[6] * gz;
+            dm[2] += v[10] * gz;
+        }
 
         if (use_sh) {
             // colour -> SH coefficients, and -> mean3D through the view direction (upstream computeColorFromSH backward): the colour and its
@@ -665,7 +675,10 @@ void gsr_launch_preprocess_bwd(const GsrBwdParams &p, const GsrSplat *splats, co
     q.fy = (float)q.H / (2.f * q.tanfovy);
     const dim3 grid((q.P + 255) / 256), block(256);
     const bool appear = q.shs || q.cov3D_precomp;
-    if (appear && q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
+    if (q.inst_ddepth) {  // depth / alpha backward (VALU records: inst_dop is always written)
+        if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
+        else hipLaunchKernelGGL((k_preprocess_bwd<false, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
+    } else if (appear && q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
     else if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
     else if (q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
     else hipLaunchKernelGGL((k_preprocess_bwd<false, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);

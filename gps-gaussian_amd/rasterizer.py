@@ -438,10 +438,13 @@ class _Rows:
         self.ptr = offsets.data_ptr() + 4 * self.index
 
 
-def _ext(rows, hint, appear=None, bin_cap=0):
+def _ext(rows, hint, appear=None, bin_cap=0, depth_alpha=None):
     """appear: None, or (shs, sh_degree, campos, cov3D_precomp, dL_dsh, dL_dcov3D) tensors / None -- the SH-colour and precomputed-covariance
-    inputs (and, for the backward, their gradient arrays)."""
+    inputs (and, for the backward, their gradient arrays).  depth_alpha: None, or two [H, W] tensors / None -- the forward's depth and alpha
+    outputs, or the backward's gradients of them (the two share their GsrViewExt slots)."""
     e = _capi.GsrViewExt()
+    if depth_alpha is not None:
+        e.out_depth, e.out_alpha = _ptr(depth_alpha[0]), _ptr(depth_alpha[1])
     e.row_range = rows.ptr if rows is not None else None
     e.order_hint = int(hint) & 0xffffffff
     e.bin_capacity = int(bin_cap)
@@ -461,7 +464,7 @@ def _too_many(R):
 
 
 def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, needs_grad, out_color=None, rows=None,
-                  radii_out=None, shs=None, cov3D_precomp=None):
+                  radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None):
     """One view's forward through the C-ABI (capacity policy, early notification, overflow repair).  `ctx` is any attribute holder: the
     autograd ctx of _RasterizeGaussians, or a plain namespace when a caller drives several views itself (render_api._RenderBatch).
     Leaves on it: raster_settings, cap, family, extra_flags, rows, saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
@@ -469,7 +472,10 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     shs [P, M, 3] (M <= 16, evaluated up to raster_settings.sh_degree towards raster_settings.campos) INSTEAD of colors_precomp;
     cov3D_precomp [P, 6] INSTEAD of scales + rotations.  out_color: optional preallocated contiguous fp32 [3,H,W] the image is written into.
     rows (a _Rows): the five inputs are batch-wide packed arrays, this view is the row range rows.offsets[rows.index : rows.index + 2] of
-    them (read on the DEVICE), radii_out the batch-wide int32 radii array.  -> (color, radii)"""
+    them (read on the DEVICE), radii_out the batch-wide int32 radii array.
+    depth_alpha: also render the depth map (sum z_i alpha_i T_i, unnormalised) and the alpha map (sum alpha_i T_i), background 0, with the VALU
+    compositing family (include/gpsgs.h GsrViewExt.out_depth); out_depth / out_alpha: optional preallocated contiguous fp32 [H,W] (or [1,H,W])
+    tensors for them.  -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W])"""
     rs = raster_settings
     lib = _capi.lib()
     if not means3D.is_cuda:
@@ -507,6 +513,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     st = _dev_state(dev)
     mode = _check_mode()
     family = _composite_flag() | (_wave_priority_flag(st, torch._C._cuda_getCurrentRawStream(dev.index), deterministic=(mode == "none")) if rows is None else 0)
+    if depth_alpha:
+        family = 0  # the depth / alpha maps are made by the VALU kernels (forward and backward of a view must agree on the family)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
     base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family
     if mode != "none" and torch.cuda.is_current_stream_capturing():
@@ -523,6 +531,12 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
             color = out_color
             if (color.dtype is not torch.float32 or color.device != dev or tuple(color.shape) != (3, H, W) or not color.is_contiguous()):
                 raise RuntimeError("gps_gaussian_amd: out_color must be a contiguous fp32 [3, H, W] tensor on the inputs' device")
+        dmaps = None
+        if depth_alpha:
+            dmaps = tuple(torch.empty((1, H, W), dtype=torch.float32, device=dev) if t is None else t for t in (out_depth, out_alpha))
+            for t in dmaps:
+                if t.dtype is not torch.float32 or t.device != dev or t.numel() != H * W or not t.is_contiguous():
+                    raise RuntimeError("gps_gaussian_amd: out_depth / out_alpha must be contiguous fp32 [H, W] tensors on the inputs' device")
         if rows is None:
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
         else:
@@ -540,11 +554,11 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
 
         def launch(cap, bin_cap, plan_flags):
             """Enqueue the whole forward (one _plan).  -> (notify note or None, cap, bin_cap)"""
-            nbytes = lib.gsr_workspace_bytes_ex(P, W, H, cap, bin_cap, fwd_only)
+            nbytes = (lib.gsr_workspace_bytes_depth_alpha if depth_alpha else lib.gsr_workspace_bytes_ex)(P, W, H, cap, bin_cap, fwd_only)
             st["last_ws_bytes"] = nbytes  # reported by last_stats(): what one view in flight holds (forward-only workspaces are ~3x smaller)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             note, hdr_ptr = ring.acquire_notify() if ring is not None else (None, None)
-            ext = _ext(rows, st.get("longest", 0), appear, bin_cap)  # work order: longest lists first, relative to the longest list seen on this device
+            ext = _ext(rows, st.get("longest", 0), appear, bin_cap, dmaps)  # (every attempt, the repair included, writes the maps) work order: longest lists first, relative to the longest list seen on this device
             rc = lib.gsr_forward_ex(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier), float(rs.tanfovx),
                                     float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap,
                                     base_flags | plan_flags, stream, hdr_ptr, note[3] if note is not None else 0, C.byref(ext))
@@ -590,16 +604,26 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     ctx.family = family  # the backward must repeat the forward's per-pixel decisions: same kernel family
     ctx.extra_flags = extra
     ctx.rows = rows
+    ctx.depth_alpha = bool(depth_alpha)
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
+    if depth_alpha:
+        return color, radii, dmaps[0], dmaps[1]
     return color, radii
 
 
-def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True):
+def _map_grad(g):
+    if g is None or (g.dtype is torch.float32 and g.is_contiguous() and not g.requires_grad):
+        return g
+    return g.detach().to(dtype=torch.float32).contiguous()
+
+
+def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_depth=None, grad_alpha=None):
     """One view's backward through the C-ABI.  color_grad=False: the caller does not need dL/dcolours (GSR_FLAG_NO_COLOR_GRAD: the tile
     family leaves the colour sums out; the returned colour gradient is zeros / not meaningful).  saved: the tuple _forward_impl left in ctx.saved; arena: optional five preallocated
     gradient tensors (means3D, colours, opacities, scales, rotations) -- for a row-range view (ctx.rows) they are REQUIRED and batch-wide,
     the view's rows of them are written.  -> (d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov); d_sh / d_cov are None unless the forward was given
-    SH coefficients / precomputed covariances (d_sc, d_rot are then not meaningful)."""
+    SH coefficients / precomputed covariances (d_sc, d_rot are then not meaningful).  grad_depth / grad_alpha: gradients of the depth and alpha
+    maps of a depth_alpha forward ([H,W] or [1,H,W]; None = zero); grad_out_color may then be None too."""
     rs = ctx.raster_settings
     lib = _capi.lib()
     m3, col, opa, sca, rot, view, proj, bg, radii, ws = saved[:10]
@@ -615,8 +639,15 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True):
     P = N if rows is None else rows.capacity
     H, W = int(rs.image_height), int(rs.image_width)
     g = grad_out_color  # H3: may arrive non-contiguous (or in another dtype); the common case -- fp32, contiguous -- is used as it is
-    if g.dtype is not torch.float32 or not g.is_contiguous() or g.requires_grad:
+    if g is None:  # only the depth / alpha maps took part in the loss
+        g = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
+    elif g.dtype is not torch.float32 or not g.is_contiguous() or g.requires_grad:
         g = g.detach().to(dtype=torch.float32).contiguous()
+    dmaps = None
+    if getattr(ctx, "depth_alpha", False) and (grad_depth is not None or grad_alpha is not None):
+        dmaps = (_map_grad(grad_depth), _map_grad(grad_alpha))
+        if any(t is not None and (t.numel() != H * W or t.device != dev) for t in dmaps):
+            raise RuntimeError("gps_gaussian_amd: depth / alpha gradients must have H x W elements on the inputs' device")
     with _device_guard(dev):
         st = _dev_state(dev)
         if _check_mode() != "none":
@@ -639,7 +670,7 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True):
         d_sh = torch.empty_like(sh) if sh is not None else None
         d_cov = torch.empty_like(cov) if cov is not None else None
         if P > 0:
-            ext = _ext(rows, 0, (sh, int(rs.sh_degree), campos, cov, d_sh, d_cov) if (sh is not None or cov is not None) else None, bin_cap)
+            ext = _ext(rows, 0, (sh, int(rs.sh_degree), campos, cov, d_sh, d_cov) if (sh is not None or cov is not None) else None, bin_cap, dmaps)
             rc = lib.gsr_backward_ex(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier),
                                      float(rs.tanfovx), float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(radii), _ptr(g),
                                      _ptr(d_m3), _ptr(d_m2), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_rot), _ptr(ws),
@@ -713,38 +744,47 @@ _debug_keep_ws = False  # tests: both host paths leave {ws, cap, bin_cap} of the
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
+                return_depth_alpha=False):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
         ctx.grad_arena = grad_arena
         # stage 2 never differentiates the colours (they are input pixels, lib/GaussianRender.py:30-31): the backward then skips their sums
         ctx.color_grad = bool(ctx.needs_input_grad[3]) or sh is not None  # (dL/dsh is formed from dL/dcolour)
-        color, radii = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
-                                     shs=sh, cov3D_precomp=cov3Ds_precomp)
+        out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
+                            shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha))
         if _debug_keep_ws:
             _tls.last_ws = dict(ws=ctx.saved[9], cap=ctx.cap, bin_cap=ctx.bin_cap)
         ctx.save_for_backward(*ctx.saved)
         ctx.saved = None
-        ctx.mark_non_differentiable(radii)
+        ctx.mark_non_differentiable(out[1])
         ctx.set_materialize_grads(False)  # otherwise autograd fills a zero int32 [P] "gradient" for radii on every backward
-        return color, radii
+        return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
-        if grad_out_color is None:  # the image did not take part in the loss
-            return (None,) * 10
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:  # no output took part in the loss
+            return (None,) * 11
         saved = ctx.saved_tensors
-        d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad)
+        d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad,
+                                                                           grad_depth, grad_alpha)
         has_sh, has_cov = saved[10] is not None, saved[11] is not None
-        # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+        # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None)
+                d_cov, None, None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None):
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
+                        return_depth_alpha=False):
+    """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
+    (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
+    and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says."""
+    if return_depth_alpha:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, grad_arena)
+                                     raster_settings, grad_arena)  # (the default call shape is the one it always was)
 
 
 class GaussianRasterizer(nn.Module):
@@ -756,13 +796,13 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None):
+                grad_arena=None, return_depth_alpha=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        if shs is None and cov3D_precomp is None and grad_arena is None:
+        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha:
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -770,8 +810,9 @@ class GaussianRasterizer(nn.Module):
         # shs [P, M, 3] are evaluated up to raster_settings.sh_degree towards raster_settings.campos (upstream computeColorFromSH); cov3D_precomp
         # [P, 6] replaces scale + rotation.  The reference passes neither (gaussian_renderer/__init__.py:54-62) but constructs the settings
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
+        # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena)
+                                   self.raster_settings, grad_arena, return_depth_alpha)
 
 
     def markVisible(self, positions):

@@ -101,13 +101,15 @@ class _RenderBatch(torch.autograd.Function):
     Numerically it IS the per-sample path: the same kernels on the same rows (tests/test_gpu_pack.py compares the bits)."""
 
     @staticmethod
-    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows):
+    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
-        # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels)
+        # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
+        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True))
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
         out = torch.empty((bs, 3, H, W), dtype=torch.float32, device=dev)
+        dmaps = (torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev), torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev)) if depth_alpha else None
         radii = torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
@@ -121,7 +123,8 @@ class _RenderBatch(torch.autograd.Function):
                     side[i].wait_stream(cur)
                 with torch.cuda.stream(side[i]):
                     _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, out_color=out[i],
-                                      rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii)
+                                      rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
+                                      out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -140,16 +143,20 @@ class _RenderBatch(torch.autograd.Function):
         ctx.color_grad = bool(ctx.needs_input_grad[1])  # False in stage 2: pack_views marks rgb non-differentiable when no image needs a gradient
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
         ctx.set_materialize_grads(False)
+        if depth_alpha:
+            return out, dmaps[0], dmaps[1]
         return out
 
     @staticmethod
-    def backward(ctx, gout):
-        if gout is None:
-            return (None,) * 8
+    def backward(ctx, gout, gdepth=None, galpha=None):
+        if gout is None and gdepth is None and galpha is None:
+            return (None,) * 9
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
-        dev = gout.device
-        g = gout.detach().to(dtype=torch.float32).contiguous()
+        dev = xyz.device
+        g = gout.detach().to(dtype=torch.float32).contiguous() if gout is not None else None
+        gd = gdepth.detach().to(dtype=torch.float32).contiguous() if gdepth is not None else None
+        ga = galpha.detach().to(dtype=torch.float32).contiguous() if galpha is not None else None
         # one gradient buffer per packed tensor (+ one for the unused screen-space gradient); every view's backward writes its own
         # rows, rows behind offsets[-1] (the unused tail of the packed capacity) are never read by the pack backward
         d_xyz, d_rgb, d_rot, d_scale, d_op = (torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes)
@@ -160,11 +167,12 @@ class _RenderBatch(torch.autograd.Function):
                 side[i].wait_stream(cur)
             ins = h.own if h.own is not None else (xyz, rgb, opacity.reshape(-1), scale, rot)
             with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.ws_box in there)
-                _RZ._backward_impl(h, tuple(ins) + tuple(h.tail), g[i], (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2), ctx.color_grad)
+                _RZ._backward_impl(h, tuple(ins) + tuple(h.tail), g[i] if g is not None else None, (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2),
+                                   ctx.color_grad, gd[i] if gd is not None else None, ga[i] if ga is not None else None)
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
-        return d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None
+        return d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None
 
 
 def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None):
@@ -188,6 +196,20 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
     return rendered_image
 
 
+def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None):
+    """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
+    depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
+    and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
+    The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE."""
+    nv = data['novel_view']
+    bg = _bg_tensor(bg_color, pts_xyz.device)
+    means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
+    rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
+    img, _, depth, alpha = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
+                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True)
+    return {'img': img, 'depth': depth, 'alpha': alpha}
+
+
 def _settings(nv, idx, bg, view=None, proj=None):
     return GaussianRasterizationSettings(
         image_height=int(nv['height'][idx]), image_width=int(nv['width'][idx]),
@@ -205,8 +227,9 @@ def _to_device_once(t, dev):
     return t
 
 
-def pts2render(data, bg_color):
-    """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].
+def pts2render(data, bg_color, with_depth_alpha=False):
+    """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
+    also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -225,12 +248,15 @@ def pts2render(data, bg_color):
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
+        if with_depth_alpha:
+            nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, True)
+        else:
+            nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist())
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha)
 
 
-def _pts2render_loop(data, bg_color, packed, offs):
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False):
     """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
@@ -260,13 +286,22 @@ def _pts2render_loop(data, bg_color, packed, offs):
             if side[i] is not cur:
                 side[i].wait_stream(cur)
             with torch.cuda.stream(side[i]):
-                out.append(render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
-                                  grad_arena=ga).unsqueeze(0))
+                if with_depth_alpha:
+                    r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga)
+                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha')))
+                else:
+                    out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
+                                       grad_arena=ga).unsqueeze(0),))
     for i in range(bs):
         if side[i] is not cur:
             cur.wait_stream(side[i])
-            out[i].record_stream(cur)
-    data['novel_view']['img_pred'] = torch.cat(out, dim=0)
+            for t in out[i]:
+                t.record_stream(cur)
+    nv = data['novel_view']
+    nv['img_pred'] = torch.cat([o[0] for o in out], dim=0)
+    if with_depth_alpha:
+        nv['depth_pred'] = torch.cat([o[1] for o in out], dim=0)
+        nv['alpha_pred'] = torch.cat([o[2] for o in out], dim=0)
     return data
 
 

@@ -48,7 +48,9 @@ extern "C" {
                                4: + gsr_mark_visible (upstream GaussianRasterizer.markVisible); gsr_debug_count_records takes workspace_bytes;
                                   DIRECT bin lists: GsrViewExt.reserved0 became bin_capacity (0 = what version 3 did), gsr_workspace_bytes_ex,
                                   gsr_direct_lists_ok; gsr_export_state / gsr_debug_count_records take bin_capacity
-                               still 4 after up_splat_scratch_bytes, up_zsplat, up_flow2render_dev: purely additive, nothing existing changed */
+                               still 4 after up_splat_scratch_bytes, up_zsplat, up_flow2render_dev: purely additive, nothing existing changed
+                               still 4 after the depth / alpha maps: GsrViewExt.reserved[4] became two pointer slots (out_depth | dL_ddepth,
+                                  out_alpha | dL_dalpha; zero = none, what 4 did, same 80-byte struct) + gsr_workspace_bytes_depth_alpha */
 
 enum {
     GPSGS_OK = 0,
@@ -127,6 +129,9 @@ int gsr_direct_lists_ok(int width, int height, uint32_t bin_capacity);
  * instance_capacity still bounds the gradient-record slots of a training workspace (header.num_slots); the lists themselves take bins x bin_capacity entries */
 size_t gsr_workspace_bytes_ex(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only);
 size_t gsr_workspace_bytes(int P, int width, int height, int64_t instance_capacity);              /* forward + backward */
+/* gsr_workspace_bytes_ex plus room for the depth / alpha backward (GsrViewExt.dL_ddepth / dL_dalpha); forward_only: the same as gsr_workspace_bytes_ex
+ * (the forward of the maps needs nothing extra) */
+size_t gsr_workspace_bytes_depth_alpha(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only);
 size_t gsr_workspace_bytes_forward_only(int P, int width, int height, int64_t instance_capacity); /* inference: no backward tail; a forward on
                                                                                                      such a workspace also skips the per-pixel state
                                                                                                      only a backward reads (final T, last contributor) */
@@ -192,7 +197,19 @@ typedef struct GsrViewExt {
     const float *cov3D_precomp;
     float *dL_dsh;      /* gsr_backward_ex only */
     float *dL_dcov3D;   /* gsr_backward_ex only */
-    uint32_t reserved[4];
+    /* ---- opt-in DEPTH and ALPHA maps of the view (the former reserved[4]; NULL = none).  Two more channels of the same blend -- same splats, sort order
+     *   and power > 0 / alpha < 1/255 / T < 1e-4 decisions -- with background 0:
+     *     depth[p] = sum_i z_i alpha_i T_i   (z_i the Gaussian's view-space depth; NOT normalised: divide by alpha for the expected depth)
+     *     alpha[p] = sum_i alpha_i T_i       (= 1 - final T, but accumulated as the sum, so that its gradient follows the colour recurrence)
+     *   gsr_forward_ex: out_depth / out_alpha, DEVICE [H, W] fp32 (4-byte aligned; either may be NULL).  Both NULL: the plain kernels run, bit for bit.
+     *   gsr_backward_ex: dL_ddepth / dL_dalpha, DEVICE [H, W] (either may be NULL = zero).  They reach dL_dopacity, dL_dmeans2D, the conic and
+     *   through it dL_dscales / dL_drotations / dL_dcov3D exactly as a colour channel with c = z_i resp. c = 1 would, and dL/dz_i = sum_p dL_ddepth
+     *   alpha_i T_i adds dL/dz * viewmatrix[:, 2] to dL_dmeans3D.  The workspace must then be sized with gsr_workspace_bytes_depth_alpha (one more
+     *   float per instance slot; GPSGS_E_WORKSPACE otherwise).
+     *   The maps are made by the VALU compositing kernels: with either output / gradient set, GSR_FLAG_COMPOSITE_TILES is ignored, so a view whose
+     *   forward produced the maps has to run its backward with the VALU family too (pass a depth / alpha gradient, or leave the tiles flag off). */
+    union { float *out_depth; const float *dL_ddepth; };
+    union { float *out_alpha; const float *dL_dalpha; };
 } GsrViewExt;
 
 /* gsr_forward_notify + GsrViewExt (host_header_out may be NULL: no notification, like gsr_forward).  The early header's word 6 carries
