@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get("GPSGS_LIB") or os.path.join(_HERE, "lib", "libgpsgs_h
 
 # every symbol include/gpsgs.h declares (tests/test_capi_symbols.py cross-checks this list against the header)
 SYMBOLS = (
-    "gpsgs_abi_version", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_copy_header_async", "gsr_read_header",
+    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_copy_header_async", "gsr_read_header",
     "gsr_export_state", "gsr_mark_visible", "gsr_selftest", "gsr_timing_read", "gsr_debug_count_records", "gsr_pack_scratch_bytes", "gsr_pack_views", "gsr_pack_views_backward", "fl_scratch_bytes",
     "fl_l1_ssim_forward", "fl_l1_ssim_backward", "up_unproject_forward", "up_unproject_backward", "up_unproject_forward_dev", "up_unproject_backward_dev", "up_splat_scratch_bytes", "up_zsplat", "up_flow2render_dev", "cs_forward", "cs_backward",
     "cv_build_forward", "cv_build_backward", "cs_lookup_forward", "cs_lookup_backward", "cu_upsample_forward", "cu_upsample_backward", "cu_upsample_scratch_bytes",
@@ -22,6 +22,7 @@ GSR_FLAG_TIMING = 2
 GSR_FLAG_COMPOSITE_TILES = 8
 GSR_FLAG_NO_COLOR_GRAD = 256
 GSR_FLAG_WAVE_PRIORITY = 512
+GSR_FLAG_ANTIALIAS = 1024
 STAGES = ("preprocess", "scan", "scatter", "sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 
 
@@ -69,6 +70,8 @@ def lib():
     vp, i32, i64, f32, sz, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint
     l.gpsgs_abi_version.restype = i32
     l.gpsgs_abi_version.argtypes = []
+    l.gsr_supported_flags.restype = i32
+    l.gsr_supported_flags.argtypes = []
     l.gpsgs_build_info.restype = C.c_char_p
     l.gpsgs_build_info.argtypes = []
     l.gsr_debug_set_wg_trace.restype = i32

@@ -135,6 +135,11 @@ __global__ __launch_bounds__(256) void k_zero16(uint4 *__restrict__ p, uint32_t 
 
 extern "C" int gpsgs_abi_version(void) { return GPSGS_ABI_VERSION; }
 
+extern "C" int gsr_supported_flags(void) {
+    return (int)(GSR_FLAG_DEBUG | GSR_FLAG_TIMING | GSR_FLAG_NO_LARGE_SORT | GSR_FLAG_COMPOSITE_TILES | GSR_FLAG_NO_COLOR_GRAD | GSR_FLAG_WAVE_PRIORITY |
+                 GSR_FLAG_ANTIALIAS);
+}
+
 extern "C" const char *gpsgs_build_info(void) { return "gfx950 hipcc " __VERSION__ " built " __DATE__; }
 
 extern "C" size_t gsr_workspace_bytes(int P, int width, int height, int64_t instance_capacity) {
@@ -243,6 +248,7 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
     q.row_range = row_range;
     q.shs = shs; q.campos = shs ? ext->campos : nullptr; q.cov3D_precomp = cov3D_precomp;
     q.sh_degree = shs ? ext->sh_degree : 0u; q.sh_coeffs = shs ? ext->sh_coeffs : 0u;
+    q.antialias = (flags & GSR_FLAG_ANTIALIAS) ? 1 : 0;  // (k_preprocess<true>: the record's opacity is opacity * k)
     const GsrBins bins = {bin_offset, bin_count, bin_count_fb, bin_cap};
     // a workspace that includes the backward tail gets the per-Gaussian slot prefix and cleared record flags from the forward
     const bool training = workspace_bytes >= L.total;
@@ -364,7 +370,8 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
                                const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
                                float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
-    (void)colors; (void)opacities;  // already folded into the splat records of the workspace
+    (void)colors;  // already folded into the splat records of the workspace (so are the opacities -- read again only with antialiasing)
+    const bool antialias = (flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
     const float *dL_ddepth = ext ? ext->dL_ddepth : nullptr, *dL_dalpha = ext ? ext->dL_dalpha : nullptr;
     const bool extras = dL_ddepth || dL_dalpha;
@@ -375,6 +382,7 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     const float *shs = ext ? ext->shs : nullptr, *cov3D_precomp = ext ? ext->cov3D_precomp : nullptr;
     if (!means3D || !viewmatrix || !projmatrix || !bg || !radii || !dL_dpix || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity || !workspace) return GPSGS_E_INVALID;
     if (!shs && !dL_dcolors) return GPSGS_E_INVALID;
+    if (antialias && !opacities) return GPSGS_E_INVALID;  // dL/dk = g * opacity
     if (cov3D_precomp ? (!ext->dL_dcov3D || scales || rotations) : (!scales || !rotations || !dL_dscales || !dL_drotations)) return GPSGS_E_INVALID;
     if (shs && (!ext->campos || !ext->dL_dsh || ext->sh_degree > 3u || ext->sh_coeffs > 16u || (ext->sh_degree + 1u) * (ext->sh_degree + 1u) > ext->sh_coeffs))
         return GPSGS_E_INVALID;
@@ -425,6 +433,8 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     b.sh_degree = shs ? ext->sh_degree : 0u; b.sh_coeffs = shs ? ext->sh_coeffs : 0u;
     b.dL_dsh = shs ? ext->dL_dsh : nullptr; b.dL_dcov3D = cov3D_precomp ? ext->dL_dcov3D : nullptr;
     b.inst_ddepth = inst_ddepth;
+    b.antialias = antialias ? 1 : 0;
+    b.opacities = opacities;
     b.dop_in_record = ((flags & GSR_FLAG_COMPOSITE_TILES) && (flags & GSR_FLAG_NO_COLOR_GRAD)) ? 1 : 0;  // what k_composite_bwd_tiles<false> just wrote
     {
         trace("preprocess_bwd", P, width, height, (long long)instance_capacity, flags);

@@ -488,6 +488,7 @@ struct GsrFwdParams {
     const float *shs, *campos, *cov3D_precomp;  // [rows, sh_coeffs, 3], [3], [rows, 6]; NULL = not used
     uint32_t sh_degree, sh_coeffs;
     float fx, fy;  // focal lengths in pixels, W / (2 tanfovx): set by gsr_launch_preprocess (two IEEE divisions per THREAD of a VALU-bound kernel otherwise)
+    int antialias; // GSR_FLAG_ANTIALIAS: the record's opacity is opacity * k(2D covariance) (k_preprocess<true>, aa_factor)
 };
 
 void gsr_launch_preprocess(const GsrFwdParams &p, GsrSplat *splats, uint4 *binrec, uint32_t *wg_tab, uint32_t *bin_count, uint32_t *bin_count_fb, GsrHeader *hdr,
@@ -556,6 +557,8 @@ struct GsrBwdParams {
     const float *inst_ddepth;   // non-NULL: the records carry dL/dz (depth / alpha backward) -> dL/dmeans3D += dL/dz * viewmatrix[:, 2]
     int dop_in_record;          // the records were written without colour sums (tile family + GSR_FLAG_NO_COLOR_GRAD): dL/dopacity is their first float, inst_dop is not read
     float fx, fy;               // as in GsrFwdParams: set by gsr_launch_preprocess_bwd
+    int antialias;              // as in GsrFwdParams (the forward of the view must have had it): dL/dopacity = g k, and dL/dk reaches the covariance
+    const float *opacities;     // read only with antialias
 };
 
 #if defined(__HIPCC__)

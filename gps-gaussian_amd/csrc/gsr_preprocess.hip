@@ -74,16 +74,30 @@ __device__ __forceinline__ Ewa ewa_setup(const float pv[3], const float *v, floa
     return e;
 }
 
-__device__ __forceinline__ void cov2d(const Ewa &e, const float c6[6], float &a, float &b, float &c) {
+// (a, b, c) = the dilated 2D covariance; (a0, c0) = its diagonal before the + 0.3 (a separate rounding: a and c keep the bits of a0 + ... + 0.3f)
+__device__ __forceinline__ void cov2d(const Ewa &e, const float c6[6], float &a, float &b, float &c, float &a0, float &c0) {
     const float S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
     float V[3][2];
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
         for (int m = 0; m < 2; m++) V[k][m] = S[k][0] * e.T[m][0] + S[k][1] * e.T[m][1] + S[k][2] * e.T[m][2];
-    a = e.T[0][0] * V[0][0] + e.T[0][1] * V[1][0] + e.T[0][2] * V[2][0] + 0.3f;
+    a0 = e.T[0][0] * V[0][0] + e.T[0][1] * V[1][0] + e.T[0][2] * V[2][0];
+    a = a0 + 0.3f;
     b = e.T[0][0] * V[0][1] + e.T[0][1] * V[1][1] + e.T[0][2] * V[2][1];
-    c = e.T[1][0] * V[0][1] + e.T[1][1] * V[1][1] + e.T[1][2] * V[2][1] + 0.3f;
+    c0 = e.T[1][0] * V[0][1] + e.T[1][1] * V[1][1] + e.T[1][2] * V[2][1];
+    c = c0 + 0.3f;
+}
+
+// Antialiasing (GSR_FLAG_ANTIALIAS; the opacity-compensated screen-space filter of Mip-Splatting): a splat widened by the 0.3 px^2 dilation keeps
+// the mass of the undilated one when its opacity is scaled by k = sqrt(rho), rho = det(cov0) / det(cov0 + 0.3 I) = (a0 c0 - b^2) / det, floored at
+// rho = 2.5e-5 (k = 0.005; also what a slightly negative a0 c0 - b^2 from rounding gets).  det: the dilated determinant a c - b^2 the kernels already
+// form.  live: rho is above the floor (only then does k depend on the covariance).  The forward and the backward evaluate this one function.
+constexpr float GSR_AA_RHO_MIN = 2.5e-5f;
+__device__ __forceinline__ float aa_factor(float a0, float b, float c0, float det, bool &live) {
+    const float rho = (a0 * c0 - b * b) / det;
+    live = rho > GSR_AA_RHO_MIN;
+    return sqrtf(live ? rho : GSR_AA_RHO_MIN);
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -182,8 +196,8 @@ struct CountHit {
 };
 
 // APPEAR = false: the inputs the reference passes (precomputed colours, scale + rotation): the instantiation every measured configuration runs.
-// APPEAR = true: SH colours (q.shs) and / or precomputed 3D covariances (q.cov3D_precomp) -- its own instantiation, so that the common one carries
-// neither the branches nor the registers of these inputs.
+// APPEAR = true: SH colours (q.shs) and / or precomputed 3D covariances (q.cov3D_precomp) and / or antialiasing (q.antialias) -- its own
+// instantiation, so that the common one carries neither the branches nor the registers of these options.
 template <bool APPEAR>
 __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, GsrSplat *__restrict__ splats, uint4 *__restrict__ binrec,
                                                                uint32_t *__restrict__ wg_tab, uint32_t *__restrict__ bin_count, uint32_t *__restrict__ bin_count_fb,
@@ -218,6 +232,7 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
     const Cam cam = load_cam(q.view, q.proj);
     const float p[3] = {q.means3D[3 * r], q.means3D[3 * r + 1], q.means3D[3 * r + 2]};
     const bool use_sh = APPEAR && q.shs != nullptr, use_cov = APPEAR && q.cov3D_precomp != nullptr;  // wave-uniform
+    const bool aa = APPEAR && q.antialias != 0;
     float col[3] = {0.f, 0.f, 0.f};
     if (!use_sh) { col[0] = q.colors[3 * r]; col[1] = q.colors[3 * r + 1]; col[2] = q.colors[3 * r + 2]; }
     const float op = q.opacities[r];
@@ -258,8 +273,8 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
             cov3d(sc, R, c6);
         }
         const Ewa e = ewa_setup(pv, cam.v, fx, fy, q.tanfovx, q.tanfovy);
-        float a, b, c;
-        cov2d(e, c6, a, b, c);
+        float a, b, c, a0, c0;
+        cov2d(e, c6, a, b, c, a0, c0);
         const float det = a * c - b * b;
         if (det != 0.f) {
             const float det_inv = 1.f / det;
@@ -285,6 +300,14 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
                     sh_color((int)q.sh_degree, q.shs + (size_t)3 * q.sh_coeffs * r, p, q.campos, rgb, cl, dir, raw);
                     o1.z = rgb[0]; o1.w = rgb[1]; o2x = rgb[2];
                 }
+                // the record's opacity: with antialiasing op * k (k <= 1), and everything below -- the alpha >= 1/255 box (tau), the hit test -- and every
+                // later stage works from that stored value.  Conic, radius and tile rect stay those of the dilated covariance.
+                float op_r = op;
+                if (aa) {
+                    bool live;
+                    op_r = op * aa_factor(a0, b, c0, det, live);
+                    o1.y = op_r;
+                }
                 // Bin rect = (upstream's 16x16-tile rect, in 8-px bins) INTERSECT (bounding box of the alpha >= 1/255
                 // level set).  alpha = op * exp(power) >= 1/255  <=>  d^T Sigma^-1 d <= 2 ln(255 op) =: 2 tau, whose
                 // axis-aligned extent is |dx| <= sqrt(2 tau a), |dy| <= sqrt(2 tau c) with (a,b,c) the dilated 2D
@@ -293,7 +316,7 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
                 // (v_log_f32 / v_sqrt_f32, 1 ulp each, instead of the library's logf and the correctly rounded square roots: ~70 vector instructions of a
                 //  VALU-bound kernel, for numbers that are inflated by 0.1 - 0.2 % before anything is decided with them.  log2(1) is exactly 0 and the
                 //  instruction is monotonic to its ulp, so the sign of tau -- opacity >= 1/255 -- is the exact one.)
-                const float tau = __builtin_amdgcn_logf(255.f * op) * 0.693147180559945f;
+                const float tau = __builtin_amdgcn_logf(255.f * op_r) * 0.693147180559945f;
                 if (tau >= 0.f) {
                     const float hx = __builtin_amdgcn_sqrtf(2.f * tau * a) * 1.001f + 0.01f, hy = __builtin_amdgcn_sqrtf(2.f * tau * c) * 1.001f + 0.01f;
                     int b0x = (int)floorf((px - hx) / 8.f), b1x = (int)floorf((px + hx) / 8.f) + 1;
@@ -390,6 +413,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
     float dm[3] = {0.f, 0.f, 0.f}, dsc[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
     float dcol[3] = {0.f, 0.f, 0.f}, dm2[2] = {0.f, 0.f}, dop = 0.f;
     const bool use_sh = APPEAR && q.shs != nullptr, use_cov = APPEAR && q.cov3D_precomp != nullptr;  // wave-uniform
+    const bool aa = APPEAR && q.antialias != 0;
     float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool sh_written = false;
     if (rendered && q.radii[r] > 0) {
@@ -404,6 +428,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         }
         __asm__ volatile("" : "+v"(in_p[0]), "+v"(in_p[1]), "+v"(in_p[2]), "+v"(in_rot.x), "+v"(in_rot.y), "+v"(in_rot.z), "+v"(in_rot.w),
                          "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]));
+        const float in_op = aa ? q.opacities[r] : 1.f;  // antialiasing: the raw opacity enters dL/dk
         // gather this Gaussian's instance records in rect order: fixed summation order -> reproducible gradients
         float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
         float g2x = 0.f, gz = 0.f;
@@ -497,8 +522,8 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         pv[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
         const float fx = q.fx, fy = q.fy;
         const Ewa e = ewa_setup(pv, cam.v, fx, fy, q.tanfovx, q.tanfovy);
-        float a, b, c;
-        cov2d(e, c6, a, b, c);
+        float a, b, c, a0, c0;
+        cov2d(e, c6, a, b, c, a0, c0);
 
         // (Tried: FMA contraction + 1-ulp reciprocals for the gradient-only part below, 886 -> 765 VALU instructions.  The chain to
         //  dL/dmean3D cancels strongly when the FoV clamp is active, and the fp32 oracle evaluates it uncontracted in this order: one
@@ -506,12 +531,28 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         // conic -> cov2D (a,b,c)
         const float denom = a * c - b * b;
         const float d2inv = 1.f / (denom * denom + 0.0000001f);
+        // antialiasing: the records summed g = dL/d(op k); dL/dop = g k and, above the floor, dL/dk = g op reaches (a0, b, c0) through rho (aa_factor):
+        // d rho / d a0 = h (c0^2 + h c0 + b^2) / det^2, d rho / d c0 = h (a0^2 + h a0 + b^2) / det^2, d rho / d b = -2 b h (a0 + c0 + h) / det^2 (h = 0.3,
+        // b the single off-diagonal variable -- the convention of dL_db below); dk / d rho = 1 / (2k).  a = a0 + h: dL/da0 is added to dL_da.
+        float aa_s = 0.f;
+        if (aa) {
+            bool live;
+            const float k = aa_factor(a0, b, c0, denom, live);
+            if (live) aa_s = dop * in_op / (2.f * k) / denom;  // (the second 1/det is applied to the polynomials: det^2 may overflow)
+            dop = dop * k;
+        }
         float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f, dc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         const float(*T)[3] = e.T;
         if (d2inv != 0.f) {
             dL_da = d2inv * (-c * c * dxx + 2.f * b * c * dxy + (denom - a * c) * dyy);
             dL_dc = d2inv * (-a * a * dyy + 2.f * a * b * dxy + (denom - a * c) * dxx);
             dL_db = d2inv * 2.f * (b * c * dxx - (denom + 2.f * b * b) * dxy + a * b * dyy);
+            if (aa) {
+                const float h = 0.3f;
+                dL_da += aa_s * (h * (c0 * c0 + h * c0 + b * b) / denom);
+                dL_dc += aa_s * (h * (a0 * a0 + h * a0 + b * b) / denom);
+                dL_db += aa_s * (-2.f * b * h * (a0 + c0 + h) / denom);
+            }
             dc6[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
             dc6[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
             dc6[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
@@ -662,7 +703,7 @@ void gsr_launch_preprocess(const GsrFwdParams &p, GsrSplat *splats, uint4 *binre
     GsrFwdParams q = p;
     q.fx = (float)q.W / (2.f * q.tanfovx);  // (the same correctly-rounded fp32 division the kernel used to evaluate per thread)
     q.fy = (float)q.H / (2.f * q.tanfovy);
-    if (p.shs || p.cov3D_precomp) hipLaunchKernelGGL(k_preprocess<true>, grid, block, 0, s, q, splats, binrec, wg_tab, bin_count, bin_count_fb, hdr);
+    if (p.shs || p.cov3D_precomp || p.antialias) hipLaunchKernelGGL(k_preprocess<true>, grid, block, 0, s, q, splats, binrec, wg_tab, bin_count, bin_count_fb, hdr);
     else hipLaunchKernelGGL(k_preprocess<false>, grid, block, 0, s, q, splats, binrec, wg_tab, bin_count, bin_count_fb, hdr);
 }
 
@@ -674,7 +715,7 @@ void gsr_launch_preprocess_bwd(const GsrBwdParams &p, const GsrSplat *splats, co
     q.fx = (float)q.W / (2.f * q.tanfovx);
     q.fy = (float)q.H / (2.f * q.tanfovy);
     const dim3 grid((q.P + 255) / 256), block(256);
-    const bool appear = q.shs || q.cov3D_precomp;
+    const bool appear = q.shs || q.cov3D_precomp || q.antialias;
     if (q.inst_ddepth) {  // depth / alpha backward (VALU records: inst_dop is always written)
         if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
         else hipLaunchKernelGGL((k_preprocess_bwd<false, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);

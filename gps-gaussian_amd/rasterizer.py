@@ -4,6 +4,8 @@ Mirrors the interface the reference binds at /root/reference/gaussian_renderer/_
 `GaussianRasterizationSettings` (12-field NamedTuple, no `antialiasing`), `GaussianRasterizer(raster_settings)` whose
 call returns the 2-tuple `(color[3,H,W], radii[P])`, and the autograd contract of upstream's `_RasterizeGaussians`
 (gradients for means3D, means2D, colors_precomp, opacities, scales, rotations; None for the rest) -- SURVEY.md section 8b.
+Opt-in antialiasing (the opacity-compensated 2D filter of the newer upstream interface, include/gpsgs.h GSR_FLAG_ANTIALIAS):
+`antialiasing=True` on rasterize_gaussians / GaussianRasterizer.forward, or a settings object with a truthy `antialiasing` attribute.
 
 All arithmetic happens in libgpsgs_hip.so (hand-written gfx950 kernels) through the C-ABI of include/gpsgs.h.
 There is NO eager/CPU fallback: non-GPU tensors or a missing library raise.
@@ -459,12 +461,22 @@ def _ext(rows, hint, appear=None, bin_cap=0, depth_alpha=None):
     return e
 
 
+def _antialias(rs, antialiasing):
+    """Antialiasing for this view: the keyword, or a truthy `antialiasing` attribute of the settings (the newer upstream settings' field; the
+    12-field GaussianRasterizationSettings has none).  Raises if the loaded library does not honour GSR_FLAG_ANTIALIAS -- an older one would
+    silently render without the filter."""
+    on = bool(antialiasing) or bool(getattr(rs, "antialiasing", False))
+    if on and not (_capi.lib().gsr_supported_flags() & _capi.GSR_FLAG_ANTIALIAS):
+        raise RuntimeError("gps_gaussian_amd: the loaded rasteriser library does not support antialiasing (GSR_FLAG_ANTIALIAS); rebuild it")
+    return on
+
+
 def _too_many(R):
     return RuntimeError("gps_gaussian_amd: this view needs %d (Gaussian, bin) instances, more than the 2^31 - 1 the workspace layout can address" % R)
 
 
 def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, needs_grad, out_color=None, rows=None,
-                  radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None):
+                  radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None, antialiasing=False):
     """One view's forward through the C-ABI (capacity policy, early notification, overflow repair).  `ctx` is any attribute holder: the
     autograd ctx of _RasterizeGaussians, or a plain namespace when a caller drives several views itself (render_api._RenderBatch).
     Leaves on it: raster_settings, cap, family, extra_flags, rows, saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
@@ -475,11 +487,14 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     them (read on the DEVICE), radii_out the batch-wide int32 radii array.
     depth_alpha: also render the depth map (sum z_i alpha_i T_i, unnormalised) and the alpha map (sum alpha_i T_i), background 0, with the VALU
     compositing family (include/gpsgs.h GsrViewExt.out_depth); out_depth / out_alpha: optional preallocated contiguous fp32 [H,W] (or [1,H,W])
-    tensors for them.  -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W])"""
+    tensors for them.  antialiasing (or a truthy raster_settings.antialiasing): GSR_FLAG_ANTIALIAS, each splat's opacity scaled by
+    sqrt(det(cov2D) / det(cov2D + 0.3 I)) (include/gpsgs.h), carried to the backward in ctx.
+    -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W])"""
     rs = raster_settings
     lib = _capi.lib()
     if not means3D.is_cuda:
         raise RuntimeError("gps_gaussian_amd: rasteriser inputs must live on a GPU (no CPU fallback)")
+    antialiasing = _antialias(rs, antialiasing)
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     dev = means3D.device
@@ -516,7 +531,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     if depth_alpha:
         family = 0  # the depth / alpha maps are made by the VALU kernels (forward and backward of a view must agree on the family)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
-    base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family
+    base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family | (_capi.GSR_FLAG_ANTIALIAS if antialiasing else 0)
     if mode != "none" and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("gps_gaussian_amd: the capacity check reads a header back on the host and cannot run under graph capture; "
                            "warm up eagerly, then capture with GPSGS_CHECK=none")
@@ -605,6 +620,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     ctx.extra_flags = extra
     ctx.rows = rows
     ctx.depth_alpha = bool(depth_alpha)
+    ctx.antialias = antialiasing
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
     if depth_alpha:
         return color, radii, dmaps[0], dmaps[1]
@@ -675,7 +691,8 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
                                      float(rs.tanfovx), float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(radii), _ptr(g),
                                      _ptr(d_m3), _ptr(d_m2), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_rot), _ptr(ws),
                                      ws.numel(), cap, (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | getattr(ctx, "extra_flags", _extra_flags) | ctx.family
-                                     | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD), stream, C.byref(ext))
+                                     | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD) | (_capi.GSR_FLAG_ANTIALIAS if getattr(ctx, "antialias", False) else 0),
+                                     stream, C.byref(ext))
             _capi.check(rc, "gsr_backward_ex")
     return d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov
 
@@ -745,7 +762,7 @@ _debug_keep_ws = False  # tests: both host paths leave {ws, cap, bin_cap} of the
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                return_depth_alpha=False):
+                return_depth_alpha=False, antialiasing=False):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
@@ -753,7 +770,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # stage 2 never differentiates the colours (they are input pixels, lib/GaussianRender.py:30-31): the backward then skips their sums
         ctx.color_grad = bool(ctx.needs_input_grad[3]) or sh is not None  # (dL/dsh is formed from dL/dcolour)
         out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
-                            shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha))
+                            shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha), antialiasing=antialiasing)
         if _debug_keep_ws:
             _tls.last_ws = dict(ws=ctx.saved[9], cap=ctx.cap, bin_cap=ctx.bin_cap)
         ctx.save_for_backward(*ctx.saved)
@@ -765,21 +782,26 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         if grad_out_color is None and grad_depth is None and grad_alpha is None:  # no output took part in the loss
-            return (None,) * 11
+            return (None,) * 12
         saved = ctx.saved_tensors
         d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad,
                                                                            grad_depth, grad_alpha)
         has_sh, has_cov = saved[10] is not None, saved[11] is not None
-        # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha)
+        # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha,
+        #  antialiasing)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None, None)
+                d_cov, None, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False):
+                        return_depth_alpha=False, antialiasing=False):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
-    and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says."""
+    and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
+    antialiasing=True (or a truthy raster_settings.antialiasing): the opacity-compensated 2D filter, include/gpsgs.h GSR_FLAG_ANTIALIAS."""
+    if antialiasing or getattr(raster_settings, "antialiasing", False):
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, bool(return_depth_alpha), True)
     if return_depth_alpha:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                          raster_settings, grad_arena, True)
@@ -796,13 +818,14 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None, return_depth_alpha=False):
+                grad_arena=None, return_depth_alpha=False, antialiasing=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha:
+        antialiasing = antialiasing or getattr(self.raster_settings, "antialiasing", False)
+        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing:
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -810,9 +833,9 @@ class GaussianRasterizer(nn.Module):
         # shs [P, M, 3] are evaluated up to raster_settings.sh_degree towards raster_settings.campos (upstream computeColorFromSH); cov3D_precomp
         # [P, 6] replaces scale + rotation.  The reference passes neither (gaussian_renderer/__init__.py:54-62) but constructs the settings
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
-        # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians
+        # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing: the Python host path (not the compiled one)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena, return_depth_alpha)
+                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing)
 
 
     def markVisible(self, positions):

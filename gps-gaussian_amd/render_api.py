@@ -101,10 +101,10 @@ class _RenderBatch(torch.autograd.Function):
     Numerically it IS the per-sample path: the same kernels on the same rows (tests/test_gpu_pack.py compares the bits)."""
 
     @staticmethod
-    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False):
+    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
         # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
-        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True))
+        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
@@ -124,7 +124,8 @@ class _RenderBatch(torch.autograd.Function):
                 with torch.cuda.stream(side[i]):
                     _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, out_color=out[i],
                                       rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
-                                      out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None)
+                                      out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None,
+                                      antialiasing=antialiasing)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -150,7 +151,7 @@ class _RenderBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, gdepth=None, galpha=None):
         if gout is None and gdepth is None and galpha is None:
-            return (None,) * 9
+            return (None,) * 10
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
@@ -172,12 +173,12 @@ class _RenderBatch(torch.autograd.Function):
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
-        return d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None
+        return d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None
 
 
-def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None):
+def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False):
     """Render one novel view.  Same arguments and return value as the reference's render(): returns image [3,H,W].
-    (grad_arena: internal, see pts2render.)"""
+    (grad_arena: internal, see pts2render.)  antialiasing=True: the opacity-compensated 2D filter (rasterizer.rasterize_gaussians)."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     screenspace_points = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
@@ -192,21 +193,23 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
         sh_degree=3, campos=nv['camera_center'][idx], prefiltered=False, debug=False)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     rendered_image, _ = rasterizer(means3D=pts_xyz, means2D=screenspace_points, shs=None, colors_precomp=pts_rgb,
-                                   opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena)
+                                   opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena,
+                                   antialiasing=antialiasing)
     return rendered_image
 
 
-def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None):
+def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
-    The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE."""
+    The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE.
+    antialiasing=True: as render()'s; the maps then see the filtered opacities too."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
     img, _, depth, alpha = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
-                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True)
+                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing)
     return {'img': img, 'depth': depth, 'alpha': alpha}
 
 
@@ -227,9 +230,10 @@ def _to_device_once(t, dev):
     return t
 
 
-def pts2render(data, bg_color, with_depth_alpha=False):
+def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
+    antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -249,14 +253,17 @@ def pts2render(data, bg_color, with_depth_alpha=False):
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
         if with_depth_alpha:
-            nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, True)
+            nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, True,
+                                                                                    bool(antialiasing))
+        elif antialiasing:
+            nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, False, True)
         else:
             nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha)
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False):
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False):
     """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
@@ -287,11 +294,12 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False):
                 side[i].wait_stream(cur)
             with torch.cuda.stream(side[i]):
                 if with_depth_alpha:
-                    r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga)
+                    r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
+                                  antialiasing=antialiasing)
                     out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha')))
                 else:
                     out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
-                                       grad_arena=ga).unsqueeze(0),))
+                                       grad_arena=ga, antialiasing=antialiasing).unsqueeze(0),))
     for i in range(bs):
         if side[i] is not cur:
             cur.wait_stream(side[i])

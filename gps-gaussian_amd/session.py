@@ -20,7 +20,7 @@ from . import rasterizer as RZ
 
 
 class RasterSession:
-    def __init__(self, P, width, height, device, training=True, wave_priority=True):
+    def __init__(self, P, width, height, device, training=True, wave_priority=True, antialiasing=False):
         self.P, self.W, self.H = int(P), int(width), int(height)
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
@@ -30,6 +30,8 @@ class RasterSession:
         # flight on different streams passes False (the kernels of different views then share the SIMDs and the scheme costs ~2 %)
         self.wave_priority = bool(wave_priority)
         self.lib = _capi.lib()
+        # antialiasing: every forward and backward of the session carries GSR_FLAG_ANTIALIAS (the opacity-compensated 2D filter, include/gpsgs.h)
+        self.aa_flag = _capi.GSR_FLAG_ANTIALIAS if RZ._antialias(None, antialiasing) else 0
         d, f32 = self.dev, torch.float32
         self.color = torch.empty((3, self.H, self.W), dtype=f32, device=d)
         self.radii = torch.empty((self.P,), dtype=torch.int32, device=d)
@@ -107,7 +109,7 @@ class RasterSession:
         P, W, H, lib = self.P, self.W, self.H, self.lib
         ptrs, fl, cam, family, _ = self._in
         stream = self._cur.cuda_stream
-        flags = RZ._extra_flags | family | plan_flags
+        flags = RZ._extra_flags | family | plan_flags | self.aa_flag
         self._ensure_ws(cap, self._cur, bin_cap)
         if P == 0:
             _capi.check(lib.gsr_forward(P, W, H, *ptrs, *fl, *cam, self.color.data_ptr(), self.radii.data_ptr(), self.ws.data_ptr(),
@@ -150,7 +152,7 @@ class RasterSession:
             rc = self.lib.gsr_backward_ex(self.P, self.W, self.H, *ptrs, *fl, *cam, self.radii.data_ptr(), g, G["means3D"].data_ptr(),
                                           G["means2D"].data_ptr(), G["colors"].data_ptr(), G["opacities"].data_ptr(), G["scales"].data_ptr(),
                                           G["rotations"].data_ptr(), self.ws.data_ptr(), self.nbytes, self.cap,
-                                          RZ._extra_flags | family | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD),
+                                          RZ._extra_flags | family | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD) | self.aa_flag,
                                           bstream.cuda_stream, C.byref(ext))
             _capi.check(rc, "gsr_backward_ex")
         return G

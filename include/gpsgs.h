@@ -83,6 +83,13 @@ enum {
                                        Results are unchanged.  It pays when a view's kernels have the chip to themselves (measured, config 2:
                                        forward 55 -> 51 us, backward 114 -> 110 us); with several views' kernels overlapped on other streams it
                                        costs ~2 % of the aggregate rate, so it is opt-in per call. */
+#define GSR_FLAG_ANTIALIAS 1024u /* antialiasing: the opacity-compensated screen-space filter of Mip-Splatting (upstream's `antialiasing=True`).
+                                    Each visible splat's opacity becomes opacity * k, k = sqrt(max(rho, 2.5e-5)), rho = (a0 c0 - b^2) /
+                                    ((a0 + 0.3)(c0 + 0.3) - b^2) with (a0, b, c0) its 2D covariance before the 0.3 px^2 dilation: compositing,
+                                    the alpha >= 1/255 tests and the depth / alpha maps all see that value, and the backward chains dL/dk into
+                                    the covariance.  Conic, radii, bin rects and depth order are unchanged.  Forward and backward of one view
+                                    must agree on it (the backward also needs `opacities` then).  Check gsr_supported_flags() before relying on
+                                    it: libraries before it ignore the bit. */
 #define GSR_FLAG_TIMING_STAGE(k) (GSR_FLAG_TIMING | (((unsigned)(k) + 1u) << 4)) /* ... or only stage k (GSR_STAGE_*) */
 
 /* stage ids reported by gsr_timing_read() */
@@ -92,6 +99,9 @@ enum {
 };
 
 int gpsgs_abi_version(void);
+/* The GSR_FLAG_* bits this library honours (the GSR_FLAG_TIMING_STAGE field, bits 4..7, not included).  Unknown bits are ignored by
+ * gsr_forward / gsr_backward, so a host that needs a later flag (GSR_FLAG_ANTIALIAS) checks for it here. */
+int gsr_supported_flags(void);
 /* Development aid: rows_device = 2 * bins rows of 4 u64 (zeroed by the caller), or NULL to switch it off.  While set, every tile-compositing
  * workgroup that did work records {wall clock at start, at end (100 MHz), shader cycles, HW_ID | XCC_ID << 32 | list length << 40} in row
  * blockIdx (forward) / bins + blockIdx (backward): the per-SIMD timeline tools/wg_trace.py analyses.  Process-wide, not thread-safe. */
