@@ -1,18 +1,22 @@
 """bench.py -- the hot-path benchmark the driver runs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Metric (BASELINE.json): novel views/s at 1024x1024 with ~600k pixel-Gaussians.  One "step" = one pass of the render
 hot path over one synthetic view of BASELINE config 2: HIP rasteriser forward + backward (1024x1024, P = 600,000
 Gaussians resident in HBM before the timed region), called the way the reference calls it -- GaussianRasterizer(raster_settings)(means3D=..., ...)
-+ image.backward(), /root/reference/gaussian_renderer/__init__.py:51-62 -- one view at a time with the exact capacity check: `value`.
-What a caller that owns its buffers gets from the C-ABI sessions (one view at a time, and six views in flight on six streams) is reported
-next to it (`session`), as are forward-only throughput, the stage-2 gradient set and the other BASELINE configurations.
++ image.backward(), the reference's gaussian_renderer/__init__.py:51-62 -- one view at a time with the exact capacity check: `value`.
+
+A plain run does only what `value` needs: it sets the workload up, warms up, times the steps, writes --dump-outputs and prints the JSON line
+(metric, value, unit, ms_per_step, ... and the timed blocks).  Everything else is measured with --full: what a caller that owns its buffers
+gets from the C-ABI sessions (one view at a time, and six views in flight on six streams) is reported next to `value` (`session`), as are
+forward-only throughput, the stage-2 gradient set, the other BASELINE configurations and the rows below.
+
 N > 1: every rank renders its own views (independent units, no data-path collective) -> weak scaling; the only
 collectives are the timing barrier and the MAX-over-ranks reduction of the elapsed time.
 
-The printed JSON line also carries
+With --full the printed JSON line also carries
   roofline     : the dominant kernel (backward compositing) priced against the HBM roofline with ALGORITHMIC bytes
                  (DESIGN.md "Kernels and rooflines"); its duration is measured live with hipEvents on the launch stream;
   cpu_baseline : the fp32 CPU oracle ("port": the reference's rasteriser is an external CUDA extension that cannot be
@@ -514,6 +518,9 @@ def main():
     ap.add_argument("--full-pipeline-budget", type=float, default=600.0, help="seconds the full-pipeline leg may take in total; what does not fit is skipped and says so")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step of the `value` path returned (image, radii, input gradients; rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (sessions, per-kernel table and roofline, other paths and configurations, neighbours, stage-2 path, "
+                         "full pipeline, CPU rows); --inflight, --headline-only and the --no-* options shape them.  Without it only `value` is measured")
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be >= 1")
@@ -609,6 +616,86 @@ def main():
             rast(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=None, colors_precomp=t["colors"],
                  scales=t["scales"], rotations=t["rotations"], cov3D_precomp=None)
 
+    def barrier():
+        D.barrier(local_rank)
+
+    # The host's cyclic garbage collector is switched off for the whole measurement (one collection + freeze first): a full collection of a
+    # process that has imported torch takes tens of milliseconds -- the size of the rare outlier blocks seen in the 2048^2 legs -- against
+    # timed blocks of 5-50 ms.  (Collecting before every timed block instead leaves the GPU idle for those milliseconds right before the
+    # clock starts: its clocks drop and EVERY block reads 10-15 % slower -- measured.)
+    import gc
+    gc.collect()
+    gc.freeze()
+    gc.disable()
+
+    def timed(fn, steps, warmup, multi=False):  # multi: fn(k) runs k steps itself (pipelined groups)
+        if multi:
+            fn(warmup)
+        else:
+            for _ in range(warmup):
+                fn()
+        torch.cuda.synchronize(dev)
+        barrier()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        if multi:
+            fn(steps)
+        else:
+            for _ in range(steps):
+                fn()
+        torch.cuda.synchronize(dev)
+        barrier()
+        torch.cuda.synchronize(dev)
+        return D.max_over_ranks(time.perf_counter() - t0, device=dev)
+
+    REPEATS = max(3, args.repeats)
+
+    def headline():
+        """THE HEADLINE: the step through the reference's plugin API -- GaussianRasterizer(raster_settings)(...) + image.backward(), the call shape
+        of gaussian_renderer/__init__.py:51-62 -- one view at a time, sync capacity check.  REPEATS blocks of EXACTLY --steps steps (barrier +
+        synchronize on both sides, MAX over ranks); `value` / `ms_per_step` are the median block, the quartiles are reported.  (Rounds 2-4 put the
+        C-ABI session number with six views in flight first: a caller-owned-buffer API no reference code uses -- VERDICT r04 weak 7.)
+        -> (elapsed seconds of every block, the last timed step's outputs for --dump-outputs or None)"""
+        nonlocal last_out
+        blocks = [timed(fwd_bwd, args.steps, max(5, args.warmup) if i == 0 else 0) for i in range(REPEATS)]
+        dumped = None
+        if last_out is not None:  # the last timed step's outputs, copied before any later leg runs the same module again
+            torch.cuda.synchronize(dev)
+            dumped = {"image": last_out["image"].cpu().numpy(), "radii": last_out["radii"].float().cpu().numpy(), "grad_means2D": m2.grad.cpu().numpy()}
+            dumped.update(("grad_" + k, t[k].grad.cpu().numpy()) for k in names)
+            last_out = None  # (fwd_bwd reads it at call time: the legs behind the headline keep nothing)
+        return blocks, dumped
+
+    def headline_line(api_blocks, R):
+        """The fields of the JSON line that describe `value` (a plain run prints these alone; R = measured (Gaussian, 8x8-bin) instances of the view)."""
+        elapsed = sorted(api_blocks)[REPEATS // 2]
+        q1, q3 = sorted(api_blocks)[REPEATS // 4], sorted(api_blocks)[(3 * REPEATS) // 4]
+        cfg_name = ("BASELINE config 2" if (args.res, args.gaussians, W) == (1024, 600000, 1024) else
+                    "BASELINE config 2 rendered at 2048^2 (use_hr_img)" if (args.res, args.gaussians, W) == (1024, 600000, 2048) else
+                    "BASELINE config 5" if (args.res, args.gaussians, W) == (2048, 2400000, 2048) else "non-BASELINE workload (parity / contract test size)")
+        return {
+            "metric": "novel views/sec at 1024x1024 (~600k Gaussians), 1 GPU", "value": round(world * args.steps / elapsed, 2),
+            "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s: %dx%d render of a synthetic stereo human, P=%d Gaussians, R=%d (Gaussian, 8x8-bin) instances, "
+                                   "HIP rasteriser forward+backward, one view per step per GPU" % (cfg_name, W, H, P, R),
+                       "api": "the reference's plugin API: GaussianRasterizer(raster_settings)(means3D=..., means2D=..., colors_precomp=..., opacities=..., scales=..., rotations=...) "
+                              "+ image.backward() (gaussian_renderer/__init__.py:51-62), one view at a time on the current stream",
+                       "check_mode": "sync (exact; the binning scan publishes the instance count to pinned host memory, checked on the host every forward)",
+                       "wave_priority": "GSR_FLAG_WAVE_PRIORITY (hardware wave priorities in the compositing kernels, results unchanged): on for a view that has the chip to "
+                                        "itself, off while several views are in flight (session.views_in_flight)"},
+            "repeats_ms_per_step": [round(x / args.steps * 1e3, 4) for x in api_blocks],
+            "ms_per_step_iqr": [round(q1 / args.steps * 1e3, 4), round(q3 / args.steps * 1e3, 4)]}
+
+    if not args.full:  # a plain run: set-up, warm-up and timed blocks of the headline, --dump-outputs, the line; every other leg needs --full
+        api_blocks, dumped = headline()
+        if rank == 0:
+            if dumped is not None:
+                dump_outputs(args.dump_outputs, dumped)
+            print(json.dumps(headline_line(api_blocks, int(RZ.last_stats(dev).get("last_R", 0)))))
+        D.shutdown()
+        return
+
     # ---- the headline step: forward + backward of one view through the C-ABI (gsr_forward_notify + gsr_backward), driven by
     # gps_gaussian_amd.session.RasterSession: same kernels, same exact capacity check (the scan publishes the instance count to pinned
     # host memory, the host waits for it every forward, an overflow would be re-rendered), preallocated buffers, no autograd round trip.
@@ -664,38 +751,6 @@ def main():
         sess.forward(L["m3"], L["col"], L["opa"], L["sca"], L["rot"], L["view"], L["proj"], rs.bg, rs.tanfovx, rs.tanfovy, 1.0)
         sess.backward(L["gout"])
 
-    def barrier():
-        D.barrier(local_rank)
-
-    # The host's cyclic garbage collector is switched off for the whole measurement (one collection + freeze first): a full collection of a
-    # process that has imported torch takes tens of milliseconds -- the size of the rare outlier blocks seen in the 2048^2 legs -- against
-    # timed blocks of 5-50 ms.  (Collecting before every timed block instead leaves the GPU idle for those milliseconds right before the
-    # clock starts: its clocks drop and EVERY block reads 10-15 % slower -- measured.)
-    import gc
-    gc.collect()
-    gc.freeze()
-    gc.disable()
-
-    def timed(fn, steps, warmup, multi=False):  # multi: fn(k) runs k steps itself (pipelined groups)
-        if multi:
-            fn(warmup)
-        else:
-            for _ in range(warmup):
-                fn()
-        torch.cuda.synchronize(dev)
-        barrier()
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        if multi:
-            fn(steps)
-        else:
-            for _ in range(steps):
-                fn()
-        torch.cuda.synchronize(dev)
-        barrier()
-        torch.cuda.synchronize(dev)
-        return D.max_over_ranks(time.perf_counter() - t0, device=dev)
-
     # ---- calibration (untimed): every kernel bracketed by hipEvents -> per-stage table, dominant kernel ------------------
     RZ.set_stage_timing(True)
     for _ in range(args.warmup):
@@ -725,7 +780,6 @@ def main():
     steps_pipelined(max(10, args.warmup, 2 * F) + 4 * F + args.steps)  # untimed; also lets the clocks settle under the concurrent load (one block's worth)
     torch.cuda.synchronize(dev)
     _capi.timing_read()
-    REPEATS = max(3, args.repeats)
     blocks = [timed(steps_pipelined, args.steps, 0, multi=True) for _ in range(REPEATS)]
     dom_live = _capi.timing_read()[dom_stage]
     # Second timed region: the same step, EXACTLY --steps of them, one view in flight, the dominant kernel still bracketed by hipEvents on
@@ -796,21 +850,9 @@ def main():
     sess_q1, sess_q3 = sorted(blocks)[REPEATS // 4], sorted(blocks)[(3 * REPEATS) // 4]
     R = int(RZ.last_stats(dev).get("last_R", 0))  # measured number of (Gaussian, bin) instances of this view
 
-    # ---- THE HEADLINE: the same step through the reference's plugin API -- GaussianRasterizer(raster_settings)(...) + image.backward(), the call shape
-    # of gaussian_renderer/__init__.py:51-62 -- one view at a time, sync capacity check.  REPEATS blocks of EXACTLY --steps steps (barrier +
-    # synchronize on both sides, MAX over ranks); `value` / `ms_per_step` are the median block, the quartiles are reported.  (Rounds 2-4 put the
-    # C-ABI session number with six views in flight first: a caller-owned-buffer API no reference code uses -- VERDICT r04 weak 7.)
-    api_blocks = [timed(fwd_bwd, args.steps, max(5, args.warmup) if i == 0 else 0) for i in range(REPEATS)]
+    # ---- THE HEADLINE (headline() above), timed here behind the session regions
+    api_blocks, dumped = headline()
     elapsed = sorted(api_blocks)[REPEATS // 2]
-    q1, q3 = sorted(api_blocks)[REPEATS // 4], sorted(api_blocks)[(3 * REPEATS) // 4]
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * args.steps / elapsed
-    dumped = None
-    if last_out is not None:  # the last timed step's outputs, copied before any later leg runs the same module again
-        torch.cuda.synchronize(dev)
-        dumped = {"image": last_out["image"].cpu().numpy(), "radii": last_out["radii"].float().cpu().numpy(), "grad_means2D": m2.grad.cpu().numpy()}
-        dumped.update(("grad_" + k, t[k].grad.cpu().numpy()) for k in names)
-        last_out = None  # (fwd_bwd reads it at call time: the legs below keep nothing)
     # ... and the same blocks with the process pinned next to its GPU (one rank only; the remaining GPU legs keep the pin, the CPU legs drop it)
     el_pinned = None
     if cpu_slice is None and world == 1:
@@ -1017,22 +1059,8 @@ def main():
         dump_outputs(args.dump_outputs, dumped)
     if rank == 0:
         rate = lambda el: round(world * args.steps / el, 2) if el else None  # noqa: E731
-        cfg_name = ("BASELINE config 2" if (args.res, args.gaussians, W) == (1024, 600000, 1024) else
-                    "BASELINE config 2 rendered at 2048^2 (use_hr_img)" if (args.res, args.gaussians, W) == (1024, 600000, 2048) else
-                    "BASELINE config 5" if (args.res, args.gaussians, W) == (2048, 2400000, 2048) else "non-BASELINE workload (parity / contract test size)")
-        line = {
-            "metric": "novel views/sec at 1024x1024 (~600k Gaussians), 1 GPU", "value": round(value, 2),
-            "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: %dx%d render of a synthetic stereo human, P=%d Gaussians, R=%d (Gaussian, 8x8-bin) instances, "
-                                   "HIP rasteriser forward+backward, one view per step per GPU" % (cfg_name, W, H, P, R),
-                       "api": "the reference's plugin API: GaussianRasterizer(raster_settings)(means3D=..., means2D=..., colors_precomp=..., opacities=..., scales=..., rotations=...) "
-                              "+ image.backward() (gaussian_renderer/__init__.py:51-62), one view at a time on the current stream",
-                       "check_mode": "sync (exact; the binning scan publishes the instance count to pinned host memory, checked on the host every forward)",
-                       "wave_priority": "GSR_FLAG_WAVE_PRIORITY (hardware wave priorities in the compositing kernels, results unchanged): on for a view that has the chip to "
-                                        "itself, off while several views are in flight (session.views_in_flight)"},
-            "repeats_ms_per_step": [round(x / args.steps * 1e3, 4) for x in api_blocks],
-            "ms_per_step_iqr": [round(q1 / args.steps * 1e3, 4), round(q3 / args.steps * 1e3, 4)],
+        line = headline_line(api_blocks, R)
+        line.update({
             # the same kernels for a caller that owns its buffers (gps_gaussian_amd.session.RasterSession: two C-ABI calls per view, preallocated outputs /
             # workspace / gradients) -- an API no reference code uses: one view at a time, and F independent views in flight on F HIP streams
             "session": {"single_view_in_flight_views_per_s": round(world * n_single / el_single, 2),
@@ -1040,7 +1068,7 @@ def main():
                         "views_in_flight_ms_per_step": round(sess_elapsed / args.steps * 1e3, 4),
                         "views_in_flight_ms_per_step_iqr": [round(sess_q1 / args.steps * 1e3, 4), round(sess_q3 / args.steps * 1e3, 4)]},
             "single_view_in_flight_views_per_s": round(world * n_single / el_single, 2),
-            "autograd_api_views_per_s": round(value, 2),
+            "autograd_api_views_per_s": line["value"],
             "cpu_affinity": ({"rank0_cpus": len(cpu_slice), "cpus": sorted(cpu_slice)[:16],
                               "how": ("NOT pinned while `value` was measured; dist.pin_near_gpu (one L3 domain on the GPU's NUMA node) for plugin_api_pinned_views_per_s and the "
                                       "GPU legs behind it" if pinned_one_rank else "dist.set_cpu_affinity: this rank's slice")}
@@ -1060,7 +1088,7 @@ def main():
             "stage2_path": stage2,
             "configs": configs,
             "full_pipeline": full_pipeline,
-        }
+        })
         print(json.dumps(line))
     D.shutdown()
 

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_line_has_the_contract_fields():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -60,13 +60,31 @@ def test_bench_json_line_has_the_contract_fields():
         assert nb[k]["forward"]["us"] > 0 and 0 < nb[k]["forward"]["hbm_frac"] < 1 and nb[k]["backward"]["algorithmic_bytes"] > 0, k
 
 
+def test_plain_run_measures_the_headline_only():
+    """Without --full, bench.py sets up, warms up and times `value` alone: the line carries the headline's fields and none of the secondary legs."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000"]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "repeats_ms_per_step", "ms_per_step_iqr"):
+        assert k in d, k
+    assert d["metric"] == "novel views/sec at 1024x1024 (~600k Gaussians), 1 GPU" and d["unit"] == "views/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and "workload" in d["config"]
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 0.02
+    assert len(d["repeats_ms_per_step"]) == 15 and d["ms_per_step"] == sorted(d["repeats_ms_per_step"])[7]     # the median of 15 timed blocks
+    assert not set(d) & {"session", "roofline", "stages", "cpu_baseline", "stage2_path", "neighbours", "configs", "full_pipeline"}
+
+
 def test_bench_two_ranks_on_one_gpu_over_gloo():
     """The multi-rank bench path (env rendezvous, per-rank workload, barrier + MAX-over-ranks timing, whole-job aggregate, agreed failure
     handling of the stage-2 leg with its gradient all-reduce) exercised on the 1-GPU box: two ranks share device 0
     (GPSGS_BENCH_SINGLE_DEVICE=1) and talk over gloo instead of RCCL.  No 2/4/8-GPU number exists; this only proves the code path."""
     env = dict(os.environ, GPSGS_BENCH_SINGLE_DEVICE="1", GPSGS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29547",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -89,7 +107,7 @@ def test_plain_command_with_gpus_2_starts_two_ranks():
     env = dict(os.environ, GPSGS_BENCH_SINGLE_DEVICE="1", GPSGS_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -111,7 +129,7 @@ def test_world_1_through_rccl():
     """GPSGS_DIST_FORCE=1: one rank, but the process group IS initialised with backend nccl (= RCCL) and the stage-2 exchange step (mean
     all-reduce of 5,144,408 gradients, one bucket) IS issued -- RCCL's communicator set-up and its all-reduce kernel run on the MI355X."""
     env = dict(os.environ, GPSGS_DIST_FORCE="1", GPSGS_BENCH_BACKEND="nccl", MASTER_ADDR="127.0.0.1", MASTER_PORT="29549", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "256", "--gaussians", "30000", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -25,7 +25,7 @@ def main():
     src, tag = sys.argv[1], sys.argv[2]
     d = load(src)
     rf, st, s2, sess = d["roofline"], d["stages"], d.get("stage2_gradient_set") or {}, d["session"]
-    L = ["Numbers of `python bench.py` on ONE MI355X (%s; source: `%s`; BASELINE config 2 = 1024x1024, 600,000 Gaussians; synthetic data; box-to-box spread of one commit is ~2 %%):" % (
+    L = ["Numbers of `python bench.py --full` on ONE MI355X (%s; source: `%s`; BASELINE config 2 = 1024x1024, 600,000 Gaussians; synthetic data; box-to-box spread of one commit is ~2 %%):" % (
         tag, os.path.relpath(src, ROOT) if os.path.isabs(src) else src), "",
          "| | rate | ms per view / iteration |", "|---|---|---|",
          "| **config 2, raster forward + backward through the reference's plugin API** (`GaussianRasterizer` + `backward()`, one view at a time, exact capacity check): `value` | **%.0f views/s** | %.4f (quartiles %.4f - %.4f) |" % (

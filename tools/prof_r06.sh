@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-CMD="python $ROOT/bench.py --steps 12 --warmup 3 --repeats 5 --no-cpu-baseline --no-configs --no-full-pipeline"
+CMD="python $ROOT/bench.py --full --steps 12 --warmup 3 --repeats 5 --no-cpu-baseline --no-configs --no-full-pipeline"
 ONE="$CMD --inflight 1 --headline-only"
 REG="python $ROOT/tools/stage_times.py --families tiles --steps 10 --res 1024 --render-res 2048 --gaussians 550000 --attributes untrained --seed-offset 77"
 KRE='k_composite|k_preprocess|k_scatter|k_sort|k_scan|k_zero16'

@@ -5,6 +5,7 @@ and prints, per N, the JSON record the driver would parse.  With fewer GPUs than
 (GPSGS_BENCH_SINGLE_DEVICE=1, GPSGS_BENCH_BACKEND=gloo): a FUNCTIONAL rehearsal of the multi-rank path -- env rendezvous, per-rank workload,
 barrier + MAX-over-ranks timing, whole-job aggregate, the stage-2 leg's gradient all-reduce -- so that the first real 8-GPU lease is a
 measurement and not a debug session.  The values it prints at N > 1 on one GPU are NOT scaling numbers (the ranks time-share one chip) and say so.
+Each run adds --full (without the configs and full-pipeline legs), so that the stage-2 leg and its gradient all-reduce run at every N.
 
     python tools/scale_dry_run.py [--ns 1,2,4,8] [--steps 5] [--warmup 2] [--res 256 --gaussians 30000]
 """
@@ -36,7 +37,7 @@ def main():
         if shared:
             env.update(GPSGS_BENCH_SINGLE_DEVICE="1", GPSGS_BENCH_BACKEND="gloo")
         bench = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup), "--res", str(a.res), "--gaussians", str(a.gaussians),
-                 "--no-full-pipeline", "--no-configs"]
+                 "--full", "--no-full-pipeline", "--no-configs"]
         cmd = ([sys.executable] + bench) if n == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
                                                         "--master-port", str(a.port + i)] + bench
         t0 = time.perf_counter()
