@@ -364,12 +364,14 @@ extern "C" int gsr_forward(int P, int width, int height, const float *means3D, c
                           bg, out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, nullptr, 0u, nullptr);
 }
 
-extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
-                               const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
-                               const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
-                               const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
-                               float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
-                               int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
+namespace {
+// gsr_backward_ex, and with cam (gsr_backward_camera) the camera gradients too: the same validation, the same launches up to the preprocess
+// backward, which then runs its CAMGRAD instantiation (bit-identical per-Gaussian results) and the fixed-order sum of the workgroup partials
+int backward_impl(int P, int width, int height, const float *means3D, const float *colors, const float *opacities, const float *scales,
+                  const float *rotations, float scale_modifier, float tanfovx, float tanfovy, const float *viewmatrix, const float *projmatrix,
+                  const float *bg, const int *radii, const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                  float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes, int64_t instance_capacity,
+                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam) {
     (void)colors;  // already folded into the splat records of the workspace (so are the opacities -- read again only with antialiasing)
     const bool antialias = (flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
@@ -378,7 +380,17 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     if ((reinterpret_cast<uintptr_t>(dL_ddepth) | reinterpret_cast<uintptr_t>(dL_dalpha)) & 3u) return GPSGS_E_INVALID;
     if (extras) flags &= ~GSR_FLAG_COMPOSITE_TILES;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
-    if (P == 0) return GPSGS_OK;
+    if (P == 0) {
+        if (cam) {  // nothing rendered: the camera gradients are zeros
+            const float *outs[3] = {cam->d_view, cam->d_proj, cam->d_campos};
+            const size_t n[3] = {16, 16, 3};
+            for (int k = 0; k < 3; k++)
+                if (outs[k] && hipMemsetAsync(const_cast<float *>(outs[k]), 0, n[k] * sizeof(float), (hipStream_t)stream) != hipSuccess) return GPSGS_E_LAUNCH;
+            return check((hipStream_t)stream, flags);
+        }
+        return GPSGS_OK;
+    }
+    if (cam && cam->scratch && (reinterpret_cast<uintptr_t>(cam->scratch) & 3u)) return GPSGS_E_INVALID;
     const float *shs = ext ? ext->shs : nullptr, *cov3D_precomp = ext ? ext->cov3D_precomp : nullptr;
     if (!means3D || !viewmatrix || !projmatrix || !bg || !radii || !dL_dpix || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity || !workspace) return GPSGS_E_INVALID;
     if (!shs && !dL_dcolors) return GPSGS_E_INVALID;
@@ -439,9 +451,43 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
     {
         trace("preprocess_bwd", P, width, height, (long long)instance_capacity, flags);
         StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
-        gsr_launch_preprocess_bwd(b, splats, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr, s);
+        gsr_launch_preprocess_bwd(b, splats, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr, s, cam);
     }
     return check(s, flags);
+}
+}  // namespace
+
+extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                               const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                               const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                               const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                               float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                               int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
+    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
+                         instance_capacity, flags, stream, ext, nullptr);
+}
+
+extern "C" size_t gsr_camera_grad_scratch_bytes(int P) {
+    if (P <= 0) return 0;
+    return sizeof(float) * (size_t)GSR_CAMGRAD_TERMS * (size_t)((P + 255) / 256);  // one partial per term and preprocess_bwd workgroup
+}
+
+extern "C" int gsr_backward_camera(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                   const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                   const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                                   const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                                   float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                                   int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                                   float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes) {
+    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
+        return GPSGS_E_INVALID;
+    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
+    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
+    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
+                         instance_capacity, flags, stream, ext, want ? &cam : nullptr);
 }
 
 extern "C" int gsr_backward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,

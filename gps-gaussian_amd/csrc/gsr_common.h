@@ -574,5 +574,16 @@ __device__ __forceinline__ void gsr_view_rows(const uint32_t *__restrict__ row_r
     }
 }
 #endif
+// Camera gradients (gsr_backward_camera): the 27 live terms of dL/d(viewmatrix, projmatrix, campos) -- viewmatrix rows 0-2, projmatrix rows 0, 1
+// and 3, campos -- are summed per preprocess_bwd workgroup into scratch (GSR_CAMGRAD_TERMS floats per workgroup of 256 Gaussians), then into
+// the 35 outputs (16 + 16 + 3, the structural zeros included).  d_view / d_proj / d_campos: NULL = not wanted.
+constexpr int GSR_CAMGRAD_TERMS = 27;
+constexpr int GSR_CAMGRAD_OUTPUTS = 35;
+struct GsrCamGrad {
+    float *scratch;
+    float *d_view, *d_proj, *d_campos;
+};
+// cam: NULL = the per-Gaussian gradients only (the existing instantiations); non-NULL = the CAMGRAD instantiations + the reduce launch
 void gsr_launch_preprocess_bwd(const GsrBwdParams &p, const GsrSplat *splats, const uint32_t *goff, const uint32_t *gpart,
-                               const uint8_t *inst_valid, const float *inst_dop, const GsrGradAcc *inst_grad, const GsrHeader *hdr, hipStream_t s);
+                               const uint8_t *inst_valid, const float *inst_dop, const GsrGradAcc *inst_grad, const GsrHeader *hdr, hipStream_t s,
+                               const GsrCamGrad *cam = nullptr);

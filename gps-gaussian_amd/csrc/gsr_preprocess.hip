@@ -177,6 +177,36 @@ __device__ __forceinline__ void sh_color(int deg, const float *__restrict__ sh, 
 // The (Gaussian, bin) predicate of the COUNT pass: small rects (<= 32 cells) are tested per cell and the outcomes kept as a bit mask for k_scatter;
 // large rects go by row intervals (gsr_row_cells) when the conic allows, per cell otherwise -- k_scatter re-derives either from the record
 // and the threshold stored in the mask word (gsr_masked_hit).
+// ---- camera gradients (CAMGRAD): fixed-order workgroup sums ---------------------------------------------------------------------------------------
+// A butterfly over the wave (the two lanes of a pair add the same two numbers: every lane ends with the same bits), then the four waves' sums in
+// wave order through LDS.  Every thread of the 256-thread workgroup must call it; thread 0's result is the workgroup's sum.
+__device__ __forceinline__ float camgrad_wave_sum(float x) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) x += __shfl_xor(x, d, 64);
+    return x;
+}
+__device__ __forceinline__ float camgrad_block_sum(float x, float *s_w) {
+    x = camgrad_wave_sum(x);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+// the workgroup's GSR_CAMGRAD_TERMS sums -> part[term * gridDim.x + blockIdx.x]
+__device__ __forceinline__ void camgrad_block_partial(float (&cg)[GSR_CAMGRAD_TERMS], float *__restrict__ part) {
+    __shared__ float s_w[4][GSR_CAMGRAD_TERMS];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < GSR_CAMGRAD_TERMS; k++) {
+        const float x = camgrad_wave_sum(cg[k]);
+        if (lane == 0) s_w[wid][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < GSR_CAMGRAD_TERMS) {
+        const int k = threadIdx.x;
+        part[(size_t)k * gridDim.x + blockIdx.x] = ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k];
+    }
+}
+
 struct CountHit {
     GsrHit h;
     GsrRowSpan rs;
@@ -396,16 +426,22 @@ __global__ __launch_bounds__(GSR_BIN_THREADS) void k_preprocess(GsrFwdParams q, 
 // EXTRA: the records carry a tenth sum, dL/dz (q.inst_ddepth: the opt-in depth map's gradient), streamed with the others in the same slot order; it
 // reaches dL/dmeans3D through the view matrix's third row (z = viewmatrix[:, 2] . (p, 1)).  Never combined with DOPREC (the depth / alpha kernels
 // are the VALU family's).
-template <bool APPEAR, bool DOPREC, bool EXTRA = false>
+// CAMGRAD (instantiated with APPEAR = true only): each Gaussian's share of dL/d(viewmatrix, projmatrix, campos) is formed from the intermediates
+// below and summed over the workgroup in a fixed order (camgrad_block_partial); the workgroup writes its GSR_CAMGRAD_TERMS partial sums to
+// cam_part (term-major, gridDim.x per term) and k_camgrad_reduce sums those.  Every thread of the workgroup takes part, threads behind the view's
+// last Gaussian with zeros.  cam_part is a trailing argument: the other instantiations never read it (their argument offsets are unchanged).
+template <bool APPEAR, bool DOPREC, bool EXTRA = false, bool CAMGRAD = false>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const GsrSplat *__restrict__ splats,
                                                         const uint32_t *__restrict__ goff, const uint32_t *__restrict__ gpart,
                                                         const uint8_t *__restrict__ inst_valid, const float *__restrict__ inst_dop,
-                                                        const GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr) {
+                                                        const GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr,
+                                                        float *__restrict__ cam_part) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     uint32_t row0;
     int nP;
     gsr_view_rows(q.row_range, q.P, row0, nP);
-    if (i >= nP) return;
+    const bool in_view = i < nP;
+    if (!CAMGRAD && !in_view) return;
     const size_t r = (size_t)row0 + (size_t)i;  // row of the batch-wide input / gradient arrays (= i without a row range)
     // an overflowed forward rendered nothing: inst_valid / inst_grad were never written (and the slot range may not even fit the
     // workspace), so every Gaussian gets an exact zero gradient instead of a gather over garbage
@@ -416,7 +452,13 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
     const bool aa = APPEAR && q.antialias != 0;
     float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool sh_written = false;
-    if (rendered && q.radii[r] > 0) {
+    // camera-gradient shares (CAMGRAD): view rows 0-2 of columns 0-3, proj rows 0, 1, 3 of columns 0-3, campos (camgrad_block_partial's order)
+    float cg[CAMGRAD ? GSR_CAMGRAD_TERMS : 1];
+    if constexpr (CAMGRAD) {
+#pragma unroll
+        for (int k = 0; k < GSR_CAMGRAD_TERMS; k++) cg[k] = 0.f;
+    }
+    if (rendered && (!CAMGRAD || in_view) && q.radii[r] > 0) {
         const Cam cam = load_cam(q.view, q.proj);
         // the per-Gaussian inputs of the chain rule are requested BEFORE the record gather, so they travel alongside it
         float in_p[3] = {q.means3D[3 * r], q.means3D[3 * r + 1], q.means3D[3 * r + 2]};
@@ -597,6 +639,29 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
             dm[1] += v[6] * gz;
             dm[2] += v[10] * gz;
         }
+        if constexpr (CAMGRAD) {
+            // view: pv = V (p, 1) -> dL/dV[r][c] += dt[r] p~[c]; T = J W (W = V's upper 3x3, J the clamped Jacobian the forward used) -> dL/dW += J^T dT
+            const float pt[4] = {p[0], p[1], p[2], 1.f};
+            const float dt[3] = {dtx, dty, dtz + gz};
+            const float J00 = fx / e.t[2], J02 = -(fx * e.t[0]) / (e.t[2] * e.t[2]);
+            const float J11 = fy / e.t[2], J12 = -(fy * e.t[1]) / (e.t[2] * e.t[2]);
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+#pragma unroll
+                for (int rr = 0; rr < 3; rr++) cg[3 * c + rr] = dt[rr] * pt[c];
+                if (c < 3) {
+                    cg[3 * c + 0] += J00 * dT[0][c];
+                    cg[3 * c + 1] += J11 * dT[1][c];
+                    cg[3 * c + 2] += J02 * dT[0][c] + J12 * dT[1][c];
+                }
+            }
+            // proj: h = F (p, 1), mean2D = (h0, h1) / (h3 + 1e-7) -> dL/dh = (dm2_0 w, dm2_1 w, 0, -(dm2_0 h0 + dm2_1 h1) w^2); row 2 is never read
+            const float dh[3] = {dm2[0] * mw, dm2[1] * mw, -(dm2[0] * mul1 + dm2[1] * mul2)};
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) cg[12 + 3 * c + k] = dh[k] * pt[c];
+        }
 
         if (use_sh) {
             // colour -> SH coefficients, and -> mean3D through the view direction (upstream computeColorFromSH backward): the colour and its
@@ -631,6 +696,11 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
             dm[0] += ((sum2 - raw[0] * raw[0]) * ddir[0] - raw[1] * raw[0] * ddir[1] - raw[2] * raw[0] * ddir[2]) * invsum32;
             dm[1] += (-raw[0] * raw[1] * ddir[0] + (sum2 - raw[1] * raw[1]) * ddir[1] - raw[2] * raw[1] * ddir[2]) * invsum32;
             dm[2] += (-raw[0] * raw[2] * ddir[0] - raw[1] * raw[2] * ddir[1] + (sum2 - raw[2] * raw[2]) * ddir[2]) * invsum32;
+            if constexpr (CAMGRAD) {  // raw = mean - campos: the campos share is the negative of the term just added to the mean's (the same expressions)
+                cg[24] = -(((sum2 - raw[0] * raw[0]) * ddir[0] - raw[1] * raw[0] * ddir[1] - raw[2] * raw[0] * ddir[2]) * invsum32);
+                cg[25] = -((-raw[0] * raw[1] * ddir[0] + (sum2 - raw[1] * raw[1]) * ddir[1] - raw[2] * raw[1] * ddir[2]) * invsum32);
+                cg[26] = -((-raw[0] * raw[2] * ddir[0] - raw[1] * raw[2] * ddir[1] + (sum2 - raw[2] * raw[2]) * ddir[2]) * invsum32);
+            }
         }
         if (use_cov) {
 #pragma unroll
@@ -660,6 +730,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         dq[2] = 2.f * (qx * (dR[0][1] + dR[1][0]) + qr * (dR[0][2] - dR[2][0]) + qz * (dR[1][2] + dR[2][1])) - 4.f * qy * (dR[0][0] + dR[2][2]);
         dq[3] = 2.f * (qr * (dR[1][0] - dR[0][1]) + qx * (dR[0][2] + dR[2][0]) + qy * (dR[1][2] + dR[2][1])) - 4.f * qz * (dR[0][0] + dR[1][1]);
     }
+    if (!CAMGRAD || in_view) {
     const size_t i3 = 3 * r;
     q.dL_dmeans3D[i3] = dm[0]; q.dL_dmeans3D[i3 + 1] = dm[1]; q.dL_dmeans3D[i3 + 2] = dm[2];
     q.dL_dmeans2D[i3] = dm2[0]; q.dL_dmeans2D[i3 + 1] = dm2[1]; q.dL_dmeans2D[i3 + 2] = 0.f;
@@ -676,6 +747,41 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(GsrBwdParams q, const Gs
         float *out = q.dL_dsh + (size_t)3 * q.sh_coeffs * r;
         for (int k = 0; k < 3 * (int)q.sh_coeffs; k++) out[k] = 0.f;
     }
+    }
+    if constexpr (CAMGRAD) camgrad_block_partial(cg, cam_part);
+}
+
+// the camera-gradient sums of the whole view (CAMGRAD): block o of GSR_CAMGRAD_OUTPUTS writes output element o -- dL/dviewmatrix[0..15],
+// dL/dprojmatrix[0..15], dL/dcampos[0..2], flat column-major (4 c + r) -- as the sum of the nb workgroup partials of its term, in a fixed order:
+// thread t adds partials t, t + 256, ... in turn, then the 256 sums go through camgrad_block_sum.  The structural zeros (viewmatrix row 3,
+// projmatrix row 2) are written as zeros.  A NULL output is not wanted.  Written, never accumulated: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void k_camgrad_reduce(const float *__restrict__ part, int nb, float *__restrict__ d_view, float *__restrict__ d_proj,
+                                                        float *__restrict__ d_campos) {
+    const int o = blockIdx.x;
+    float *dst;
+    int term;
+    if (o < 16) {
+        dst = d_view ? d_view + o : nullptr;
+        term = (o & 3) == 3 ? -1 : 3 * (o >> 2) + (o & 3);
+    } else if (o < 32) {
+        const int f = o - 16, rr = f & 3;
+        dst = d_proj ? d_proj + f : nullptr;
+        term = rr == 2 ? -1 : 12 + 3 * (f >> 2) + (rr == 3 ? 2 : rr);
+    } else {
+        dst = d_campos ? d_campos + (o - 32) : nullptr;
+        term = 24 + (o - 32);
+    }
+    if (!dst) return;  // (block-uniform: the whole workgroup leaves)
+    if (term < 0) {
+        if (threadIdx.x == 0) *dst = 0.f;
+        return;
+    }
+    const float *src = part + (size_t)term * nb;
+    float x = 0.f;
+    for (int k = threadIdx.x; k < nb; k += 256) x += src[k];
+    __shared__ float s_w[4];
+    x = camgrad_block_sum(x, s_w);
+    if (threadIdx.x == 0) *dst = x;
 }
 
 // upstream checkFrustum / markVisible (GaussianRasterizer.markVisible of the module the reference imports at
@@ -709,18 +815,26 @@ void gsr_launch_preprocess(const GsrFwdParams &p, GsrSplat *splats, uint4 *binre
 
 void gsr_launch_preprocess_bwd(const GsrBwdParams &p, const GsrSplat *splats, const uint32_t *goff, const uint32_t *gpart,
                                const uint8_t *inst_valid, const float *inst_dop, const GsrGradAcc *inst_grad, const GsrHeader *hdr,
-                               hipStream_t s) {
+                               hipStream_t s, const GsrCamGrad *cam) {
     if (p.P <= 0) return;
     GsrBwdParams q = p;
     q.fx = (float)q.W / (2.f * q.tanfovx);
     q.fy = (float)q.H / (2.f * q.tanfovy);
     const dim3 grid((q.P + 255) / 256), block(256);
     const bool appear = q.shs || q.cov3D_precomp || q.antialias;
+    if (cam) {  // camera gradients: the APPEAR side's CAMGRAD instantiations (they serve the plain inputs too), then the fixed-order sum of the partials
+        float *part = cam->scratch;
+        if (q.inst_ddepth) hipLaunchKernelGGL((k_preprocess_bwd<true, false, true, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, part);
+        else if (q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<true, true, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, part);
+        else hipLaunchKernelGGL((k_preprocess_bwd<true, false, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, part);
+        hipLaunchKernelGGL(k_camgrad_reduce, dim3(GSR_CAMGRAD_OUTPUTS), dim3(256), 0, s, (const float *)part, (int)grid.x, cam->d_view, cam->d_proj, cam->d_campos);
+        return;
+    }
     if (q.inst_ddepth) {  // depth / alpha backward (VALU records: inst_dop is always written)
-        if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
-        else hipLaunchKernelGGL((k_preprocess_bwd<false, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
-    } else if (appear && q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
-    else if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
-    else if (q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
-    else hipLaunchKernelGGL((k_preprocess_bwd<false, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr);
+        if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
+        else hipLaunchKernelGGL((k_preprocess_bwd<false, false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
+    } else if (appear && q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
+    else if (appear) hipLaunchKernelGGL((k_preprocess_bwd<true, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
+    else if (q.dop_in_record) hipLaunchKernelGGL((k_preprocess_bwd<false, true>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
+    else hipLaunchKernelGGL((k_preprocess_bwd<false, false>), grid, block, 0, s, q, splats, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr);
 }

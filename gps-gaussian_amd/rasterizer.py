@@ -6,6 +6,8 @@ call returns the 2-tuple `(color[3,H,W], radii[P])`, and the autograd contract o
 (gradients for means3D, means2D, colors_precomp, opacities, scales, rotations; None for the rest) -- SURVEY.md section 8b.
 Opt-in antialiasing (the opacity-compensated 2D filter of the newer upstream interface, include/gpsgs.h GSR_FLAG_ANTIALIAS):
 `antialiasing=True` on rasterize_gaussians / GaussianRasterizer.forward, or a settings object with a truthy `antialiasing` attribute.
+Opt-in camera gradients (include/gpsgs.h gsr_backward_camera): `camera_grad=True` on rasterize_gaussians / GaussianRasterizer.forward makes
+raster_settings.viewmatrix, projmatrix and campos differentiable; without it they are constants, as upstream.
 
 All arithmetic happens in libgpsgs_hip.so (hand-written gfx950 kernels) through the C-ABI of include/gpsgs.h.
 There is NO eager/CPU fallback: non-GPU tensors or a missing library raise.
@@ -633,13 +635,15 @@ def _map_grad(g):
     return g.detach().to(dtype=torch.float32).contiguous()
 
 
-def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_depth=None, grad_alpha=None):
+def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_depth=None, grad_alpha=None, cam_out=None):
     """One view's backward through the C-ABI.  color_grad=False: the caller does not need dL/dcolours (GSR_FLAG_NO_COLOR_GRAD: the tile
     family leaves the colour sums out; the returned colour gradient is zeros / not meaningful).  saved: the tuple _forward_impl left in ctx.saved; arena: optional five preallocated
     gradient tensors (means3D, colours, opacities, scales, rotations) -- for a row-range view (ctx.rows) they are REQUIRED and batch-wide,
     the view's rows of them are written.  -> (d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov); d_sh / d_cov are None unless the forward was given
     SH coefficients / precomputed covariances (d_sc, d_rot are then not meaningful).  grad_depth / grad_alpha: gradients of the depth and alpha
-    maps of a depth_alpha forward ([H,W] or [1,H,W]; None = zero); grad_out_color may then be None too."""
+    maps of a depth_alpha forward ([H,W] or [1,H,W]; None = zero); grad_out_color may then be None too.  cam_out: None, or three contiguous fp32
+    device tensors / None -- dL/d(viewmatrix [16], projmatrix [16], campos [3]) are WRITTEN into them (gsr_backward_camera: the per-Gaussian
+    gradients keep their bits)."""
     rs = ctx.raster_settings
     lib = _capi.lib()
     m3, col, opa, sca, rot, view, proj, bg, radii, ws = saved[:10]
@@ -685,15 +689,29 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
             d_col, d_sc, d_op = b_col.view(P, 3), b_sc.view(P, 3), b_op.view(P, 1)
         d_sh = torch.empty_like(sh) if sh is not None else None
         d_cov = torch.empty_like(cov) if cov is not None else None
+        if cam_out is not None and not any(t is not None for t in cam_out):
+            cam_out = None
         if P > 0:
             ext = _ext(rows, 0, (sh, int(rs.sh_degree), campos, cov, d_sh, d_cov) if (sh is not None or cov is not None) else None, bin_cap, dmaps)
-            rc = lib.gsr_backward_ex(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier),
-                                     float(rs.tanfovx), float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(radii), _ptr(g),
-                                     _ptr(d_m3), _ptr(d_m2), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_rot), _ptr(ws),
-                                     ws.numel(), cap, (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | getattr(ctx, "extra_flags", _extra_flags) | ctx.family
-                                     | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD) | (_capi.GSR_FLAG_ANTIALIAS if getattr(ctx, "antialias", False) else 0),
-                                     stream, C.byref(ext))
-            _capi.check(rc, "gsr_backward_ex")
+            args = (P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier),
+                    float(rs.tanfovx), float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(radii), _ptr(g),
+                    _ptr(d_m3), _ptr(d_m2), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_rot), _ptr(ws),
+                    ws.numel(), cap, (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | getattr(ctx, "extra_flags", _extra_flags) | ctx.family
+                    | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD) | (_capi.GSR_FLAG_ANTIALIAS if getattr(ctx, "antialias", False) else 0),
+                    stream, C.byref(ext))
+            if cam_out is None:
+                rc = lib.gsr_backward_ex(*args)
+                _capi.check(rc, "gsr_backward_ex")
+            else:
+                # one scratch slab per view in flight (the stream-ordered allocator keeps it alive until this stream's kernels are done)
+                nbytes = lib.gsr_camera_grad_scratch_bytes(P)
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                rc = lib.gsr_backward_camera(*args, *(_ptr(t) for t in cam_out), _ptr(scratch), nbytes)
+                _capi.check(rc, "gsr_backward_camera")
+        elif cam_out is not None:
+            for t in cam_out:
+                if t is not None:
+                    t.zero_()
     return d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov
 
 
@@ -759,14 +777,30 @@ def _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations
 _debug_keep_ws = False  # tests: both host paths leave {ws, cap, bin_cap} of the last forward in _tls.last_ws (export_state needs them)
 
 
+def _cam_grads(need, like, dev):
+    """Device outputs for the camera gradients whose inputs need one: [16], [16], [3] fp32 (None where not needed)."""
+    return tuple(torch.empty((n,), dtype=torch.float32, device=dev) if w and t is not None else None for w, t, n in zip(need, like, (16, 16, 3)))
+
+
+def _cam_grad_as(g, t):
+    """A camera gradient in the input's own shape, dtype and device (a pinned CPU camera tensor gets a CPU gradient)."""
+    if g is None or t is None:
+        return None
+    return g.reshape(t.shape).to(device=t.device, dtype=t.dtype)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                return_depth_alpha=False, antialiasing=False):
+                return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
         ctx.grad_arena = grad_arena
+        # camera_grad: viewmatrix / projmatrix / campos are the settings' own tensors, passed again as inputs so that autograd hands them their
+        # gradients (the forward itself reads them from raster_settings, as always)
+        ctx.camera_grad = bool(camera_grad)
+        ctx.cams = (viewmatrix, projmatrix, campos) if camera_grad else None
         # stage 2 never differentiates the colours (they are input pixels, lib/GaussianRender.py:30-31): the backward then skips their sums
         ctx.color_grad = bool(ctx.needs_input_grad[3]) or sh is not None  # (dL/dsh is formed from dL/dcolour)
         out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
@@ -782,23 +816,35 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         if grad_out_color is None and grad_depth is None and grad_alpha is None:  # no output took part in the loss
-            return (None,) * 12
+            return (None,) * 16
         saved = ctx.saved_tensors
+        cam_out = None
+        if ctx.camera_grad:
+            cam_out = _cam_grads(ctx.needs_input_grad[13:16], ctx.cams, saved[0].device)
         d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad,
-                                                                           grad_depth, grad_alpha)
+                                                                           grad_depth, grad_alpha, cam_out)
         has_sh, has_cov = saved[10] is not None, saved[11] is not None
+        d_cam = (None, None, None) if cam_out is None else tuple(_cam_grad_as(g, t) for g, t in zip(cam_out, ctx.cams))
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha,
-        #  antialiasing)
+        #  antialiasing, camera_grad, viewmatrix, projmatrix, campos)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None, None, None)
+                d_cov, None, None, None, None, None) + d_cam
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False, antialiasing=False):
+                        return_depth_alpha=False, antialiasing=False, camera_grad=False):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
     and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
-    antialiasing=True (or a truthy raster_settings.antialiasing): the opacity-compensated 2D filter, include/gpsgs.h GSR_FLAG_ANTIALIAS."""
+    antialiasing=True (or a truthy raster_settings.antialiasing): the opacity-compensated 2D filter, include/gpsgs.h GSR_FLAG_ANTIALIAS.
+    camera_grad=True: raster_settings.viewmatrix, projmatrix and campos become differentiable inputs -- each that requires a gradient gets
+    dL/d(itself) in its own shape, dtype and device (include/gpsgs.h gsr_backward_camera; without the keyword they are constants, as upstream)."""
+    if camera_grad:
+        rs = raster_settings
+        cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+        aa = bool(antialiasing) or bool(getattr(rs, "antialiasing", False))
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, bool(return_depth_alpha), aa, True, *cams)
     if antialiasing or getattr(raster_settings, "antialiasing", False):
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                          raster_settings, grad_arena, bool(return_depth_alpha), True)
@@ -818,14 +864,14 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None, return_depth_alpha=False, antialiasing=False):
+                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         antialiasing = antialiasing or getattr(self.raster_settings, "antialiasing", False)
-        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing:
+        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing and not camera_grad:
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -833,9 +879,10 @@ class GaussianRasterizer(nn.Module):
         # shs [P, M, 3] are evaluated up to raster_settings.sh_degree towards raster_settings.campos (upstream computeColorFromSH); cov3D_precomp
         # [P, 6] replaces scale + rotation.  The reference passes neither (gaussian_renderer/__init__.py:54-62) but constructs the settings
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
-        # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing: the Python host path (not the compiled one)
+        # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing and camera_grad: the Python host path (not
+        # the compiled one)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing)
+                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad)
 
 
     def markVisible(self, positions):

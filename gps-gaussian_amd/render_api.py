@@ -101,10 +101,13 @@ class _RenderBatch(torch.autograd.Function):
     Numerically it IS the per-sample path: the same kernels on the same rows (tests/test_gpu_pack.py compares the bits)."""
 
     @staticmethod
-    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False):
+    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False, camera_grad=False,
+                view_all=None, proj_all=None, campos_all=None):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
         # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
-        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS
+        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS;
+        # camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds them) get
+        # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True))
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
@@ -141,6 +144,8 @@ class _RenderBatch(torch.autograd.Function):
             h.saved = None
         ctx.save_for_backward(xyz, rgb, rot, scale, opacity)
         ctx.views, ctx.side = views, side
+        ctx.camera_grad = bool(camera_grad)
+        ctx.cams = (view_all, proj_all, campos_all) if camera_grad else None
         ctx.color_grad = bool(ctx.needs_input_grad[1])  # False in stage 2: pack_views marks rgb non-differentiable when no image needs a gradient
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
         ctx.set_materialize_grads(False)
@@ -151,7 +156,7 @@ class _RenderBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, gdepth=None, galpha=None):
         if gout is None and gdepth is None and galpha is None:
-            return (None,) * 10
+            return (None,) * 14
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
@@ -162,6 +167,11 @@ class _RenderBatch(torch.autograd.Function):
         # rows, rows behind offsets[-1] (the unused tail of the packed capacity) are never read by the pack backward
         d_xyz, d_rgb, d_rot, d_scale, d_op = (torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes)
         d_m2 = torch.empty(ctx.shapes[0], dtype=torch.float32, device=dev)
+        # camera gradients: [B, 16], [B, 16], [B, 3] on the device, sample i's rows written by its own backward
+        cam_all = None
+        if ctx.camera_grad:
+            cam_all = tuple(torch.empty((len(views), n), dtype=torch.float32, device=dev) if w and t is not None else None
+                            for w, t, n in zip(ctx.needs_input_grad[11:14], ctx.cams, (16, 16, 3)))
         cur = torch.cuda.current_stream(dev)
         for i, h in enumerate(views):
             if side[i] is not cur:
@@ -169,16 +179,22 @@ class _RenderBatch(torch.autograd.Function):
             ins = h.own if h.own is not None else (xyz, rgb, opacity.reshape(-1), scale, rot)
             with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.ws_box in there)
                 _RZ._backward_impl(h, tuple(ins) + tuple(h.tail), g[i] if g is not None else None, (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2),
-                                   ctx.color_grad, gd[i] if gd is not None else None, ga[i] if ga is not None else None)
+                                   ctx.color_grad, gd[i] if gd is not None else None, ga[i] if ga is not None else None,
+                                   None if cam_all is None else tuple(c[i] if c is not None else None for c in cam_all))
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
-        return d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None
+        d_cam = (None, None, None)
+        if cam_all is not None:
+            d_cam = tuple(_RZ._cam_grad_as(c, t) for c, t in zip(cam_all, ctx.cams))
+        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam
 
 
-def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False):
+def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
     """Render one novel view.  Same arguments and return value as the reference's render(): returns image [3,H,W].
-    (grad_arena: internal, see pts2render.)  antialiasing=True: the opacity-compensated 2D filter (rasterizer.rasterize_gaussians)."""
+    (grad_arena: internal, see pts2render.)  antialiasing=True: the opacity-compensated 2D filter (rasterizer.rasterize_gaussians).
+    camera_grad=True: data['novel_view']['world_view_transform'], ['full_proj_transform'] and ['camera_center'] receive the gradient of
+    sample idx's camera (through their [idx] slices) when they require one."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     screenspace_points = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
@@ -194,22 +210,24 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     rendered_image, _ = rasterizer(means3D=pts_xyz, means2D=screenspace_points, shs=None, colors_precomp=pts_rgb,
                                    opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena,
-                                   antialiasing=antialiasing)
+                                   antialiasing=antialiasing, camera_grad=camera_grad)
     return rendered_image
 
 
-def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False):
+def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
     The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE.
-    antialiasing=True: as render()'s; the maps then see the filtered opacities too."""
+    antialiasing=True: as render()'s; the maps then see the filtered opacities too.  camera_grad=True: as render()'s, the maps' gradients
+    included."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
     img, _, depth, alpha = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
-                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing)
+                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
+                                      camera_grad=camera_grad)
     return {'img': img, 'depth': depth, 'alpha': alpha}
 
 
@@ -230,10 +248,12 @@ def _to_device_once(t, dev):
     return t
 
 
-def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False):
+def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
     antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
+    camera_grad=True (opt-in): each sample's camera gradient reaches data['novel_view']['world_view_transform'], ['full_proj_transform'] and
+    ['camera_center'] ([B,4,4], [B,4,4], [B,3]) where they require one -- with the bits of B render_ex / render calls.
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -252,7 +272,15 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False):
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        if with_depth_alpha:
+        if camera_grad:
+            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center'])
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
+                                     True, *cams)
+            if with_depth_alpha:
+                nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = out
+            else:
+                nv['img_pred'] = out
+        elif with_depth_alpha:
             nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, True,
                                                                                     bool(antialiasing))
         elif antialiasing:
@@ -260,10 +288,10 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False):
         else:
             nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing)
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False):
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False):
     """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
@@ -295,11 +323,11 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
             with torch.cuda.stream(side[i]):
                 if with_depth_alpha:
                     r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
-                                  antialiasing=antialiasing)
+                                  antialiasing=antialiasing, camera_grad=camera_grad)
                     out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha')))
                 else:
                     out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
-                                       grad_arena=ga, antialiasing=antialiasing).unsqueeze(0),))
+                                       grad_arena=ga, antialiasing=antialiasing, camera_grad=camera_grad).unsqueeze(0),))
     for i in range(bs):
         if side[i] is not cur:
             cur.wait_stream(side[i])

@@ -248,6 +248,31 @@ int gsr_backward_ex(int P, int width, int height, const float *means3D, const fl
                     float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace,
                     size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext);
 
+/* Camera gradients (opt-in).  gsr_backward_camera is gsr_backward_ex with the same arguments -- it writes every per-Gaussian gradient with the
+ * same bits and honours the same flags and GsrViewExt fields -- and also WRITES (does not accumulate) the gradient of the loss with respect to
+ * the camera, each a DEVICE array that may be NULL (not wanted):
+ *   dL_dviewmatrix[16], dL_dprojmatrix[16]: flat column-major as viewmatrix / projmatrix are read, element (r, c) at index 4 c + r (the
+ *     transposed [4,4] tensor the reference passes, read as tensor.reshape(16)).  Per visible Gaussian, m~ = (x, y, z, 1):
+ *       dL/dv[4c+r] += dt[r] m~[c] (r < 3), dt = dL/d(view-space mean), depth-map term included; + (J^T dL/dT)[r][c] (r, c < 3), T = J W and
+ *       J the clamped EWA Jacobian the forward used.  Row 3 (indices 3, 7, 11, 15) is never read and is exactly 0.
+ *       dL/dp[4c+r] = dh[r] m~[c], h = projmatrix m~, dh = (g0 w, g1 w, 0, -(g0 h0 + g1 h1) w^2), w = 1 / (h3 + 1e-7), g = dL/dmean2D (NDC).
+ *       Row 2 (indices 2, 6, 10, 14) is exactly 0.
+ *   dL_dcampos[3]: minus the SH view-direction term of dL_dmeans3D; exactly 0 without shs.
+ * The conventions are the backward's own (straight-through min(0.99) clamp, 1/(det^2 + 1e-7) conic gradient, clamped view-space x/y constant); all
+ * discrete decisions are constants.  An overflowed forward gives zeros.  tanfov, scale_modifier and bg get no gradient.
+ * Deterministic: each preprocess-backward workgroup sums its Gaussians' shares in a fixed order into scratch, a second launch sums those in a fixed
+ * order -- no atomics, the same bits on every run, stream and view in flight.  scratch: DEVICE, at least gsr_camera_grad_scratch_bytes(P) bytes
+ * (one per view in flight; GPSGS_E_WORKSPACE otherwise; may be NULL when P = 0 or no output is wanted).  With all three outputs NULL the call is
+ * gsr_backward_ex.  No host synchronisation. */
+size_t gsr_camera_grad_scratch_bytes(int P);
+int gsr_backward_camera(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                        const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                        const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                        const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                        float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace,
+                        size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                        float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes);
+
 /* Visibility mask (upstream `_C.mark_visible`, reached through GaussianRasterizer.markVisible(positions) of the module the reference imports at
  * gaussian_renderer/__init__.py:14; the reference itself never calls it): present[i] = 1 iff point i passes the near-plane test of the forward
  * (view-space z > 0.2), else 0.  means3D[P,3], viewmatrix[16] / projmatrix[16] as for gsr_forward (projmatrix is accepted for signature parity and
