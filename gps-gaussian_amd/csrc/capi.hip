@@ -173,11 +173,35 @@ extern "C" size_t gsr_workspace_bytes_forward_only(int P, int width, int height,
     return gsr_layout(P, width, height, instance_capacity).total_fwd;
 }
 
-extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
-                              const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
-                              const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
-                              void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
-                              void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext) {
+extern "C" size_t gsr_workspace_bytes_features(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int channels, int forward_only) {
+    if (channels < 1 || channels > GSR_MAX_FEATURES) return 0;
+    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
+    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
+    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    return forward_only ? L.total_fwd : L.total_extra + gsr_feature_tail_bytes(instance_capacity, channels);
+}
+
+namespace {
+// F-channel feature maps: the channel count of a GsrFeatures (0 = none), or -1 for an invalid one (range, NULL features for P > 0, misaligned pointers)
+int feature_channels(const GsrFeatures *feat, bool backward, int P) {
+    if (!feat || feat->channels == 0) return 0;
+    if (feat->channels < 0 || feat->channels > GSR_MAX_FEATURES || (P > 0 && !feat->features)) return -1;  // (a view without Gaussians has no rows)
+    const uintptr_t a = reinterpret_cast<uintptr_t>(feat->features) | reinterpret_cast<uintptr_t>(feat->out_features) |
+                        (backward ? reinterpret_cast<uintptr_t>(feat->dL_dfeatures) : 0u);
+    if (a & 3u) return -1;
+    if (!backward && !feat->out_features) return -1;
+    return feat->channels;
+}
+
+// gsr_forward_ex, and with feat (gsr_forward_features) the feature maps too
+int forward_impl(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                 const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                 const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                 void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                 void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
+    const int F = feature_channels(feat, false, P);
+    if (F < 0) return GPSGS_E_INVALID;
+    if (F > 0) flags &= ~GSR_FLAG_COMPOSITE_TILES;  // feature maps: the VALU kernels only (as the depth / alpha maps)
     const uint32_t *row_range = ext ? ext->row_range : nullptr;
     const uint32_t order_hint = ext ? ext->order_hint : 0u;
     // opt-in depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
@@ -237,6 +261,7 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
         if (hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (out_depth && hipMemsetAsync(out_depth, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (out_alpha && hipMemsetAsync(out_alpha, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (F > 0 && hipMemsetAsync(feat->out_features, 0, sizeof(float) * (size_t)F * width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (hipMemsetAsync(bin_offset, 0, (size_t)(L.NB + 1) * 4, s) != hipSuccess) return GPSGS_E_LAUNCH;
         return check(s, flags);
     }
@@ -340,11 +365,33 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
         if (flags & GSR_FLAG_COMPOSITE_TILES)
             gsr_launch_composite_fwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, training,
                                            (flags & GSR_FLAG_WAVE_PRIORITY) != 0, fused_sort ? keys : nullptr, s);
+        else if (F > 0)
+            gsr_launch_composite_fwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd,
+                                          out_depth, out_alpha, feat->features, F, row_range, feat->out_features, s);
         else
             gsr_launch_composite_fwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, out_depth,
                                      out_alpha, s);
     }
     return check(s, flags);
+}
+}  // namespace
+
+extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                              const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                              const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                              void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                              void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext) {
+    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, nullptr);
+}
+
+extern "C" int gsr_forward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                    const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                    const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                                    void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                                    void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
+    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, feat);
 }
 
 extern "C" int gsr_forward_notify(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -371,7 +418,7 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
                   const float *rotations, float scale_modifier, float tanfovx, float tanfovy, const float *viewmatrix, const float *projmatrix,
                   const float *bg, const int *radii, const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
                   float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes, int64_t instance_capacity,
-                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam) {
+                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam, const GsrFeatures *feat = nullptr) {
     (void)colors;  // already folded into the splat records of the workspace (so are the opacities -- read again only with antialiasing)
     const bool antialias = (flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
@@ -379,6 +426,13 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     const bool extras = dL_ddepth || dL_dalpha;
     if ((reinterpret_cast<uintptr_t>(dL_ddepth) | reinterpret_cast<uintptr_t>(dL_dalpha)) & 3u) return GPSGS_E_INVALID;
     if (extras) flags &= ~GSR_FLAG_COMPOSITE_TILES;
+    // feature maps (either gradient pointer may be NULL): the VALU family's feature kernels, cap x F more floats in the workspace's feature tail
+    const int F = feature_channels(feat, true, P);
+    if (F < 0) return GPSGS_E_INVALID;
+    if (F > 0) flags &= ~GSR_FLAG_COMPOSITE_TILES;
+    const float *dL_dfeat = F > 0 ? feat->dL_dfeaturemap : nullptr;
+    float *dL_dfeatures = F > 0 ? feat->dL_dfeatures : nullptr;
+    const bool feat_sums = dL_dfeat && dL_dfeatures;  // the per-slot feature sums (part b) are formed
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
     if (P == 0) {
         if (cam) {  // nothing rendered: the camera gradients are zeros
@@ -401,7 +455,7 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     const uint32_t bin_cap = ext ? ext->bin_capacity : 0u;  // must be what the forward was given
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
-    if (workspace_bytes < (extras ? L.total_extra : L.total)) return GPSGS_E_WORKSPACE;
+    if (workspace_bytes < (feat_sums ? L.total_extra + gsr_feature_tail_bytes(instance_capacity, F) : extras ? L.total_extra : L.total)) return GPSGS_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const GsrHeader *hdr = reinterpret_cast<const GsrHeader *>(at(workspace, L.header));
     const GsrBins bins = {reinterpret_cast<const uint32_t *>(at(workspace, L.bin_offset)), reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count)),
@@ -417,6 +471,8 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     float *inst_dop = reinterpret_cast<float *>(at(workspace, L.inst_dop));
     GsrGradAcc *inst_grad = reinterpret_cast<GsrGradAcc *>(at(workspace, L.inst_grad));
     float *inst_ddepth = extras ? reinterpret_cast<float *>(at(workspace, L.inst_ddepth)) : nullptr;
+    float *inst_dfeat = feat_sums ? reinterpret_cast<float *>(at(workspace, L.total_extra)) : nullptr;
+    const uint32_t *row_range = ext ? ext->row_range : nullptr;
 
     // goff / gscan_part / cleared inst_valid were produced by the matching gsr_forward (training workspace)
     int rc;
@@ -428,6 +484,9 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
         if (flags & GSR_FLAG_COMPOSITE_TILES)
             gsr_launch_composite_bwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
                                            (flags & GSR_FLAG_NO_COLOR_GRAD) == 0, (flags & GSR_FLAG_WAVE_PRIORITY) != 0, s);
+        else if (dL_dfeat)  // (a NULL feature-map gradient runs the plain kernel: the per-Gaussian gradients keep their bits)
+            gsr_launch_composite_bwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop,
+                                          inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, feat->features, F, row_range, dL_dfeat, inst_dfeat, s);
         else
             gsr_launch_composite_bwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
                                      dL_ddepth, dL_dalpha, inst_ddepth, s);
@@ -452,6 +511,12 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
         trace("preprocess_bwd", P, width, height, (long long)instance_capacity, flags);
         StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
         gsr_launch_preprocess_bwd(b, splats, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr, s, cam);
+    }
+    if (dL_dfeatures) {
+        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
+        trace("feature_grad_gather", P, width, height, (long long)instance_capacity, flags);
+        StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
+        gsr_launch_feature_grad_gather(P, F, row_range, radii, goff, gscan_part, inst_valid, inst_dfeat, hdr, dL_dfeatures, s);
     }
     return check(s, flags);
 }
@@ -488,6 +553,24 @@ extern "C" int gsr_backward_camera(int P, int width, int height, const float *me
     return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                          radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
                          instance_capacity, flags, stream, ext, want ? &cam : nullptr);
+}
+
+extern "C" int gsr_backward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                     const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                     const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                                     const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                                     float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                                     int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                                     float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                                     const GsrFeatures *feat) {
+    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
+        return GPSGS_E_INVALID;
+    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
+    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
+    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
+                         instance_capacity, flags, stream, ext, want ? &cam : nullptr, feat);
 }
 
 extern "C" int gsr_backward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,

@@ -39,6 +39,8 @@
 //                  algorithmic): scattered READS are what costs on this memory system, scattered writes cost the sectors they touch.
 //   --- depth / alpha tail (only in a workspace sized with gsr_workspace_bytes_depth_alpha; every offset above is unchanged) ---
 //   inst_ddepth[cap] the tenth per-instance sum, dL/dz (the depth map's gradient reaching the view-space depth), at the same slot as inst_dop
+//   --- feature tail (only in a workspace sized with gsr_workspace_bytes_features; every offset above is unchanged) ---
+//   inst_dfeat[cap][F] the F per-instance feature sums sum_p w dL/dfeat[c, p], slot-major, set for the slots whose inst_valid flag is set
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -520,6 +522,23 @@ void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *spla
                               const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop, GsrGradAcc *inst_grad, const GsrHeader *hdr,
                               const float *dL_ddepth, const float *dL_dalpha /* [H, W], NULL = zero */,
                               float *inst_ddepth /* non-NULL: the EXTRA instantiation, which writes dL/dz per record slot */, hipStream_t s);
+// F-channel feature maps (GsrFeatures; the VALU family only).  Forward: the image, final_T, n_contrib (and the depth / alpha maps) exactly as
+// gsr_launch_composite_fwd writes them, plus out_feat [F, H, W]; features [rows, F] follow row_range.  Backward: the geometry kernel (the features'
+// share of cd, dL_dfeat [F, H, W] non-NULL) in place of gsr_launch_composite_bwd, then, with inst_dfeat (cap x F floats) non-NULL, the per-slot
+// feature sums; gsr_launch_feature_grad_gather turns those into dL_dfeatures [rows, F] (inst_dfeat NULL: zeros).
+void gsr_launch_composite_fwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                   const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
+                                   const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const float *features, int F,
+                                   const uint32_t *row_range, float *out_feat, hipStream_t s);
+void gsr_launch_composite_bwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                   const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
+                                   const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
+                                   GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
+                                   const float *features, int F, const uint32_t *row_range, const float *dL_dfeat, float *inst_dfeat, hipStream_t s);
+void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart,
+                                    const uint8_t *inst_valid, const float *inst_dfeat, const GsrHeader *hdr, float *dL_dfeatures, hipStream_t s);
+// the feature tail of a training workspace: F floats per instance slot, behind the depth / alpha tail (total_extra)
+static inline size_t gsr_feature_tail_bytes(int64_t cap, int F) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * (size_t)F * 4); }
 // development knob: GPSGS_DEBUG_LDS_PAD=<bytes> of unused dynamic LDS per compositing workgroup (caps the waves resident per CU, to
 // measure how the kernels scale with occupancy); 0 / unset in normal use
 #include <stdlib.h>

@@ -306,6 +306,470 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
     }
 }
 
+// ---- F-channel feature maps (GsrFeatures): feat[c, p] = sum_i f[i, c] alpha_i T_i, background 0 -------------------------------------------------
+// The same blend as k_composite_fwd, with F more channels whose values come from the caller's [rows, F] array instead of the splat record.  The
+// channels are split into chunks of NF over gridDim.y (NF accumulators per lane keep the kernel near the plain one's register budget); every
+// chunk's wave walks the same bin with the same arithmetic, so w = alpha T has the same bits in every chunk and in a plain run, and chunk 0 alone
+// writes the image, final_T, n_contrib (and the depth / alpha maps) and clears the record flags.  Each lane stages its splat's NF features
+// (dword loads: a row is 4-byte aligned only) into LDS beside sA / sB / sC; the blend loop reads them as broadcasts, acc += f w being the
+// same v_fma_f32 as a colour channel's.
+constexpr int GSR_FEAT_PAD = 4;  // LDS row stride NF + 4 floats: a lane's 16-byte stores of its row spread over the banks
+template <bool EXTRA, int NF>
+__global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H, int bx, const GsrSplat *__restrict__ splats,
+                                                            GsrBins bins, const uint32_t *__restrict__ wg_order,
+                                                            const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
+                                                            float *__restrict__ out_color, float *__restrict__ final_T,
+                                                            uint32_t *__restrict__ n_contrib, const GsrHeader *__restrict__ hdr, uint8_t *__restrict__ inst_valid,
+                                                            float *__restrict__ out_depth, float *__restrict__ out_alpha,
+                                                            const float *__restrict__ features, int F, const uint32_t *__restrict__ row_range,
+                                                            float *__restrict__ out_feat) {
+    constexpr int FS = NF + GSR_FEAT_PAD;
+    __shared__ float4 sA[WAVES][WAVE];
+    __shared__ float4 sB[WAVES][WAVE];
+    __shared__ float sC[WAVES][WAVE];
+    __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
+    __shared__ __attribute__((aligned(16))) float sF[WAVES][WAVE * FS];
+    const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
+    const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
+    const bool chunk0 = blockIdx.y == 0;
+    const int c0 = (int)blockIdx.y * NF, nc = min(NF, F - c0);  // this chunk's channels [c0, c0 + nc)
+    const size_t npix = (size_t)W * H;
+    if (hdr->overflow) {
+        if (chunk0) {
+            fwd_write_blank(g, W, H, out_color, final_T, n_contrib);
+            if (EXTRA && g.inside) {
+                const size_t q = (size_t)g.py * W + g.px;
+                if (out_depth) out_depth[q] = 0.f;
+                if (out_alpha) out_alpha[q] = 0.f;
+            }
+        }
+        if (g.inside) {
+            const size_t q = (size_t)g.py * W + g.px;
+            for (int k = 0; k < nc; k++) out_feat[(size_t)(c0 + k) * npix + q] = 0.f;
+        }
+        return;
+    }
+    if (chunk0) clear_record_flags(inst_valid, hdr, (int)threadIdx.x, 64 * WAVES);
+    const uint32_t row0 = row_range ? row_range[0] : 0u;  // splat id i is row row0 + i of the caller's arrays (gsr_view_rows)
+    const float *__restrict__ fbase = features + c0;
+    const float pxf = (float)g.px, pyf = (float)g.py;
+    float4 *wA = sA[g.wid], *wB = sB[g.wid];
+    float *wC = sC[g.wid], *wD = sD[g.wid], *wF = sF[g.wid];
+
+    float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, CD = 0.f, CA = 0.f;
+    float acc[NF];
+#pragma unroll
+    for (int k = 0; k < NF; k++) acc[k] = 0.f;
+    uint32_t last = 0, last_rnd = 0;
+    typedef unsigned long long lanemask_t;
+    lanemask_t active = __ballot(g.inside);
+    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r0), r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r1);
+
+    float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
+    float nC = 0.f, nD = 0.f;
+    float nF[NF];
+    auto fetch = [&](uint32_t k) {  // list entry k: its 48-byte record and its NF features (0 past the last channel)
+        const uint32_t id = point_list[k];
+        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
+        nA = s[0]; nB = s[1]; nC = s[2].x;
+        if (EXTRA) nD = s[2].y;
+        const float *f = fbase + (size_t)(row0 + id) * (size_t)F;
+#pragma unroll
+        for (int c = 0; c < NF; c++) nF[c] = c < nc ? f[c] : 0.f;
+    };
+#pragma unroll
+    for (int c = 0; c < NF; c++) nF[c] = 0.f;
+    if (r0 + g.lane < r1) fetch(r0 + g.lane);
+    for (uint32_t base = r0; base < r1; base += WAVE) {
+        if (active == 0ull) break;
+        wave_sync_lds();
+        wA[g.lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
+        wB[g.lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
+        wC[g.lane] = nC;
+        if (EXTRA) wD[g.lane] = nD;
+#pragma unroll
+        for (int c = 0; c < NF; c += 4) *reinterpret_cast<float4 *>(wF + g.lane * FS + c) = make_float4(nF[c], nF[c + 1], nF[c + 2], nF[c + 3]);
+        wave_sync_lds();
+        const uint32_t nk = base + WAVE + g.lane;
+        nB.y = 0.f;
+        if (nk < r1) fetch(nk);
+        const int cnt = (int)min((uint32_t)WAVE, r1 - base);
+#pragma unroll
+        for (int j0 = 0; j0 < WAVE; j0 += 8) {
+            if (j0 < cnt && active != 0ull) {
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int j = j0 + u;
+                    const float4 a = wA[j];
+                    const float4 b = wB[j];
+                    const float c2 = wC[j];
+                    const float dx = a.x - pxf, dy = a.y - pyf;
+                    const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
+                    const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power));
+                    const lanemask_t valid = active & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
+                    const float test_T = __builtin_fmaf(-alpha, T, T);
+                    const lanemask_t sat = __ballot(test_T < 0.0001f);
+                    active &= ~(valid & sat);
+                    const bool use = __builtin_amdgcn_inverse_ballot_w64(valid & ~sat);
+                    const float w = use ? alpha * T : 0.f;
+                    C0 += b.z * w;
+                    C1 += b.w * w;
+                    C2 += c2 * w;
+                    if (EXTRA) {
+                        CD += wD[j] * w;
+                        CA += w;
+                    }
+#pragma unroll
+                    for (int c = 0; c < NF; c += 4) {
+                        const float4 f = *reinterpret_cast<const float4 *>(wF + j * FS + c);
+                        acc[c] += f.x * w;  // fma(f, w, acc): a colour channel's contraction
+                        acc[c + 1] += f.y * w;
+                        acc[c + 2] += f.z * w;
+                        acc[c + 3] += f.w * w;
+                    }
+                    T = use ? test_T : T;
+                    last_rnd = use ? (uint32_t)(j + 1) : last_rnd;
+                }
+            }
+        }
+        last = last_rnd ? (base - r0) + last_rnd : last;
+        last_rnd = 0;
+    }
+    if (g.inside) {
+        const size_t q = (size_t)g.py * W + g.px;
+        if (chunk0) {
+            final_T[q] = T;
+            n_contrib[q] = last;
+            const float bgs = hdr->num_points != 0u ? 1.f : 0.f;
+            out_color[q] = C0 + T * (bgs * bg[0]);
+            out_color[npix + q] = C1 + T * (bgs * bg[1]);
+            out_color[2 * npix + q] = C2 + T * (bgs * bg[2]);
+            if (EXTRA) {
+                if (out_depth) out_depth[q] = CD;
+                if (out_alpha) out_alpha[q] = CA;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NF; c++)
+            if (c < nc) out_feat[(size_t)(c0 + c) * npix + q] = acc[c];
+    }
+}
+
+// Feature maps, backward (a): the geometry.  k_composite_bwd with the features' share of cd: cd += sum_c f[i, c] dL/dfeat[c, p] over ALL F
+// channels (NG >= F of them held per lane in registers, the staged splats' rows in LDS), folded in before dL/dalpha -- exactly as F more colour
+// channels with background 0 would enter the scalar recurrence.  The record, its nine-term reduce-scatter and inst_ddepth stay as they are.
+// The staged splats' feature rows are loaded at the top of each round (the register prefetch would cost NG more VGPRs).
+template <bool EXTRA, int NG>
+__global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H, int bx, const GsrSplat *__restrict__ splats,
+                                                            GsrBins bins, const uint32_t *__restrict__ wg_order,
+                                                            const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
+                                                            const float *__restrict__ dL_dpix, const float *__restrict__ final_T,
+                                                            const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ goff,
+                                                            const uint32_t *__restrict__ gpart, uint8_t *__restrict__ inst_valid, float *__restrict__ inst_dop,
+                                                            GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr,
+                                                            const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, float *__restrict__ inst_ddepth,
+                                                            const float *__restrict__ features, int F, const uint32_t *__restrict__ row_range,
+                                                            const float *__restrict__ dL_dfeat) {
+    constexpr int REC = EXTRA ? 4 : 3;
+    constexpr int FS = NG + GSR_FEAT_PAD;
+    __shared__ float4 sA[WAVES][WAVE];
+    __shared__ float4 sB[WAVES][WAVE];
+    __shared__ float sC[WAVES][WAVE];
+    __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
+    __shared__ float4 sAcc[WAVES][WAVE * REC];
+    __shared__ __attribute__((aligned(16))) float sF[WAVES][WAVE * FS];
+    if (hdr->overflow) return;
+    const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
+    if (list_pos >= hdr->num_busy_wgs) return;
+    const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
+    if (g.r1 <= g.r0) return;
+    const int lane = g.lane;
+    const float pxf = (float)g.px, pyf = (float)g.py;
+    const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
+    float4 *wA = sA[g.wid], *wB = sB[g.wid], *wAcc = sAcc[g.wid];
+    float *wC = sC[g.wid], *wD = sD[g.wid], *wAccF = reinterpret_cast<float *>(sAcc[g.wid]), *wF = sF[g.wid];
+    const int slot = acc_slot(lane);
+    const uint32_t row0 = row_range ? row_range[0] : 0u;
+
+    const float T_final = g.inside ? final_T[q] : 0.f;
+    const uint32_t last = g.inside ? n_contrib[q] : 0u;
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+    if (g.inside) {
+        d0 = dL_dpix[q];
+        d1 = dL_dpix[npix + q];
+        d2 = dL_dpix[2 * npix + q];
+    }
+    float dd = 0.f, da = 0.f;
+    if (EXTRA && g.inside) {
+        if (dL_ddepth) dd = dL_ddepth[q];
+        if (dL_dalpha) da = dL_dalpha[q];
+    }
+    float gf[NG];  // dL/dfeat[c] of this pixel (0 past the last channel and outside the image)
+#pragma unroll
+    for (int c = 0; c < NG; c++) gf[c] = (c < F && g.inside) ? dL_dfeat[(size_t)c * npix + q] : 0.f;
+    const float bg_dot = bg[0] * d0 + bg[1] * d1 + bg[2] * d2;
+    const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
+
+    uint32_t m = last;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    const int64_t max_last = (int64_t)__builtin_amdgcn_readfirstlane((int)m);
+    if (max_last == 0) return;
+
+    float T = T_final, A = 0.f;
+    const float nTb = -T_final * bg_dot;
+
+    float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
+    float nC = 0.f, nD = 0.f;
+    uint32_t nRec = 0, nId = 0;
+    bool nHas = false;
+    const int bin_x = g.bin % bx, bin_y = g.bin / bx;
+    auto stage = [&](uint32_t list_pos) {
+        const uint32_t id = point_list[list_pos];
+        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
+        nA = s[0]; nB = s[1];
+        const float4 c = s[2];
+        nC = c.x;
+        if (EXTRA) nD = c.y;
+        const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
+        const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
+        nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+        nId = id;
+        nHas = true;
+    };
+    if ((int64_t)lane <= max_last - 1) stage(g.r0 + (uint32_t)(max_last - 1 - lane));
+    for (int64_t top = max_last - 1; top >= 0; top -= WAVE) {
+        const int cnt = (int)min((int64_t)WAVE, top + 1);
+        wave_sync_lds();
+        wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
+        wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
+        wC[lane] = nC;
+        if (EXTRA) wD[lane] = nD;
+        {  // this round's feature rows (a slot without a splat: zeros)
+            const float *f = features + (size_t)(row0 + nId) * (size_t)F;
+#pragma unroll
+            for (int c = 0; c < NG; c += 4) {
+                float4 v;
+                v.x = (nHas && c < F) ? f[c] : 0.f;
+                v.y = (nHas && c + 1 < F) ? f[c + 1] : 0.f;
+                v.z = (nHas && c + 2 < F) ? f[c + 2] : 0.f;
+                v.w = (nHas && c + 3 < F) ? f[c + 3] : 0.f;
+                *reinterpret_cast<float4 *>(wF + lane * FS + c) = v;
+            }
+        }
+        const uint32_t curRec = nRec;
+        nHas = false;
+        wave_sync_lds();
+        const int64_t ntop = top - WAVE;
+        if (ntop - lane >= 0) stage(g.r0 + (uint32_t)(ntop - lane));
+        unsigned long long touched = 0ull;
+        for (int j = 0; j < cnt; j++) {
+            const uint32_t pos = (uint32_t)(top - j);
+            const float4 a = wA[j];
+            const float4 b = wB[j];
+            const float dx = a.x - pxf, dy = a.y - pyf;
+            const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
+            const float G = __builtin_amdgcn_exp2f(power);
+            const float alpha = fminf(0.99f, b.y * G);
+            const unsigned long long valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
+            if (valid_m == 0ull) continue;
+            const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
+            touched |= 1ull << j;
+            const float Ge = valid ? G : 0.f;
+            const float ae = valid ? alpha : 0.f;
+            const float om = 1.f - ae;
+            const float rcp = __builtin_amdgcn_rcpf(om);
+            T = T * rcp;
+            float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
+            if (EXTRA) {
+#pragma clang fp contract(off)
+                const float zd = wD[j] * dd;
+                cd = cd + (zd + da);
+            }
+            float fd = 0.f;  // the features' share: sum_c f[c] dL/dfeat[c]
+#pragma unroll
+            for (int c = 0; c < NG; c += 4) {
+                const float4 f = *reinterpret_cast<const float4 *>(wF + j * FS + c);
+                fd += f.x * gf[c];
+                fd += f.y * gf[c + 1];
+                fd += f.z * gf[c + 2];
+                fd += f.w * gf[c + 3];
+            }
+            cd = cd + fd;
+            const float w = ae * T;
+            const float dL_dalpha = (cd - A) * T + nTb * rcp;
+            A = ae * cd + om * A;
+            const float g_r = w * d0;
+            const float g_g = w * d1;
+            const float g_b = w * d2;
+            const float m_0 = (b.y * dL_dalpha) * Ge;
+            const float m_x = m_0 * dx;
+            const float m_y = m_0 * dy;
+            const float m_xx = m_x * dx;
+            const float m_xy = m_x * dy;
+            const float m_yy = m_y * dy;
+            const float red[9] = {g_r, g_g, g_b, m_x, m_y, m_xx, m_xy, m_yy, m_0};
+            const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
+            if (slot >= 0) wAccF[4 * REC * j + slot] = out;
+            if (EXTRA) {
+                const float rz = wave_row_sum(w * dd);
+                if ((lane & 15) == 7) wAccF[4 * REC * j + 12 + (lane >> 4)] = rz;
+            }
+        }
+        wave_sync_lds();
+        if ((touched >> lane) & 1ull) {
+            const float4 v0 = wAcc[REC * lane], v1 = wAcc[REC * lane + 1], rs = wAcc[REC * lane + 2];
+            const float4 sa = wA[lane], sb = wB[lane];
+            const float Sx = v0.w, Sy = v1.x, Sxx = v1.y, Sxy = v1.z, Syy = v1.w;
+            const float S0 = (rs.x + rs.y) + (rs.z + rs.w);
+            const float kA = 2.f / GSR_LOG2E, kB = 1.f / GSR_LOG2E;
+            const float g_mx = ddelx_dx * (kA * sa.z * Sx + kB * sa.w * Sy);
+            const float g_my = ddely_dy * (kA * sb.x * Sy + kB * sa.w * Sx);
+            float4 *dst = reinterpret_cast<float4 *>(inst_grad + curRec);
+            dst[0] = make_float4(v0.x, v0.y, v0.z, g_mx);
+            dst[1] = make_float4(g_my, -0.5f * Sxx, -0.5f * Sxy, -0.5f * Syy);
+            inst_dop[curRec] = S0 * __builtin_amdgcn_rcpf(sb.y);
+            if (EXTRA) {
+                const float4 rz = wAcc[REC * lane + 3];
+                inst_ddepth[curRec] = (rz.x + rz.y) + (rz.z + rz.w);
+            }
+            inst_valid[curRec] = 1;
+        }
+    }
+}
+
+// Feature maps, backward (b): dL/df[i, c] = sum_p w dL/dfeat[c, p] per (bin, splat) instance.  w = alpha T needs only the T recurrence, which
+// does not depend on colour, so this walk is chunked over gridDim.y like the forward and repeats the geometry walk's decisions (same arithmetic:
+// its `touched` set is the set of instances whose inst_valid flag k_composite_bwd(_feat) sets).  Per round every lane parks its 64 weights in LDS
+// (w[p][j], row stride 65: conflict-free both ways); then lane j forms its staged splat's NF sums over the 64 pixels in pixel order from the
+// broadcast gradients of the chunk -- a fixed order, no atomics -- and writes them to inst_dfeat[slot * F + c].
+template <int NF>
+__global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_featgrad(int W, int H, int bx, const GsrSplat *__restrict__ splats,
+                                                                GsrBins bins, const uint32_t *__restrict__ wg_order,
+                                                                const uint32_t *__restrict__ point_list, const float *__restrict__ final_T,
+                                                                const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ goff,
+                                                                const uint32_t *__restrict__ gpart, const GsrHeader *__restrict__ hdr,
+                                                                int F, const float *__restrict__ dL_dfeat, float *__restrict__ inst_dfeat) {
+    constexpr int WS = WAVE + 1;
+    __shared__ float4 sA[WAVES][WAVE];
+    __shared__ float4 sB[WAVES][WAVE];
+    __shared__ __attribute__((aligned(16))) float sG[WAVES][WAVE * NF];
+    __shared__ float sW[WAVES][WAVE * WS];
+    if (hdr->overflow) return;
+    const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
+    if (list_pos >= hdr->num_busy_wgs) return;
+    const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
+    if (g.r1 <= g.r0) return;
+    const int lane = g.lane;
+    const int c0 = (int)blockIdx.y * NF, nc = min(NF, F - c0);
+    const float pxf = (float)g.px, pyf = (float)g.py;
+    const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
+    float4 *wA = sA[g.wid], *wB = sB[g.wid];
+    float *wG = sG[g.wid], *wW = sW[g.wid];
+
+    const float T_final = g.inside ? final_T[q] : 0.f;
+    const uint32_t last = g.inside ? n_contrib[q] : 0u;
+#pragma unroll
+    for (int c = 0; c < NF; c++) wG[lane * NF + c] = (c < nc && g.inside) ? dL_dfeat[(size_t)(c0 + c) * npix + q] : 0.f;
+
+    uint32_t m = last;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    const int64_t max_last = (int64_t)__builtin_amdgcn_readfirstlane((int)m);
+    if (max_last == 0) return;
+
+    float T = T_final;
+    float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
+    uint32_t nRec = 0;
+    const int bin_x = g.bin % bx, bin_y = g.bin / bx;
+    auto stage = [&](uint32_t list_pos) {
+        const uint32_t id = point_list[list_pos];
+        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
+        nA = s[0]; nB = s[1];
+        const float4 c = s[2];
+        const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
+        const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
+        nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+    };
+    if ((int64_t)lane <= max_last - 1) stage(g.r0 + (uint32_t)(max_last - 1 - lane));
+    for (int64_t top = max_last - 1; top >= 0; top -= WAVE) {
+        const int cnt = (int)min((int64_t)WAVE, top + 1);
+        wave_sync_lds();
+        wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
+        wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
+        const uint32_t curRec = nRec;
+        wave_sync_lds();
+        const int64_t ntop = top - WAVE;
+        if (ntop - lane >= 0) stage(g.r0 + (uint32_t)(ntop - lane));
+        unsigned long long touched = 0ull;
+        for (int j = 0; j < cnt; j++) {
+            const uint32_t pos = (uint32_t)(top - j);
+            const float4 a = wA[j];
+            const float4 b = wB[j];
+            const float dx = a.x - pxf, dy = a.y - pyf;
+            const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
+            const float G = __builtin_amdgcn_exp2f(power);
+            const float alpha = fminf(0.99f, b.y * G);
+            const unsigned long long valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
+            if (valid_m == 0ull) continue;  // (its weights are never read: lane j only sums when touched)
+            const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
+            touched |= 1ull << j;
+            const float ae = valid ? alpha : 0.f;
+            const float rcp = __builtin_amdgcn_rcpf(1.f - ae);
+            T = T * rcp;
+            wW[lane * WS + j] = ae * T;
+        }
+        wave_sync_lds();
+        if ((touched >> lane) & 1ull) {
+            float acc[NF];
+#pragma unroll
+            for (int c = 0; c < NF; c++) acc[c] = 0.f;
+#pragma unroll 2
+            for (int p = 0; p < WAVE; p++) {
+                const float w = wW[p * WS + lane];
+#pragma unroll
+                for (int c = 0; c < NF; c += 4) {
+                    const float4 gv = *reinterpret_cast<const float4 *>(wG + p * NF + c);
+                    acc[c] += w * gv.x;
+                    acc[c + 1] += w * gv.y;
+                    acc[c + 2] += w * gv.z;
+                    acc[c + 3] += w * gv.w;
+                }
+            }
+            float *dst = inst_dfeat + (size_t)curRec * (size_t)F + c0;
+#pragma unroll
+            for (int c = 0; c < NF; c++)
+                if (c < nc) dst[c] = acc[c];
+        }
+    }
+}
+
+// Feature maps, backward (b), second half: each Gaussian's flagged slots streamed in slot order (k_preprocess_bwd's order and slot range) into
+// dL_dfeatures[row, c]; one thread per (Gaussian, channel), so neighbouring threads read neighbouring floats of a slot.  Gaussians without records
+// -- culled, overflowed view, or inst_dfeat NULL (the feature map received no gradient) -- get exact zeros.  Rows outside the view are not written.
+__global__ __launch_bounds__(256) void k_feature_grad_gather(int P, int F, const uint32_t *__restrict__ row_range, const int *__restrict__ radii,
+                                                             const uint32_t *__restrict__ goff, const uint32_t *__restrict__ gpart,
+                                                             const uint8_t *__restrict__ inst_valid, const float *__restrict__ inst_dfeat,
+                                                             const GsrHeader *__restrict__ hdr, float *__restrict__ dL_dfeatures) {
+    uint32_t row0;
+    int nP;
+    gsr_view_rows(row_range, P, row0, nP);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)nP * F) return;
+    const int i = (int)(idx / F), c = (int)(idx - (int64_t)i * F);
+    const size_t r = (size_t)row0 + (size_t)i;
+    float sum = 0.f;
+    if (inst_dfeat && hdr->overflow == 0u && radii[r] > 0) {
+        const int gb = i >> GSR_BIN_SHIFT;
+        const uint32_t gbase = gpart[gb];
+        const uint32_t s0 = gbase + goff[i];
+        const uint32_t s1 = ((i & (GSR_BIN_THREADS - 1)) != GSR_BIN_THREADS - 1 && i + 1 < P) ? gbase + goff[i + 1] : ((gb + 1) * GSR_BIN_THREADS < P ? gpart[gb + 1] : hdr->num_slots);
+        for (uint32_t k = s0; k < s1; k++)
+            if (inst_valid[k]) sum += inst_dfeat[(size_t)k * F + c];
+    }
+    dL_dfeatures[r * F + c] = sum;
+}
+
 }  // namespace
 
 void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
@@ -334,4 +798,65 @@ void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *spla
     else
         hipLaunchKernelGGL(k_composite_bwd<false>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
                            final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr, nullptr, nullptr);
+}
+
+// feature chunk width of the forward and the per-slot sums: the smallest of 4 / 8 / 16 that holds F, 16-channel chunks beyond
+static int feat_chunk(int F) { return F <= 4 ? 4 : F <= 8 ? 8 : 16; }
+
+void gsr_launch_composite_fwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                   const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
+                                   const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const float *features, int F,
+                                   const uint32_t *row_range, float *out_feat, hipStream_t s) {
+    const int wgs = (bx / WAVES) * by;
+    if (wgs <= 0 || F <= 0) return;
+    const int nf = feat_chunk(F);
+    const dim3 grid(wgs, (F + nf - 1) / nf), block(64 * WAVES);
+    const bool ex = out_depth || out_alpha;
+#define GSR_FWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_fwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, \
+                                              out_color, final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha, features, F, row_range, out_feat)
+    if (ex) {
+        if (nf == 4) GSR_FWD_FEAT(true, 4); else if (nf == 8) GSR_FWD_FEAT(true, 8); else GSR_FWD_FEAT(true, 16);
+    } else {
+        if (nf == 4) GSR_FWD_FEAT(false, 4); else if (nf == 8) GSR_FWD_FEAT(false, 8); else GSR_FWD_FEAT(false, 16);
+    }
+#undef GSR_FWD_FEAT
+}
+
+void gsr_launch_composite_bwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                   const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
+                                   const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
+                                   GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
+                                   const float *features, int F, const uint32_t *row_range, const float *dL_dfeat, float *inst_dfeat, hipStream_t s) {
+    const int wgs = (bx / WAVES) * by;
+    if (wgs <= 0 || F <= 0 || !dL_dfeat) return;
+    {
+        const dim3 grid(wgs), block(64 * WAVES);
+#define GSR_BWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_bwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, \
+                                              dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, \
+                                              features, F, row_range, dL_dfeat)
+        if (inst_ddepth) {
+            if (F <= 4) GSR_BWD_FEAT(true, 4); else if (F <= 8) GSR_BWD_FEAT(true, 8); else if (F <= 16) GSR_BWD_FEAT(true, 16);
+            else if (F <= 32) GSR_BWD_FEAT(true, 32); else GSR_BWD_FEAT(true, 64);
+        } else {
+            if (F <= 4) GSR_BWD_FEAT(false, 4); else if (F <= 8) GSR_BWD_FEAT(false, 8); else if (F <= 16) GSR_BWD_FEAT(false, 16);
+            else if (F <= 32) GSR_BWD_FEAT(false, 32); else GSR_BWD_FEAT(false, 64);
+        }
+#undef GSR_BWD_FEAT
+    }
+    if (inst_dfeat) {
+        const int nf = feat_chunk(F);
+        const dim3 grid(wgs, (F + nf - 1) / nf), block(64 * WAVES);
+#define GSR_FEATGRAD(N) hipLaunchKernelGGL((k_composite_bwd_featgrad<N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, \
+                                           final_T, n_contrib, goff, gpart, hdr, F, dL_dfeat, inst_dfeat)
+        if (nf == 4) GSR_FEATGRAD(4); else if (nf == 8) GSR_FEATGRAD(8); else GSR_FEATGRAD(16);
+#undef GSR_FEATGRAD
+    }
+}
+
+void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart,
+                                    const uint8_t *inst_valid, const float *inst_dfeat, const GsrHeader *hdr, float *dL_dfeatures, hipStream_t s) {
+    const int64_t n = (int64_t)P * F;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_feature_grad_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, F, row_range, radii, goff, gpart, inst_valid, inst_dfeat, hdr,
+                       dL_dfeatures);
 }

@@ -78,14 +78,15 @@ class _PackViews(torch.autograd.Function):
         ctx.meta = (n_views, B, S2, [tuple(t.shape) for t in tensors])
         # the packed colours are differentiable only if some image is (in stage 2 none is: the rasteriser backward then skips dL/dcolour)
         img_needs = any(ctx.needs_input_grad[1 + v * per + 1] for v in range(n_views))
+        # row_of_pixel (the packed row of every pixel, -1 where invalid) is handed out too: pack_features packs more maps with it
         if img_needs:
-            ctx.mark_non_differentiable(offsets)
+            ctx.mark_non_differentiable(offsets, row_of_pixel)
         else:
-            ctx.mark_non_differentiable(offsets, out[1])
-        return (*out, offsets)
+            ctx.mark_non_differentiable(offsets, out[1], row_of_pixel)
+        return (*out, offsets, row_of_pixel)
 
     @staticmethod
-    def backward(ctx, g_xyz, g_rgb, g_rot, g_scale, g_op, _g_offsets):
+    def backward(ctx, g_xyz, g_rgb, g_rot, g_scale, g_op, _g_offsets, _g_rows):
         lib = _capi.lib()
         (row_of_pixel,) = ctx.saved_tensors
         n_views, B, S2, shapes = ctx.meta
@@ -114,12 +115,30 @@ class _PackViews(torch.autograd.Function):
         return (None, *grads)
 
 
-def pack_views(data, views=VIEWS):
+def pack_views(data, views=VIEWS, return_rows=False):
     """data: the reference's nested dict (data[view]['xyz','img','rot_maps','scale_maps','opacity_maps','pts_valid']).
     Returns (xyz, rgb, rot, scale, opacity, offsets): packed rows for the whole batch (capacity B*len(views)*S2 rows; only
-    the first offsets[-1] are defined) and the int32 device tensor offsets[B+1]."""
+    the first offsets[-1] are defined) and the int32 device tensor offsets[B+1].  return_rows=True: also row_of_pixel, int32 [B, len(views), S2]
+    on the device, the packed row of every pixel (-1 where pts_valid is false), for pack_features."""
     flat = []
     for v in views:
         d = data[v]
         flat += [d['xyz'], d['img'], d['rot_maps'], d['scale_maps'], d['opacity_maps'], d['pts_valid']]
-    return _PackViews.apply(len(views), *flat)
+    out = _PackViews.apply(len(views), *flat)
+    return out if return_rows else out[:6]
+
+
+def pack_features(data, key, row_of_pixel, views=VIEWS):
+    """data[view][key] [B, F, H, W] of every view -> [B * len(views) * S2, F] fp32 rows in pack_views' order (same validity mask, same rows; rows
+    behind offsets[-1] are zeros), differentiable back to the per-view maps.  Torch index ops on the device: no host synchronisation.  Every
+    pixel has its own destination row (an invalid one a scratch row behind the packed capacity), so the copy is deterministic."""
+    maps = [data[v][key] for v in views]
+    B, F = int(maps[0].shape[0]), int(maps[0].shape[1])
+    S2 = int(row_of_pixel.shape[-1])
+    if any(m.dim() != 4 or tuple(m.shape[:2]) != (B, F) or m.shape[2] * m.shape[3] != S2 for m in maps):
+        raise RuntimeError("gps_gaussian_amd: feature maps must be [B, F, H, W] like the views' images")
+    src = torch.stack([m.reshape(B, F, S2) for m in maps], 1).to(torch.float32).permute(0, 1, 3, 2).reshape(-1, F)  # [B*V*S2, F], pixel order
+    rows = row_of_pixel.reshape(-1).to(torch.int64)
+    cap = rows.numel()
+    dest = torch.where(rows >= 0, rows, cap + torch.arange(cap, device=rows.device))
+    return src.new_zeros((2 * cap, F)).index_copy(0, dest, src)[:cap]

@@ -477,8 +477,18 @@ def _too_many(R):
     return RuntimeError("gps_gaussian_amd: this view needs %d (Gaussian, bin) instances, more than the 2^31 - 1 the workspace layout can address" % R)
 
 
+def _features(features, N, dev):
+    """features [P, F] -> fp32 contiguous on the device (as _prep does), 1 <= F <= GSR_MAX_FEATURES; raises before anything is launched."""
+    if not isinstance(features, torch.Tensor):
+        raise TypeError("features must be a tensor")
+    if features.dim() != 2 or not 1 <= features.shape[1] <= _capi.GSR_MAX_FEATURES or features.shape[0] != N:
+        raise RuntimeError("features must have dimensions (num_points, F) with 1 <= F <= %d" % _capi.GSR_MAX_FEATURES)
+    return _prep(features, "features", (int(features.shape[1]),), dev)
+
+
 def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, needs_grad, out_color=None, rows=None,
-                  radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None, antialiasing=False):
+                  radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None, antialiasing=False,
+                  features=None, out_feat=None, feat_grad=True):
     """One view's forward through the C-ABI (capacity policy, early notification, overflow repair).  `ctx` is any attribute holder: the
     autograd ctx of _RasterizeGaussians, or a plain namespace when a caller drives several views itself (render_api._RenderBatch).
     Leaves on it: raster_settings, cap, family, extra_flags, rows, saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
@@ -490,8 +500,11 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     depth_alpha: also render the depth map (sum z_i alpha_i T_i, unnormalised) and the alpha map (sum alpha_i T_i), background 0, with the VALU
     compositing family (include/gpsgs.h GsrViewExt.out_depth); out_depth / out_alpha: optional preallocated contiguous fp32 [H,W] (or [1,H,W])
     tensors for them.  antialiasing (or a truthy raster_settings.antialiasing): GSR_FLAG_ANTIALIAS, each splat's opacity scaled by
-    sqrt(det(cov2D) / det(cov2D + 0.3 I)) (include/gpsgs.h), carried to the backward in ctx.
-    -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W])"""
+    sqrt(det(cov2D) / det(cov2D + 0.3 I)) (include/gpsgs.h), carried to the backward in ctx.  features [P, F] (1 <= F <= 64): also render the
+    feature map [F,H,W] = sum_i f_i alpha_i T_i, background 0, with the VALU family (include/gpsgs.h GsrFeatures); out_feat: optional preallocated
+    contiguous fp32 [F,H,W] tensor for it; feat_grad=False: the backward will not form dL/dfeatures (the workspace gets no feature tail).  The
+    feature array is appended to ctx.saved.
+    -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W]); with features the feature map is appended last"""
     rs = raster_settings
     lib = _capi.lib()
     if not means3D.is_cuda:
@@ -522,6 +535,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     if not all(t is None or t.shape[0] == N for t in (col, opa, sca, rot, sh, cov)):
         raise RuntimeError("all per-Gaussian inputs must have num_points rows")
     appear = (sh, int(rs.sh_degree), campos, cov, None, None) if (sh is not None or cov is not None) else None
+    fea = _features(features, N, dev) if features is not None else None
     view = _cam(rs.viewmatrix, 16, dev)
     proj = _cam(rs.projmatrix, 16, dev)
     bg = _cam(rs.bg, 3, dev)
@@ -530,8 +544,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     st = _dev_state(dev)
     mode = _check_mode()
     family = _composite_flag() | (_wave_priority_flag(st, torch._C._cuda_getCurrentRawStream(dev.index), deterministic=(mode == "none")) if rows is None else 0)
-    if depth_alpha:
-        family = 0  # the depth / alpha maps are made by the VALU kernels (forward and backward of a view must agree on the family)
+    if depth_alpha or fea is not None:
+        family = 0  # the depth / alpha and feature maps are made by the VALU kernels (forward and backward of a view must agree on the family)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
     base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family | (_capi.GSR_FLAG_ANTIALIAS if antialiasing else 0)
     if mode != "none" and torch.cuda.is_current_stream_capturing():
@@ -554,6 +568,14 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
             for t in dmaps:
                 if t.dtype is not torch.float32 or t.device != dev or t.numel() != H * W or not t.is_contiguous():
                     raise RuntimeError("gps_gaussian_amd: out_depth / out_alpha must be contiguous fp32 [H, W] tensors on the inputs' device")
+        fmap = feat = None
+        if fea is not None:
+            F = int(fea.shape[1])
+            fmap = torch.empty((F, H, W), dtype=torch.float32, device=dev) if out_feat is None else out_feat
+            if fmap.dtype is not torch.float32 or fmap.device != dev or fmap.numel() != F * H * W or not fmap.is_contiguous():
+                raise RuntimeError("gps_gaussian_amd: out_feat must be a contiguous fp32 [F, H, W] tensor on the inputs' device")
+            feat = _capi.GsrFeatures()
+            feat.channels, feat.features, feat.out_features = F, fea.data_ptr(), fmap.data_ptr()
         if rows is None:
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
         else:
@@ -571,17 +593,22 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
 
         def launch(cap, bin_cap, plan_flags):
             """Enqueue the whole forward (one _plan).  -> (notify note or None, cap, bin_cap)"""
-            nbytes = (lib.gsr_workspace_bytes_depth_alpha if depth_alpha else lib.gsr_workspace_bytes_ex)(P, W, H, cap, bin_cap, fwd_only)
+            if feat is not None and feat_grad and not fwd_only:  # the per-slot feature sums need the feature tail
+                nbytes = lib.gsr_workspace_bytes_features(P, W, H, cap, bin_cap, feat.channels, fwd_only)
+            else:
+                nbytes = (lib.gsr_workspace_bytes_depth_alpha if depth_alpha else lib.gsr_workspace_bytes_ex)(P, W, H, cap, bin_cap, fwd_only)
             st["last_ws_bytes"] = nbytes  # reported by last_stats(): what one view in flight holds (forward-only workspaces are ~3x smaller)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             note, hdr_ptr = ring.acquire_notify() if ring is not None else (None, None)
             ext = _ext(rows, st.get("longest", 0), appear, bin_cap, dmaps)  # (every attempt, the repair included, writes the maps) work order: longest lists first, relative to the longest list seen on this device
-            rc = lib.gsr_forward_ex(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier), float(rs.tanfovx),
-                                    float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap,
-                                    base_flags | plan_flags, stream, hdr_ptr, note[3] if note is not None else 0, C.byref(ext))
+            args = (P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier), float(rs.tanfovx),
+                    float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap,
+                    base_flags | plan_flags, stream, hdr_ptr, note[3] if note is not None else 0, C.byref(ext))
+            # (every attempt, the repair included, writes the feature map too)
+            rc = lib.gsr_forward_ex(*args) if feat is None else lib.gsr_forward_features(*args, C.byref(feat))
             if rc != 0 and note is not None:
                 ring.release(note[1])
-            _capi.check(rc, "gsr_forward_ex")
+            _capi.check(rc, "gsr_forward_ex" if feat is None else "gsr_forward_features")
             box[:] = ws, cap, bin_cap
             return note, cap, bin_cap
 
@@ -624,9 +651,10 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     ctx.depth_alpha = bool(depth_alpha)
     ctx.antialias = antialiasing
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
-    if depth_alpha:
-        return color, radii, dmaps[0], dmaps[1]
-    return color, radii
+    if fea is not None:
+        ctx.saved = ctx.saved + (fea,)
+    out = (color, radii) + ((dmaps[0], dmaps[1]) if depth_alpha else ())
+    return out + (fmap,) if fea is not None else out
 
 
 def _map_grad(g):
@@ -635,7 +663,8 @@ def _map_grad(g):
     return g.detach().to(dtype=torch.float32).contiguous()
 
 
-def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_depth=None, grad_alpha=None, cam_out=None):
+def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_depth=None, grad_alpha=None, cam_out=None, grad_feat=None,
+                   feat_out=None):
     """One view's backward through the C-ABI.  color_grad=False: the caller does not need dL/dcolours (GSR_FLAG_NO_COLOR_GRAD: the tile
     family leaves the colour sums out; the returned colour gradient is zeros / not meaningful).  saved: the tuple _forward_impl left in ctx.saved; arena: optional five preallocated
     gradient tensors (means3D, colours, opacities, scales, rotations) -- for a row-range view (ctx.rows) they are REQUIRED and batch-wide,
@@ -643,11 +672,13 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
     SH coefficients / precomputed covariances (d_sc, d_rot are then not meaningful).  grad_depth / grad_alpha: gradients of the depth and alpha
     maps of a depth_alpha forward ([H,W] or [1,H,W]; None = zero); grad_out_color may then be None too.  cam_out: None, or three contiguous fp32
     device tensors / None -- dL/d(viewmatrix [16], projmatrix [16], campos [3]) are WRITTEN into them (gsr_backward_camera: the per-Gaussian
-    gradients keep their bits)."""
+    gradients keep their bits).  Features (the forward was given some: saved[13]): grad_feat is the feature map's gradient ([F,H,W], None = zero);
+    feat_out None, or a contiguous fp32 [rows, F] device tensor that dL/dfeatures is WRITTEN into (a row-range view: batch-wide, its rows written)."""
     rs = ctx.raster_settings
     lib = _capi.lib()
     m3, col, opa, sca, rot, view, proj, bg, radii, ws = saved[:10]
     sh, cov, campos = saved[10:13] if len(saved) >= 13 else (None, None, None)
+    fea = saved[13] if len(saved) >= 14 else None
     cap = ctx.cap
     rows = getattr(ctx, "rows", None)
     box = getattr(ctx, "ws_box", None)
@@ -663,6 +694,17 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
         g = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
     elif g.dtype is not torch.float32 or not g.is_contiguous() or g.requires_grad:
         g = g.detach().to(dtype=torch.float32).contiguous()
+    feat = None
+    if fea is not None:
+        F = int(fea.shape[1])
+        gf = _map_grad(grad_feat)
+        if gf is not None and (gf.numel() != F * H * W or gf.device != dev):
+            raise RuntimeError("gps_gaussian_amd: the feature map's gradient must have F x H x W elements on the inputs' device")
+        if feat_out is not None and (feat_out.dtype is not torch.float32 or not feat_out.is_contiguous() or feat_out.device != dev
+                                     or tuple(feat_out.shape) != (N, F)):
+            raise RuntimeError("gps_gaussian_amd: the features' gradient array must be contiguous fp32 [rows, F] on the inputs' device")
+        feat = _capi.GsrFeatures()
+        feat.channels, feat.features, feat.dL_dfeaturemap, feat.dL_dfeatures = F, fea.data_ptr(), _ptr(gf), _ptr(feat_out)
     dmaps = None
     if getattr(ctx, "depth_alpha", False) and (grad_depth is not None or grad_alpha is not None):
         dmaps = (_map_grad(grad_depth), _map_grad(grad_alpha))
@@ -699,7 +741,14 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
                     ws.numel(), cap, (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | getattr(ctx, "extra_flags", _extra_flags) | ctx.family
                     | (0 if color_grad else _capi.GSR_FLAG_NO_COLOR_GRAD) | (_capi.GSR_FLAG_ANTIALIAS if getattr(ctx, "antialias", False) else 0),
                     stream, C.byref(ext))
-            if cam_out is None:
+            if feat is not None:
+                # one entry point for every combination: camera outputs may be NULL
+                nbytes = lib.gsr_camera_grad_scratch_bytes(P) if cam_out is not None else 0
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if cam_out is not None else None
+                rc = lib.gsr_backward_features(*args, *((_ptr(t) for t in cam_out) if cam_out is not None else (None, None, None)), _ptr(scratch), nbytes,
+                                               C.byref(feat))
+                _capi.check(rc, "gsr_backward_features")
+            elif cam_out is None:
                 rc = lib.gsr_backward_ex(*args)
                 _capi.check(rc, "gsr_backward_ex")
             else:
@@ -792,7 +841,7 @@ def _cam_grad_as(g, t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None):
+                return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None, features=None):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
@@ -803,8 +852,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.cams = (viewmatrix, projmatrix, campos) if camera_grad else None
         # stage 2 never differentiates the colours (they are input pixels, lib/GaussianRender.py:30-31): the backward then skips their sums
         ctx.color_grad = bool(ctx.needs_input_grad[3]) or sh is not None  # (dL/dsh is formed from dL/dcolour)
+        # features [P, F]: the feature map is appended to the outputs, dL/dfeatures is formed only when they require a gradient
+        ctx.return_depth_alpha = bool(return_depth_alpha)
+        ctx.has_features = features is not None
         out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
-                            shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha), antialiasing=antialiasing)
+                            shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha), antialiasing=antialiasing,
+                            features=features, feat_grad=features is not None and ctx.needs_input_grad[16])
         if _debug_keep_ws:
             _tls.last_ws = dict(ws=ctx.saved[9], cap=ctx.cap, bin_cap=ctx.bin_cap)
         ctx.save_for_backward(*ctx.saved)
@@ -814,31 +867,47 @@ class _RasterizeGaussians(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:  # no output took part in the loss
-            return (None,) * 16
+    def backward(ctx, grad_out_color, _grad_radii, *grad_maps):
+        # grad_maps: (dL/ddepth, dL/dalpha) with return_depth_alpha, then dL/dfeaturemap with features
+        grad_depth, grad_alpha = grad_maps[:2] if ctx.return_depth_alpha else (None, None)
+        grad_feat = grad_maps[-1] if ctx.has_features else None
+        if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_feat is None:  # no output took part in the loss
+            return (None,) * 17
         saved = ctx.saved_tensors
         cam_out = None
         if ctx.camera_grad:
             cam_out = _cam_grads(ctx.needs_input_grad[13:16], ctx.cams, saved[0].device)
+        d_feat = None
+        if ctx.has_features and ctx.needs_input_grad[16]:
+            fea = saved[13]
+            d_feat = torch.empty(tuple(fea.shape), dtype=torch.float32, device=fea.device)
         d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad,
-                                                                           grad_depth, grad_alpha, cam_out)
+                                                                           grad_depth, grad_alpha, cam_out, grad_feat, d_feat)
         has_sh, has_cov = saved[10] is not None, saved[11] is not None
         d_cam = (None, None, None) if cam_out is None else tuple(_cam_grad_as(g, t) for g, t in zip(cam_out, ctx.cams))
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha,
         #  antialiasing, camera_grad, viewmatrix, projmatrix, campos)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None, None, None, None) + d_cam
+                d_cov, None, None, None, None, None) + d_cam + (d_feat,)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False, antialiasing=False, camera_grad=False):
+                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
     and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
     antialiasing=True (or a truthy raster_settings.antialiasing): the opacity-compensated 2D filter, include/gpsgs.h GSR_FLAG_ANTIALIAS.
     camera_grad=True: raster_settings.viewmatrix, projmatrix and campos become differentiable inputs -- each that requires a gradient gets
-    dL/d(itself) in its own shape, dtype and device (include/gpsgs.h gsr_backward_camera; without the keyword they are constants, as upstream)."""
+    dL/d(itself) in its own shape, dtype and device (include/gpsgs.h gsr_backward_camera; without the keyword they are constants, as upstream).
+    features [P, F] (1 <= F <= 64, on means3D's device): also returns the feature map [F,H,W] = sum_i f_i alpha_i T_i, background 0, LAST --
+    (color, radii, feat) or (color, radii, depth, alpha, feat) -- rendered by the VALU kernels with the image's blend weights, differentiable in
+    the features and, through the weights, in the geometry (include/gpsgs.h GsrFeatures)."""
+    if features is not None:
+        rs = raster_settings
+        cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos)) if camera_grad else (None, None, None)
+        aa = bool(antialiasing) or bool(getattr(rs, "antialiasing", False))
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, bool(return_depth_alpha), aa, bool(camera_grad), *cams, features)
     if camera_grad:
         rs = raster_settings
         cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
@@ -864,14 +933,15 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False):
+                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         antialiasing = antialiasing or getattr(self.raster_settings, "antialiasing", False)
-        if shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing and not camera_grad:
+        if (shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing and not camera_grad
+                and features is None):
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -881,8 +951,9 @@ class GaussianRasterizer(nn.Module):
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
         # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing and camera_grad: the Python host path (not
         # the compiled one)
+        # features [P, F]: the feature map is appended to the outputs (rasterize_gaussians)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad)
+                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad, features)
 
 
     def markVisible(self, positions):

@@ -102,22 +102,25 @@ class _RenderBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False, camera_grad=False,
-                view_all=None, proj_all=None, campos_all=None):
+                view_all=None, proj_all=None, campos_all=None, features=None):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
         # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
         # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS;
         # camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds them) get
-        # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True))
+        # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True)); features: packed [N, F] (pack.pack_features), the
+        # feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...))
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
         out = torch.empty((bs, 3, H, W), dtype=torch.float32, device=dev)
         dmaps = (torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev), torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev)) if depth_alpha else None
+        fmaps = torch.empty((bs, features.shape[1], H, W), dtype=torch.float32, device=dev) if features is not None else None
+        feat_grad = features is not None and ctx.needs_input_grad[14]
         radii = torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
         side = _streams(dev, bs) if (bs > 1 and not torch.cuda.is_current_stream_capturing()) else [cur] * bs
-        needs = any(ctx.needs_input_grad[:5])
+        needs = any(ctx.needs_input_grad[:5]) or feat_grad
         views = []
         with _RZ.defer_capacity_checks():
             for i in range(bs):
@@ -128,7 +131,8 @@ class _RenderBatch(torch.autograd.Function):
                     _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, out_color=out[i],
                                       rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
                                       out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None,
-                                      antialiasing=antialiasing)
+                                      antialiasing=antialiasing, features=features, out_feat=fmaps[i] if fmaps is not None else None,
+                                      feat_grad=feat_grad)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -148,21 +152,26 @@ class _RenderBatch(torch.autograd.Function):
         ctx.cams = (view_all, proj_all, campos_all) if camera_grad else None
         ctx.color_grad = bool(ctx.needs_input_grad[1])  # False in stage 2: pack_views marks rgb non-differentiable when no image needs a gradient
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
+        ctx.depth_alpha, ctx.has_features, ctx.feat_grad = bool(depth_alpha), features is not None, feat_grad
+        ctx.feat_shape = tuple(features.shape) if features is not None else None
         ctx.set_materialize_grads(False)
-        if depth_alpha:
-            return out, dmaps[0], dmaps[1]
-        return out
+        outs = (out,) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmaps,) if fmaps is not None else ())
+        return outs if len(outs) > 1 else out
 
     @staticmethod
-    def backward(ctx, gout, gdepth=None, galpha=None):
-        if gout is None and gdepth is None and galpha is None:
-            return (None,) * 14
+    def backward(ctx, gout, *gmaps):
+        gdepth, galpha = gmaps[:2] if ctx.depth_alpha else (None, None)
+        gfeat = gmaps[-1] if ctx.has_features else None
+        if gout is None and gdepth is None and galpha is None and gfeat is None:
+            return (None,) * 15
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
         g = gout.detach().to(dtype=torch.float32).contiguous() if gout is not None else None
         gd = gdepth.detach().to(dtype=torch.float32).contiguous() if gdepth is not None else None
         ga = galpha.detach().to(dtype=torch.float32).contiguous() if galpha is not None else None
+        gf = gfeat.detach().to(dtype=torch.float32).contiguous() if gfeat is not None else None
+        d_feat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev) if ctx.feat_grad else None  # batch-wide, each view writes its rows
         # one gradient buffer per packed tensor (+ one for the unused screen-space gradient); every view's backward writes its own
         # rows, rows behind offsets[-1] (the unused tail of the packed capacity) are never read by the pack backward
         d_xyz, d_rgb, d_rot, d_scale, d_op = (torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes)
@@ -180,14 +189,15 @@ class _RenderBatch(torch.autograd.Function):
             with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.ws_box in there)
                 _RZ._backward_impl(h, tuple(ins) + tuple(h.tail), g[i] if g is not None else None, (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2),
                                    ctx.color_grad, gd[i] if gd is not None else None, ga[i] if ga is not None else None,
-                                   None if cam_all is None else tuple(c[i] if c is not None else None for c in cam_all))
+                                   None if cam_all is None else tuple(c[i] if c is not None else None for c in cam_all),
+                                   gf[i] if gf is not None else None, d_feat)
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
         d_cam = (None, None, None)
         if cam_all is not None:
             d_cam = tuple(_RZ._cam_grad_as(c, t) for c, t in zip(cam_all, ctx.cams))
-        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam
+        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat,)
 
 
 def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
@@ -214,21 +224,26 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
     return rendered_image
 
 
-def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
+def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False,
+              features=None):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
     The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE.
     antialiasing=True: as render()'s; the maps then see the filtered opacities too.  camera_grad=True: as render()'s, the maps' gradients
-    included."""
+    included.  features [P, F] (1 <= F <= 64): also 'feat' [F,H,W] = sum_i f_i alpha_i T_i, background 0 (for a feature background add
+    (1 - alpha) bg_f), differentiable in the features and the geometry (rasterizer.rasterize_gaussians)."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
-    img, _, depth, alpha = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
-                                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
-                                      camera_grad=camera_grad)
-    return {'img': img, 'depth': depth, 'alpha': alpha}
+    out = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
+                     rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
+                     camera_grad=camera_grad, features=features)
+    r = {'img': out[0], 'depth': out[2], 'alpha': out[3]}
+    if features is not None:
+        r['feat'] = out[4]
+    return r
 
 
 def _settings(nv, idx, bg, view=None, proj=None):
@@ -248,12 +263,15 @@ def _to_device_once(t, dev):
     return t
 
 
-def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False):
+def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
     antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
     camera_grad=True (opt-in): each sample's camera gradient reaches data['novel_view']['world_view_transform'], ['full_proj_transform'] and
     ['camera_center'] ([B,4,4], [B,4,4], [B,3]) where they require one -- with the bits of B render_ex / render calls.
+    feature_key (opt-in): data['lmain'][feature_key] and data['rmain'][feature_key], each [B,F,H,W] (1 <= F <= 64), are packed with the
+    same validity mask and row order as 'img' (pack.pack_features: torch index ops, no host sync) and splatted with the image's blend weights:
+    'feat_pred' [B,F,H,W] (render_ex(features=...)), differentiable back to the per-view maps.
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -264,7 +282,13 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     from .pack import pack_views
 
     bs = data['lmain']['img'].shape[0]
-    xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
+    feats = None
+    if feature_key is None:
+        xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
+    else:
+        from .pack import pack_features
+        xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
+        feats = pack_features(data, feature_key, row_of_pixel)
     nv = data['novel_view']
     dev = xyz.device
     sizes_hw = {(int(nv['height'][i]), int(nv['width'][i])) for i in range(bs)}
@@ -272,7 +296,15 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        if camera_grad:
+        if feats is not None:
+            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
+                                     bool(camera_grad), *cams, feats)
+            nv['img_pred'] = out[0]
+            if with_depth_alpha:
+                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
+            nv['feat_pred'] = out[-1]
+        elif camera_grad:
             cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center'])
             out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
                                      True, *cams)
@@ -288,10 +320,10 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         else:
             nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad)
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad, feats)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False):
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None):
     """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
@@ -307,6 +339,9 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
     else:
         arenas, a_parts = [None] * 5, None
     parts = [_SplitRows.apply(t, sizes, a) for t, a in zip(packed, arenas)]
+    # the features' split has no arena (the rasteriser backward allocates dL/dfeatures per sample): its backward concatenates the samples'
+    # gradients, and the empty device tensor only gives the zero-filled tail its device
+    f_parts = _SplitRows.apply(feats, sizes, feats.new_empty((0, feats.shape[1]))) if feats is not None else None
     out = []
     dev = xyz.device
     cur = torch.cuda.current_stream(dev)
@@ -321,10 +356,10 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
             if side[i] is not cur:
                 side[i].wait_stream(cur)
             with torch.cuda.stream(side[i]):
-                if with_depth_alpha:
+                if with_depth_alpha or feats is not None:
                     r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
-                                  antialiasing=antialiasing, camera_grad=camera_grad)
-                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha')))
+                                  antialiasing=antialiasing, camera_grad=camera_grad, features=f_parts[i] if feats is not None else None)
+                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha') + (('feat',) if feats is not None else ())))
                 else:
                     out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
                                        grad_arena=ga, antialiasing=antialiasing, camera_grad=camera_grad).unsqueeze(0),))
@@ -338,6 +373,8 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
     if with_depth_alpha:
         nv['depth_pred'] = torch.cat([o[1] for o in out], dim=0)
         nv['alpha_pred'] = torch.cat([o[2] for o in out], dim=0)
+    if feats is not None:
+        nv['feat_pred'] = torch.cat([o[3] for o in out], dim=0)
     return data
 
 

@@ -50,7 +50,9 @@ extern "C" {
                                   gsr_direct_lists_ok; gsr_export_state / gsr_debug_count_records take bin_capacity
                                still 4 after up_splat_scratch_bytes, up_zsplat, up_flow2render_dev: purely additive, nothing existing changed
                                still 4 after the depth / alpha maps: GsrViewExt.reserved[4] became two pointer slots (out_depth | dL_ddepth,
-                                  out_alpha | dL_dalpha; zero = none, what 4 did, same 80-byte struct) + gsr_workspace_bytes_depth_alpha */
+                                  out_alpha | dL_dalpha; zero = none, what 4 did, same 80-byte struct) + gsr_workspace_bytes_depth_alpha
+                               still 4 after the feature maps: GsrFeatures, gsr_workspace_bytes_features, gsr_forward_features,
+                                  gsr_backward_features (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -272,6 +274,48 @@ int gsr_backward_camera(int P, int width, int height, const float *means3D, cons
                         float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace,
                         size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                         float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes);
+
+/* F-channel feature maps (opt-in).  A per-Gaussian feature vector f[i, 0..F) is splatted with the image's blend weights:
+ *   feat[c, p] = sum_i f[i, c] alpha_i T_i,  background 0
+ * -- the image's splats, sort order and power > 0 / alpha < 1/255 / T < 1e-4 decisions (for a feature background, add (1 - alpha) bg_f with the
+ * alpha map).  Rendered by the VALU compositing family: with features the tiles flag is ignored for that view's forward and backward, and the image
+ * has the bits of a plain VALU render.  Combines with depth / alpha maps, antialiasing, camera gradients, shs, cov3D_precomp, row ranges, both list
+ * forms and GSR_FLAG_NO_COLOR_GRAD.
+ *   features: DEVICE [rows, F] fp32, 4-byte aligned, rows as GsrViewExt.row_range says (the same rows as means3D).
+ *   gsr_forward_features: out_features DEVICE [F, H, W] (written).
+ *   gsr_backward_features: dL_dfeaturemap DEVICE [F, H, W], NULL = zero gradient (the per-Gaussian gradients then have the bits of a plain VALU
+ *     backward and dL_dfeatures is zero-filled); dL_dfeatures DEVICE [rows, F], WRITTEN for the view's rows (NULL = not wanted):
+ *     dL/df[i, c] = sum_p alpha_i T_i dL/dfeat[c, p].  dL/dfeat reaches opacity, means2D, the conic and means3D exactly as F more colour channels
+ *     with background 0 would.  No atomics: per (bin, splat) instance the F sums go to the workspace's feature tail, a gather streams each
+ *     Gaussian's slots in slot order -- the same bits on every run.  The workspace must be sized with gsr_workspace_bytes_features (the depth /
+ *     alpha tail plus cap x F floats); its camera outputs may be NULL, so it serves every combination (it is gsr_backward_camera otherwise).
+ * channels = 0 (or a NULL GsrFeatures) is the call without features.  GPSGS_E_INVALID for channels outside 0..GSR_MAX_FEATURES, NULL features with
+ * channels > 0 and P > 0 (a view without Gaussians has no rows: NULL is accepted there), pointers that are not 4-byte aligned; GPSGS_E_WORKSPACE for
+ * a workspace that is too small. */
+#define GSR_MAX_FEATURES 64
+typedef struct GsrFeatures {
+    int32_t channels;   /* F in 1..GSR_MAX_FEATURES; 0 = none */
+    uint32_t reserved0; /* 0 */
+    const float *features;                                        /* DEVICE [rows, F]; follows GsrViewExt.row_range */
+    union { float *out_features; const float *dL_dfeaturemap; };  /* [F, H, W]; backward: NULL = zero gradient */
+    float *dL_dfeatures;                                          /* backward: [rows, F], written; NULL = not wanted */
+} GsrFeatures;
+/* gsr_workspace_bytes_depth_alpha(...) plus the 256-byte aligned feature tail (instance_capacity x channels floats); forward_only: the forward-only
+ * size (the forward writes no tail).  0 for channels outside 1..GSR_MAX_FEATURES or invalid arguments. */
+size_t gsr_workspace_bytes_features(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int channels, int forward_only);
+int gsr_forward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                         const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                         const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                         void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                         void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat);
+int gsr_backward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                          const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                          const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                          const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                          float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace,
+                          size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                          float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                          const GsrFeatures *feat);
 
 /* Visibility mask (upstream `_C.mark_visible`, reached through GaussianRasterizer.markVisible(positions) of the module the reference imports at
  * gaussian_renderer/__init__.py:14; the reference itself never calls it): present[i] = 1 iff point i passes the near-plane test of the forward
