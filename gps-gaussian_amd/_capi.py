@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get("GPSGS_LIB") or os.path.join(_HERE, "lib", "libgpsgs_h
 
 # every symbol include/gpsgs.h declares (tests/test_capi_symbols.py cross-checks this list against the header)
 SYMBOLS = (
-    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features", "gsr_copy_header_async", "gsr_read_header",
+    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features", "gsr_workspace_bytes_contrib", "gsr_forward_contrib", "gsr_copy_header_async", "gsr_read_header",
     "gsr_export_state", "gsr_mark_visible", "gsr_selftest", "gsr_timing_read", "gsr_debug_count_records", "gsr_pack_scratch_bytes", "gsr_pack_views", "gsr_pack_views_backward", "fl_scratch_bytes",
     "fl_l1_ssim_forward", "fl_l1_ssim_backward", "up_unproject_forward", "up_unproject_backward", "up_unproject_forward_dev", "up_unproject_backward_dev", "up_splat_scratch_bytes", "up_zsplat", "up_flow2render_dev", "cs_forward", "cs_backward",
     "cv_build_forward", "cv_build_backward", "cs_lookup_forward", "cs_lookup_backward", "cu_upsample_forward", "cu_upsample_backward", "cu_upsample_scratch_bytes",
@@ -66,6 +66,12 @@ class GsrFeatures(C.Structure):
     _fields_ = [("channels", C.c_int32), ("reserved0", C.c_uint32), ("features", C.c_void_p), ("_map", _FeatureMapSlot), ("dL_dfeatures", C.c_void_p)]
 
 
+class GsrContrib(C.Structure):
+    """Per-Gaussian contribution statistics of one view (include/gpsgs.h): weight_sum, weight_max (fp32 [rows]) and pixel_count (int32 [rows]),
+    each NULL = not wanted; reserved must be NULL."""
+    _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixel_count", C.c_void_p), ("reserved", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -121,6 +127,10 @@ def lib():
     l.gsr_forward_features.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrFeatures)]
     l.gsr_backward_features.restype = i32
     l.gsr_backward_features.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrFeatures)]
+    l.gsr_workspace_bytes_contrib.restype = sz
+    l.gsr_workspace_bytes_contrib.argtypes = [i32, i32, i32, i64, u32, i32]
+    l.gsr_forward_contrib.restype = i32
+    l.gsr_forward_contrib.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrContrib)]
     l.gsr_copy_header_async.restype = i32
     l.gsr_copy_header_async.argtypes = [vp, vp, vp]
     l.gsr_read_header.restype = i32

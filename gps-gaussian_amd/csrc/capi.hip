@@ -181,6 +181,14 @@ extern "C" size_t gsr_workspace_bytes_features(int P, int width, int height, int
     return forward_only ? L.total_fwd : L.total_extra + gsr_feature_tail_bytes(instance_capacity, channels);
 }
 
+extern "C" size_t gsr_workspace_bytes_contrib(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
+    (void)forward_only;  // (the same size: the statistics read the slot prefix of the backward tail)
+    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
+    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
+    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    return L.total_extra + gsr_contrib_tail_bytes(instance_capacity);
+}
+
 namespace {
 // F-channel feature maps: the channel count of a GsrFeatures (0 = none), or -1 for an invalid one (range, NULL features for P > 0, misaligned pointers)
 int feature_channels(const GsrFeatures *feat, bool backward, int P) {
@@ -198,10 +206,17 @@ int forward_impl(int P, int width, int height, const float *means3D, const float
                  const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
                  const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                  void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
-                 void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
+                 void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat, const GsrContrib *contrib = nullptr) {
     const int F = feature_channels(feat, false, P);
     if (F < 0) return GPSGS_E_INVALID;
     if (F > 0) flags &= ~GSR_FLAG_COMPOSITE_TILES;  // feature maps: the VALU kernels only (as the depth / alpha maps)
+    // contribution statistics (any pointer may be NULL): the VALU family's CONTRIB forward, 16 bytes per instance slot in the workspace's tail
+    float *c_sum = contrib ? contrib->weight_sum : nullptr, *c_max = contrib ? contrib->weight_max : nullptr;
+    int32_t *c_cnt = contrib ? contrib->pixel_count : nullptr;
+    if ((reinterpret_cast<uintptr_t>(c_sum) | reinterpret_cast<uintptr_t>(c_max) | reinterpret_cast<uintptr_t>(c_cnt)) & 3u) return GPSGS_E_INVALID;
+    const bool stats = c_sum || c_max || c_cnt;
+    if (stats && F > 0) return GPSGS_E_INVALID;  // (the two tails share an offset; no entry point passes both)
+    if (stats) flags &= ~GSR_FLAG_COMPOSITE_TILES;
     const uint32_t *row_range = ext ? ext->row_range : nullptr;
     const uint32_t order_hint = ext ? ext->order_hint : 0u;
     // opt-in depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
@@ -221,6 +236,7 @@ int forward_impl(int P, int width, int height, const float *means3D, const float
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
     if (workspace_bytes < L.total_fwd) return GPSGS_E_WORKSPACE;  // the backward tail is optional for a forward
+    if (stats && workspace_bytes < L.total_extra + gsr_contrib_tail_bytes(instance_capacity)) return GPSGS_E_WORKSPACE;  // (then a training workspace)
     hipStream_t s = (hipStream_t)stream;
     uint32_t *host_hdr = nullptr;
     if (host_header_out) {  // must be pinned (hipHostMalloc / hipHostRegister) memory the device can write
@@ -368,9 +384,21 @@ int forward_impl(int P, int width, int height, const float *means3D, const float
         else if (F > 0)
             gsr_launch_composite_fwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd,
                                           out_depth, out_alpha, feat->features, F, row_range, feat->out_features, s);
-        else
+        else if (stats) {
+            float4 *inst_contrib = reinterpret_cast<float4 *>(at(workspace, L.total_extra));
+            gsr_launch_contrib_clear(inst_contrib, instance_capacity, hdr, s);
+            gsr_launch_composite_fwd_contrib(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd,
+                                             out_depth, out_alpha, q.goff, reinterpret_cast<const uint32_t *>(at(workspace, L.gprefix)), inst_contrib, s);
+        } else
             gsr_launch_composite_fwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, out_depth,
                                      out_alpha, s);
+    }
+    if (stats) {
+        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
+        trace("contrib_gather", P, width, height, (long long)instance_capacity, flags);
+        StageTimer t(flags, GSR_STAGE_COMPOSITE_FWD, s);
+        gsr_launch_contrib_gather(P, row_range, radii, q.goff, reinterpret_cast<const uint32_t *>(at(workspace, L.gprefix)),
+                                  reinterpret_cast<const float4 *>(at(workspace, L.total_extra)), hdr, c_sum, c_max, c_cnt, s);
     }
     return check(s, flags);
 }
@@ -392,6 +420,16 @@ extern "C" int gsr_forward_features(int P, int width, int height, const float *m
                                     void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
     return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                         out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, feat);
+}
+
+extern "C" int gsr_forward_contrib(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                   const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                   const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                                   void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                                   void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrContrib *contrib) {
+    if (contrib && contrib->reserved) return GPSGS_E_INVALID;
+    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, nullptr, contrib);
 }
 
 extern "C" int gsr_forward_notify(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,

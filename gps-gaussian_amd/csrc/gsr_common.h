@@ -41,6 +41,9 @@
 //   inst_ddepth[cap] the tenth per-instance sum, dL/dz (the depth map's gradient reaching the view-space depth), at the same slot as inst_dop
 //   --- feature tail (only in a workspace sized with gsr_workspace_bytes_features; every offset above is unchanged) ---
 //   inst_dfeat[cap][F] the F per-instance feature sums sum_p w dL/dfeat[c, p], slot-major, set for the slots whose inst_valid flag is set
+//   --- contribution tail (only in a workspace sized with gsr_workspace_bytes_contrib; every offset above is unchanged; never with a feature tail) ---
+//   inst_contrib[cap] 16 bytes per instance slot {sum of w, max of w, blended pixels (u32 bits), 0}, written by the CONTRIB forward for the instances
+//                  it blended anywhere and zero elsewhere (k_contrib_clear); independent of inst_valid, which stays the backward's
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -539,6 +542,19 @@ void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, con
                                     const uint8_t *inst_valid, const float *inst_dfeat, const GsrHeader *hdr, float *dL_dfeatures, hipStream_t s);
 // the feature tail of a training workspace: F floats per instance slot, behind the depth / alpha tail (total_extra)
 static inline size_t gsr_feature_tail_bytes(int64_t cap, int F) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * (size_t)F * 4); }
+// Per-Gaussian contribution statistics (GsrContrib; the VALU family only).  gsr_launch_contrib_clear zeroes the tail's slots [0, num_slots) of a
+// view that did not overflow; gsr_launch_composite_fwd_contrib is gsr_launch_composite_fwd (same image, final_T, n_contrib, maps, cleared flags) plus
+// {sum w, max w, pixels} per blended instance at its slot (goff / gpart of a training workspace); gsr_launch_contrib_gather sums each Gaussian's
+// slots in slot order into the three [rows] outputs (each may be NULL; zeros for culled Gaussians and an overflowed view).
+void gsr_launch_contrib_clear(float4 *inst_contrib, int64_t cap, const GsrHeader *hdr, hipStream_t s);
+void gsr_launch_composite_fwd_contrib(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                      const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
+                                      const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const uint32_t *goff,
+                                      const uint32_t *gpart, float4 *inst_contrib, hipStream_t s);
+void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const float4 *inst_contrib,
+                               const GsrHeader *hdr, float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s);
+// the contribution tail of a workspace: 16 bytes per instance slot, behind the depth / alpha tail (total_extra)
+static inline size_t gsr_contrib_tail_bytes(int64_t cap) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * 16); }
 // development knob: GPSGS_DEBUG_LDS_PAD=<bytes> of unused dynamic LDS per compositing workgroup (caps the waves resident per CU, to
 // measure how the kernels scale with occupancy); 0 / unset in normal use
 #include <stdlib.h>

@@ -25,20 +25,82 @@
 
 namespace {
 
+// ---- per-Gaussian contribution statistics (GsrContrib): a max / sum reduce-scatter of eight values ------------------------------------------
+// The forward's CONTRIB instantiation reduces the 64 per-lane weights of each staged splat to a wave sum and a wave max.  Eight splats (one
+// blend group) go through one butterfly reduce-scatter per operation, wave_reduce_scatter9's first 18 instructions: value k ends in every lane
+// of one 8-lane group (acc_slot(lane) for lanes 0, 8, .., 56).  Max is exact; the sum's order is fixed, so both have the same bits on every run.
+// The weights are never negative or NaN (+0 where nothing is blended), so their max is the max of their bit patterns: one v_max_u32 per step
+// (fmaxf costs two canonicalising v_max_f32 on top).
+template <bool MAX>
+__device__ __forceinline__ float rs_op(float a, float b) {
+    return MAX ? __uint_as_float(max(__float_as_uint(a), __float_as_uint(b))) : a + b;
+}
+template <bool MAX, int CTRL>
+__device__ __forceinline__ float dpp_op_row(float v) {
+    const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true);
+    return rs_op<MAX>(v, __int_as_float(t));
+}
+template <bool MAX>
+__device__ __forceinline__ float wave_reduce_scatter8(const float (&v)[8], bool upper8) {
+    auto swap32 = [](float a, float b) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+        return rs_op<MAX>(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+    auto swap16 = [](float a, float b) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+        return rs_op<MAX>(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    };
+    const float u0 = swap32(v[0], v[1]), u1 = swap32(v[2], v[3]);
+    const float u2 = swap32(v[4], v[5]), u3 = swap32(v[6], v[7]);
+    const float t0 = swap16(u0, u1), t1 = swap16(u2, u3);
+    const float keep = upper8 ? t1 : t0, send = upper8 ? t0 : t1;
+    const int sw = __builtin_amdgcn_update_dpp(0, __float_as_int(send), 0x128, 0xF, 0xF, true);  // row_ror:8
+    float r = rs_op<MAX>(keep, __int_as_float(sw));
+    r = dpp_op_row<MAX, 0x141>(r);  // row_half_mirror
+    r = dpp_op_row<MAX, 0x1B>(r);   // quad_perm [3,2,1,0]
+    r = dpp_op_row<MAX, 0xB1>(r);   // quad_perm [1,0,3,2]
+    return r;
+}
+
+// CONTRIB: a lane's prefetch of the splat at list position pos -- the record as the plain forward loads it, plus its bin rect (the whole third float4)
+// and from it the instance's slot, as k_composite_bwd's stage() forms it
+template <bool EXTRA>
+__device__ __forceinline__ void contrib_fetch(const GsrSplat *__restrict__ splats, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ goff,
+                                              const uint32_t *__restrict__ gpart, int bin_x, int bin_y, uint32_t pos, float4 &nA, float4 &nB, float &nC,
+                                              float &nD, uint32_t &nRec) {
+    const uint32_t id = point_list[pos];
+    const float4 *s = reinterpret_cast<const float4 *>(splats + id);
+    nA = s[0]; nB = s[1];
+    const float4 c = s[2];
+    nC = c.x;
+    if (EXTRA) nD = c.y;
+    const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
+    const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
+    nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+}
+
 // EXTRA: the opt-in depth and alpha maps (GsrViewExt.out_depth / out_alpha) -- two more channels of the same blend, background 0:
 // depth = sum z_i alpha_i T_i (z_i = the view-space depth in the splat record's `depth` slot), alpha = sum alpha_i T_i.  The record already carries
 // z next to b, so the gather is the same 48-byte record; only one LDS word per staged splat and two accumulators are added.
-template <bool EXTRA>
+// CONTRIB: the per-instance contribution statistics (GsrContrib) -- for every staged splat the sum and the max of its 64 weights w = alpha T and the
+// number of pixels it is blended into.  The count is the popcount of the blended-lane ballot (scalar), selected into lane j of a register; the sum and
+// max go through wave_reduce_scatter8 once per blend group of eight splats and are parked in LDS.  Once per round lane j writes staged splat j's
+// {sum, max, count, 0} to inst_contrib[slot] -- the instance's Gaussian-major slot, as the backward's records -- if the splat was blended anywhere.
+// Slots nobody writes (not walked, nothing blended, bin-rect cells outside the list) were zeroed by k_contrib_clear in front of this launch.
+template <bool EXTRA, bool CONTRIB = false>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
                                                        float *__restrict__ out_color, float *__restrict__ final_T,
                                                        uint32_t *__restrict__ n_contrib, const GsrHeader *__restrict__ hdr, uint8_t *__restrict__ inst_valid,
-                                                       float *__restrict__ out_depth, float *__restrict__ out_alpha) {
+                                                       float *__restrict__ out_depth, float *__restrict__ out_alpha,
+                                                       const uint32_t *__restrict__ goff = nullptr, const uint32_t *__restrict__ gpart = nullptr,
+                                                       float4 *__restrict__ inst_contrib = nullptr) {
     __shared__ float4 sA[WAVES][WAVE];
     __shared__ float4 sB[WAVES][WAVE];
     __shared__ float sC[WAVES][WAVE];
     __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
+    __shared__ float sS[WAVES][CONTRIB ? WAVE : 1], sM[WAVES][CONTRIB ? WAVE : 1];  // CONTRIB: per staged splat, the wave sum and max of w
     const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
     const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
     if (hdr->overflow) {  // nothing can be rendered from truncated lists: a deterministic zero image instead of uninitialised memory
@@ -66,7 +128,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
 
     float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
     float nC = 0.f, nD = 0.f;
-    if (r0 + g.lane < r1) {  // prefetch round 0
+    uint32_t nRec = 0;  // CONTRIB: the slot of this lane's prefetched instance (k_composite_bwd's stage())
+    if constexpr (CONTRIB) {
+        if (r0 + g.lane < r1) contrib_fetch<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, r0 + g.lane, nA, nB, nC, nD, nRec);  // prefetch round 0
+    } else if (r0 + g.lane < r1) {  // prefetch round 0
         const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[r0 + g.lane]);
         nA = s[0]; nB = s[1]; nC = s[2].x;
         if (EXTRA) nD = s[2].y;
@@ -78,21 +143,26 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
         wB[g.lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
         wC[g.lane] = nC;
         if (EXTRA) wD[g.lane] = nD;
+        const uint32_t curRec = nRec;
         wave_sync_lds();
         const uint32_t nk = base + WAVE + g.lane;
         nB.y = 0.f;  // a slot without a splat blends nothing (opacity 0 -> alpha 0 < 1/255; stale x, y, conic stay finite)
-        if (nk < r1) {  // prefetch the next round while this one is blended
+        if constexpr (CONTRIB) {
+            if (nk < r1) contrib_fetch<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, nk, nA, nB, nC, nD, nRec);  // prefetch the next round
+        } else if (nk < r1) {  // prefetch the next round while this one is blended
             const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[nk]);
             nA = s[0]; nB = s[1]; nC = s[2].x;
             if (EXTRA) nD = s[2].y;
         }
         const int cnt = (int)min((uint32_t)WAVE, r1 - base);
+        uint32_t n_blend = 0;  // CONTRIB: lane j = the number of pixels staged splat j was blended into (0 for a group that was not walked)
         // Branch-free blend in groups of 8 (the tail group is padded by opacity-0 slots; 4 and 16 measured slower); between groups one
         // scalar test stops the round as soon as all 64 pixels are saturated -- on average half a round (~8 % of a body bin's list) is
         // not walked at all
 #pragma unroll
         for (int j0 = 0; j0 < WAVE; j0 += 8) {
             if (j0 < cnt && active != 0ull) {
+                float wv[8];  // CONTRIB: the group's weights
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     const int j = j0 + u;
@@ -115,13 +185,31 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                         CD += wD[j] * w;  // the same contraction as a colour channel: fma(z, w, CD)
                         CA += w;          // alpha as the sum of the weights (its gradient then follows the colour recurrence), not 1 - T
                     }
+                    if constexpr (CONTRIB) {
+                        wv[u] = w;
+                        const uint32_t nb = (uint32_t)__builtin_popcountll(valid & ~sat);  // (scalar)
+                        n_blend = __builtin_amdgcn_inverse_ballot_w64(1ull << j) ? nb : n_blend;  // lane j takes it
+                    }
                     T = use ? test_T : T;
                     last_rnd = use ? (uint32_t)(j + 1) : last_rnd;
+                }
+                if constexpr (CONTRIB) {
+                    const bool upper8 = (g.lane & 8) != 0;
+                    const float ws = wave_reduce_scatter8<false>(wv, upper8), wm = wave_reduce_scatter8<true>(wv, upper8);
+                    if ((g.lane & 7) == 0) {
+                        const int k = j0 + acc_slot(g.lane);
+                        sS[g.wid][k] = ws;
+                        sM[g.wid][k] = wm;
+                    }
                 }
             }
         }
         last = last_rnd ? (base - r0) + last_rnd : last;
         last_rnd = 0;
+        if constexpr (CONTRIB) {
+            wave_sync_lds();
+            if (n_blend != 0u) inst_contrib[curRec] = make_float4(sS[g.wid][g.lane], sM[g.wid][g.lane], __uint_as_float(n_blend), 0.f);
+        }
     }
     if (g.inside) {
         const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
@@ -770,6 +858,48 @@ __global__ __launch_bounds__(256) void k_feature_grad_gather(int P, int F, const
     dL_dfeatures[r * F + c] = sum;
 }
 
+// Contribution statistics: the tail's slots [0, num_slots) are zeroed in front of the CONTRIB forward -- a slot no staged splat writes (not walked
+// before its bin saturated, blended into no pixel, or a bin-rect cell outside the Gaussian's lists) must read as empty.  It cannot be the forward's
+// own job like clear_record_flags: there another workgroup's record could land before the clearing one.  An overflowed view is left alone (its slot
+// count may exceed the capacity the tail was sized for; the gather writes zeros for it).
+__global__ __launch_bounds__(256) void k_contrib_clear(float4 *__restrict__ inst_contrib, const GsrHeader *__restrict__ hdr) {
+    if (hdr->overflow) return;
+    const uint32_t n = hdr->num_slots;
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n; k += gridDim.x * 256u) inst_contrib[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Contribution statistics, second half: each Gaussian's slots streamed in slot order (k_preprocess_bwd's slot range) into weight_sum / weight_max /
+// pixel_count[row]; one thread per Gaussian.  A fixed summation order and no atomics: the same bits on every run.  Culled Gaussians and every
+// Gaussian of an overflowed view get exact zeros; rows outside the view are not written; a NULL output is skipped.
+__global__ __launch_bounds__(256) void k_contrib_gather(int P, const uint32_t *__restrict__ row_range, const int *__restrict__ radii,
+                                                        const uint32_t *__restrict__ goff, const uint32_t *__restrict__ gpart,
+                                                        const float4 *__restrict__ inst_contrib, const GsrHeader *__restrict__ hdr,
+                                                        float *__restrict__ weight_sum, float *__restrict__ weight_max, int32_t *__restrict__ pixel_count) {
+    uint32_t row0;
+    int nP;
+    gsr_view_rows(row_range, P, row0, nP);
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= nP) return;
+    const size_t r = (size_t)row0 + (size_t)i;
+    float sum = 0.f, mx = 0.f;
+    uint32_t n = 0u;
+    if (hdr->overflow == 0u && radii[r] > 0) {
+        const int gb = i >> GSR_BIN_SHIFT;
+        const uint32_t gbase = gpart[gb];
+        const uint32_t s0 = gbase + goff[i];
+        const uint32_t s1 = ((i & (GSR_BIN_THREADS - 1)) != GSR_BIN_THREADS - 1 && i + 1 < P) ? gbase + goff[i + 1] : ((gb + 1) * GSR_BIN_THREADS < P ? gpart[gb + 1] : hdr->num_slots);
+        for (uint32_t k = s0; k < s1; k++) {
+            const float4 v = inst_contrib[k];
+            sum += v.x;
+            mx = fmaxf(mx, v.y);
+            n += __float_as_uint(v.z);
+        }
+    }
+    if (weight_sum) weight_sum[r] = sum;
+    if (weight_max) weight_max[r] = mx;
+    if (pixel_count) pixel_count[r] = (int32_t)n;
+}
+
 }  // namespace
 
 void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
@@ -859,4 +989,30 @@ void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, con
     if (n <= 0) return;
     hipLaunchKernelGGL(k_feature_grad_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, F, row_range, radii, goff, gpart, inst_valid, inst_dfeat, hdr,
                        dL_dfeatures);
+}
+
+void gsr_launch_contrib_clear(float4 *inst_contrib, int64_t cap, const GsrHeader *hdr, hipStream_t s) {
+    const int64_t blocks = (cap + 255) / 256;
+    hipLaunchKernelGGL(k_contrib_clear, dim3((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, inst_contrib, hdr);
+}
+
+void gsr_launch_composite_fwd_contrib(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                      const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
+                                      const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const uint32_t *goff,
+                                      const uint32_t *gpart, float4 *inst_contrib, hipStream_t s) {
+    const int wgs = (bx / WAVES) * by;
+    if (wgs <= 0) return;
+    if (out_depth || out_alpha)
+        hipLaunchKernelGGL((k_composite_fwd<true, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
+                           out_color, final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha, goff, gpart, inst_contrib);
+    else
+        hipLaunchKernelGGL((k_composite_fwd<false, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
+                           out_color, final_T, n_contrib, hdr, inst_valid, nullptr, nullptr, goff, gpart, inst_contrib);
+}
+
+void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const float4 *inst_contrib,
+                               const GsrHeader *hdr, float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_contrib_gather, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, row_range, radii, goff, gpart, inst_contrib, hdr, weight_sum,
+                       weight_max, pixel_count);
 }

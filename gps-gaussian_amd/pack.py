@@ -142,3 +142,11 @@ def pack_features(data, key, row_of_pixel, views=VIEWS):
     cap = rows.numel()
     dest = torch.where(rows >= 0, rows, cap + torch.arange(cap, device=rows.device))
     return src.new_zeros((2 * cap, F)).index_copy(0, dest, src)[:cap]
+
+
+def unpack_rows(values, row_of_pixel):
+    """values [rows] in pack_views' row order (a per-Gaussian quantity of the packed batch) -> [B, len(views), S2]: every pixel gets its row's
+    value, a pixel whose pts_valid is false gets 0.  Torch index ops on the device: no host synchronisation."""
+    rows = row_of_pixel.to(torch.int64)
+    vals = values[rows.clamp(min=0)]
+    return torch.where(rows >= 0, vals, torch.zeros((), dtype=values.dtype, device=values.device))

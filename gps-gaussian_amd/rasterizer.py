@@ -488,7 +488,7 @@ def _features(features, N, dev):
 
 def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, needs_grad, out_color=None, rows=None,
                   radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None, antialiasing=False,
-                  features=None, out_feat=None, feat_grad=True):
+                  features=None, out_feat=None, feat_grad=True, contrib=False, out_contrib=None):
     """One view's forward through the C-ABI (capacity policy, early notification, overflow repair).  `ctx` is any attribute holder: the
     autograd ctx of _RasterizeGaussians, or a plain namespace when a caller drives several views itself (render_api._RenderBatch).
     Leaves on it: raster_settings, cap, family, extra_flags, rows, saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
@@ -503,8 +503,11 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     sqrt(det(cov2D) / det(cov2D + 0.3 I)) (include/gpsgs.h), carried to the backward in ctx.  features [P, F] (1 <= F <= 64): also render the
     feature map [F,H,W] = sum_i f_i alpha_i T_i, background 0, with the VALU family (include/gpsgs.h GsrFeatures); out_feat: optional preallocated
     contiguous fp32 [F,H,W] tensor for it; feat_grad=False: the backward will not form dL/dfeatures (the workspace gets no feature tail).  The
-    feature array is appended to ctx.saved.
-    -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W]); with features the feature map is appended last"""
+    feature array is appended to ctx.saved.  contrib: also the per-Gaussian contribution statistics (include/gpsgs.h GsrContrib), weight_sum,
+    weight_max fp32 [P] and pixel_count int32 [P], with the VALU family; not with features.  out_contrib: optional three preallocated contiguous
+    tensors for them -- a row-range view's are REQUIRED and batch-wide (its rows are written).
+    -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W]); with features the feature map is appended last; with contrib
+    the three statistics after everything else"""
     rs = raster_settings
     lib = _capi.lib()
     if not means3D.is_cuda:
@@ -536,6 +539,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
         raise RuntimeError("all per-Gaussian inputs must have num_points rows")
     appear = (sh, int(rs.sh_degree), campos, cov, None, None) if (sh is not None or cov is not None) else None
     fea = _features(features, N, dev) if features is not None else None
+    if contrib and fea is not None:
+        raise RuntimeError("gps_gaussian_amd: the contribution statistics cannot be combined with features in one call")
     view = _cam(rs.viewmatrix, 16, dev)
     proj = _cam(rs.projmatrix, 16, dev)
     bg = _cam(rs.bg, 3, dev)
@@ -544,8 +549,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     st = _dev_state(dev)
     mode = _check_mode()
     family = _composite_flag() | (_wave_priority_flag(st, torch._C._cuda_getCurrentRawStream(dev.index), deterministic=(mode == "none")) if rows is None else 0)
-    if depth_alpha or fea is not None:
-        family = 0  # the depth / alpha and feature maps are made by the VALU kernels (forward and backward of a view must agree on the family)
+    if depth_alpha or fea is not None or contrib:
+        family = 0  # the depth / alpha and feature maps and the statistics are made by the VALU kernels (forward and backward must agree on it)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
     base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family | (_capi.GSR_FLAG_ANTIALIAS if antialiasing else 0)
     if mode != "none" and torch.cuda.is_current_stream_capturing():
@@ -576,6 +581,20 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
                 raise RuntimeError("gps_gaussian_amd: out_feat must be a contiguous fp32 [F, H, W] tensor on the inputs' device")
             feat = _capi.GsrFeatures()
             feat.channels, feat.features, feat.out_features = F, fea.data_ptr(), fmap.data_ptr()
+        cstats = cst = None
+        if contrib:
+            if out_contrib is None:
+                if rows is not None:
+                    raise RuntimeError("gps_gaussian_amd: a row-range view needs its batch-wide statistics arrays (out_contrib)")
+                cstats = (torch.empty((N,), dtype=torch.float32, device=dev), torch.empty((N,), dtype=torch.float32, device=dev),
+                          torch.empty((N,), dtype=torch.int32, device=dev))
+            else:
+                cstats = tuple(out_contrib)
+            if any(t.dtype is not dt or t.device != dev or t.numel() != N or not t.is_contiguous()
+                   for t, dt in zip(cstats, (torch.float32, torch.float32, torch.int32))):
+                raise RuntimeError("gps_gaussian_amd: out_contrib must be contiguous [rows] tensors (fp32, fp32, int32) on the inputs' device")
+            cst = _capi.GsrContrib()
+            cst.weight_sum, cst.weight_max, cst.pixel_count = (t.data_ptr() for t in cstats)
         if rows is None:
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
         else:
@@ -593,7 +612,9 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
 
         def launch(cap, bin_cap, plan_flags):
             """Enqueue the whole forward (one _plan).  -> (notify note or None, cap, bin_cap)"""
-            if feat is not None and feat_grad and not fwd_only:  # the per-slot feature sums need the feature tail
+            if cst is not None:  # the statistics need the slot prefix of the backward tail and the contribution tail (also for inference)
+                nbytes = lib.gsr_workspace_bytes_contrib(P, W, H, cap, bin_cap, fwd_only)
+            elif feat is not None and feat_grad and not fwd_only:  # the per-slot feature sums need the feature tail
                 nbytes = lib.gsr_workspace_bytes_features(P, W, H, cap, bin_cap, feat.channels, fwd_only)
             else:
                 nbytes = (lib.gsr_workspace_bytes_depth_alpha if depth_alpha else lib.gsr_workspace_bytes_ex)(P, W, H, cap, bin_cap, fwd_only)
@@ -604,11 +625,16 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
             args = (P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier), float(rs.tanfovx),
                     float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(color), _ptr(radii), _ptr(ws), nbytes, cap,
                     base_flags | plan_flags, stream, hdr_ptr, note[3] if note is not None else 0, C.byref(ext))
-            # (every attempt, the repair included, writes the feature map too)
-            rc = lib.gsr_forward_ex(*args) if feat is None else lib.gsr_forward_features(*args, C.byref(feat))
+            # (every attempt, the repair included, writes the feature map and the statistics too)
+            if cst is not None:
+                rc, what = lib.gsr_forward_contrib(*args, C.byref(cst)), "gsr_forward_contrib"
+            elif feat is not None:
+                rc, what = lib.gsr_forward_features(*args, C.byref(feat)), "gsr_forward_features"
+            else:
+                rc, what = lib.gsr_forward_ex(*args), "gsr_forward_ex"
             if rc != 0 and note is not None:
                 ring.release(note[1])
-            _capi.check(rc, "gsr_forward_ex" if feat is None else "gsr_forward_features")
+            _capi.check(rc, what)
             box[:] = ws, cap, bin_cap
             return note, cap, bin_cap
 
@@ -653,8 +679,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
     if fea is not None:
         ctx.saved = ctx.saved + (fea,)
-    out = (color, radii) + ((dmaps[0], dmaps[1]) if depth_alpha else ())
-    return out + (fmap,) if fea is not None else out
+    out = (color, radii) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmap,) if fea is not None else ())
+    return out + cstats if contrib else out
 
 
 def _map_grad(g):
@@ -841,7 +867,8 @@ def _cam_grad_as(g, t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None, features=None):
+                return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None, features=None,
+                return_contrib=False):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
@@ -855,24 +882,27 @@ class _RasterizeGaussians(torch.autograd.Function):
         # features [P, F]: the feature map is appended to the outputs, dL/dfeatures is formed only when they require a gradient
         ctx.return_depth_alpha = bool(return_depth_alpha)
         ctx.has_features = features is not None
+        # return_contrib: the three per-Gaussian statistics are appended last, not differentiable (like radii)
+        ctx.n_contrib_out = 3 if return_contrib else 0
         out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
                             shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha), antialiasing=antialiasing,
-                            features=features, feat_grad=features is not None and ctx.needs_input_grad[16])
+                            features=features, feat_grad=features is not None and ctx.needs_input_grad[16], contrib=bool(return_contrib))
         if _debug_keep_ws:
             _tls.last_ws = dict(ws=ctx.saved[9], cap=ctx.cap, bin_cap=ctx.bin_cap)
         ctx.save_for_backward(*ctx.saved)
         ctx.saved = None
-        ctx.mark_non_differentiable(out[1])
+        ctx.mark_non_differentiable(out[1], *out[len(out) - ctx.n_contrib_out:])
         ctx.set_materialize_grads(False)  # otherwise autograd fills a zero int32 [P] "gradient" for radii on every backward
         return out
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, *grad_maps):
-        # grad_maps: (dL/ddepth, dL/dalpha) with return_depth_alpha, then dL/dfeaturemap with features
+        # grad_maps: (dL/ddepth, dL/dalpha) with return_depth_alpha, then dL/dfeaturemap with features, then three Nones for the statistics
+        grad_maps = grad_maps[:len(grad_maps) - ctx.n_contrib_out]
         grad_depth, grad_alpha = grad_maps[:2] if ctx.return_depth_alpha else (None, None)
         grad_feat = grad_maps[-1] if ctx.has_features else None
         if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_feat is None:  # no output took part in the loss
-            return (None,) * 17
+            return (None,) * 18
         saved = ctx.saved_tensors
         cam_out = None
         if ctx.camera_grad:
@@ -888,11 +918,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha,
         #  antialiasing, camera_grad, viewmatrix, projmatrix, campos)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None, None, None, None) + d_cam + (d_feat,)
+                d_cov, None, None, None, None, None) + d_cam + (d_feat, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None):
+                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
     and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
@@ -901,7 +931,17 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     dL/d(itself) in its own shape, dtype and device (include/gpsgs.h gsr_backward_camera; without the keyword they are constants, as upstream).
     features [P, F] (1 <= F <= 64, on means3D's device): also returns the feature map [F,H,W] = sum_i f_i alpha_i T_i, background 0, LAST --
     (color, radii, feat) or (color, radii, depth, alpha, feat) -- rendered by the VALU kernels with the image's blend weights, differentiable in
-    the features and, through the weights, in the geometry (include/gpsgs.h GsrFeatures)."""
+    the features and, through the weights, in the geometry (include/gpsgs.h GsrFeatures).
+    return_contrib=True: also returns the per-Gaussian contribution statistics LAST -- contrib_weight (fp32 [P], the sum over pixels of the blend
+    weight alpha T), contrib_max (fp32 [P], its maximum) and contrib_pixels (int32 [P], the pixels the Gaussian is blended into) -- from the image's
+    own blend (the VALU kernels; zeros for culled Gaussians and for a view that overflowed unrepaired), not differentiable, bitwise reproducible
+    (include/gpsgs.h GsrContrib).  Combines with everything above except features (RuntimeError before anything is launched)."""
+    if return_contrib:
+        rs = raster_settings
+        cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos)) if camera_grad else (None, None, None)
+        aa = bool(antialiasing) or bool(getattr(rs, "antialiasing", False))
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, bool(return_depth_alpha), aa, bool(camera_grad), *cams, features, True)
     if features is not None:
         rs = raster_settings
         cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos)) if camera_grad else (None, None, None)
@@ -933,7 +973,7 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None):
+                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
@@ -941,7 +981,7 @@ class GaussianRasterizer(nn.Module):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         antialiasing = antialiasing or getattr(self.raster_settings, "antialiasing", False)
         if (shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing and not camera_grad
-                and features is None):
+                and features is None and not return_contrib):
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -951,9 +991,9 @@ class GaussianRasterizer(nn.Module):
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
         # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing and camera_grad: the Python host path (not
         # the compiled one)
-        # features [P, F]: the feature map is appended to the outputs (rasterize_gaussians)
+        # features [P, F]: the feature map is appended to the outputs; return_contrib: the three statistics after it (rasterize_gaussians)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad, features)
+                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad, features, return_contrib)
 
 
     def markVisible(self, positions):

@@ -102,13 +102,14 @@ class _RenderBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False, camera_grad=False,
-                view_all=None, proj_all=None, campos_all=None, features=None):
+                view_all=None, proj_all=None, campos_all=None, features=None, contrib=False):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
         # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
         # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS;
         # camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds them) get
         # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True)); features: packed [N, F] (pack.pack_features), the
-        # feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...))
+        # feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...)); contrib: then the per-Gaussian statistics
+        # weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its rows)
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
@@ -117,6 +118,8 @@ class _RenderBatch(torch.autograd.Function):
         fmaps = torch.empty((bs, features.shape[1], H, W), dtype=torch.float32, device=dev) if features is not None else None
         feat_grad = features is not None and ctx.needs_input_grad[14]
         radii = torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
+        cstats = (torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev), torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev),
+                  torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)) if contrib else None
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
         side = _streams(dev, bs) if (bs > 1 and not torch.cuda.is_current_stream_capturing()) else [cur] * bs
@@ -132,7 +135,7 @@ class _RenderBatch(torch.autograd.Function):
                                       rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
                                       out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None,
                                       antialiasing=antialiasing, features=features, out_feat=fmaps[i] if fmaps is not None else None,
-                                      feat_grad=feat_grad)
+                                      feat_grad=feat_grad, contrib=bool(contrib), out_contrib=cstats)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -154,16 +157,21 @@ class _RenderBatch(torch.autograd.Function):
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
         ctx.depth_alpha, ctx.has_features, ctx.feat_grad = bool(depth_alpha), features is not None, feat_grad
         ctx.feat_shape = tuple(features.shape) if features is not None else None
+        ctx.n_contrib_out = 3 if contrib else 0
         ctx.set_materialize_grads(False)
         outs = (out,) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmaps,) if fmaps is not None else ())
+        if cstats is not None:
+            ctx.mark_non_differentiable(*cstats)
+            outs = outs + cstats
         return outs if len(outs) > 1 else out
 
     @staticmethod
     def backward(ctx, gout, *gmaps):
+        gmaps = gmaps[:len(gmaps) - ctx.n_contrib_out]  # (the statistics are not differentiable)
         gdepth, galpha = gmaps[:2] if ctx.depth_alpha else (None, None)
         gfeat = gmaps[-1] if ctx.has_features else None
         if gout is None and gdepth is None and galpha is None and gfeat is None:
-            return (None,) * 15
+            return (None,) * 16
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
@@ -197,7 +205,7 @@ class _RenderBatch(torch.autograd.Function):
         d_cam = (None, None, None)
         if cam_all is not None:
             d_cam = tuple(_RZ._cam_grad_as(c, t) for c, t in zip(cam_all, ctx.cams))
-        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat,)
+        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat, None)
 
 
 def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
@@ -225,24 +233,29 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
 
 
 def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False,
-              features=None):
+              features=None, contrib=False):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
     The image is what render() returns up to the compositing family: the maps come from the VALU kernels, render() uses GPSGS_COMPOSITE.
     antialiasing=True: as render()'s; the maps then see the filtered opacities too.  camera_grad=True: as render()'s, the maps' gradients
     included.  features [P, F] (1 <= F <= 64): also 'feat' [F,H,W] = sum_i f_i alpha_i T_i, background 0 (for a feature background add
-    (1 - alpha) bg_f), differentiable in the features and the geometry (rasterizer.rasterize_gaussians)."""
+    (1 - alpha) bg_f), differentiable in the features and the geometry (rasterizer.rasterize_gaussians).  contrib=True: also the per-Gaussian
+    contribution statistics of the view, 'contrib_weight' (fp32 [P], sum over pixels of alpha T), 'contrib_max' (fp32 [P], its maximum) and
+    'contrib_pixels' (int32 [P], pixels blended into), not differentiable (rasterizer.rasterize_gaussians(return_contrib=True)); not with
+    features."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
     out = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
-                     camera_grad=camera_grad, features=features)
+                     camera_grad=camera_grad, features=features, return_contrib=contrib)
     r = {'img': out[0], 'depth': out[2], 'alpha': out[3]}
     if features is not None:
         r['feat'] = out[4]
+    if contrib:
+        r['contrib_weight'], r['contrib_max'], r['contrib_pixels'] = out[-3:]
     return r
 
 
@@ -263,7 +276,21 @@ def _to_device_once(t, dev):
     return t
 
 
-def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None):
+_CONTRIB_KEYS = ('contrib_weight', 'contrib_max', 'contrib_pixels')
+
+
+def _write_contrib_maps(data, stats, row_of_pixel):
+    """The packed rows' statistics -> data[view][key] [B,1,H,W] for lmain and rmain (pack.unpack_rows: device index ops, no host sync)."""
+    from .pack import VIEWS, unpack_rows
+
+    for key, vals in zip(_CONTRIB_KEYS, stats):
+        maps = unpack_rows(vals, row_of_pixel)
+        for v, view in enumerate(VIEWS):
+            H, W = int(data[view]['img'].shape[2]), int(data[view]['img'].shape[3])
+            data[view][key] = maps[:, v].reshape(-1, 1, H, W)
+
+
+def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None, with_contrib=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
     antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
@@ -272,6 +299,9 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     feature_key (opt-in): data['lmain'][feature_key] and data['rmain'][feature_key], each [B,F,H,W] (1 <= F <= 64), are packed with the
     same validity mask and row order as 'img' (pack.pack_features: torch index ops, no host sync) and splatted with the image's blend weights:
     'feat_pred' [B,F,H,W] (render_ex(features=...)), differentiable back to the per-view maps.
+    with_contrib=True (opt-in): every Gaussian's contribution statistics in the novel view (render_ex(contrib=True)) go back to the source pixel it
+    came from -- data['lmain'] and data['rmain'] get 'contrib_weight', 'contrib_max' (fp32) and 'contrib_pixels' (int32), each [B,1,H,W], 0 where
+    pts_valid is false.  Not differentiable; not with feature_key (RuntimeError before anything is launched).
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -282,8 +312,12 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     from .pack import pack_views
 
     bs = data['lmain']['img'].shape[0]
-    feats = None
-    if feature_key is None:
+    feats = row_of_pixel = None
+    if with_contrib and feature_key is not None:
+        raise RuntimeError("gps_gaussian_amd: with_contrib cannot be combined with feature_key")
+    if with_contrib:
+        xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
+    elif feature_key is None:
         xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
     else:
         from .pack import pack_features
@@ -296,7 +330,15 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        if feats is not None:
+        if with_contrib:
+            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
+                                     bool(camera_grad), *cams, None, True)
+            nv['img_pred'] = out[0]
+            if with_depth_alpha:
+                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
+            _write_contrib_maps(data, out[-3:], row_of_pixel)
+        elif feats is not None:
             cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
             out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
                                      bool(camera_grad), *cams, feats)
@@ -320,11 +362,13 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         else:
             nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad, feats)
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad, feats,
+                            row_of_pixel if with_contrib else None)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None):
-    """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream."""
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None, row_of_pixel=None):
+    """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream.  row_of_pixel (pack_views'): the
+    contribution statistics are wanted (pts2render(with_contrib=True))."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
     # ONE split per packed tensor (its backward is one concatenation of the per-sample gradients); B Python slices would make
@@ -356,10 +400,12 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
             if side[i] is not cur:
                 side[i].wait_stream(cur)
             with torch.cuda.stream(side[i]):
-                if with_depth_alpha or feats is not None:
+                if with_depth_alpha or feats is not None or row_of_pixel is not None:
                     r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
-                                  antialiasing=antialiasing, camera_grad=camera_grad, features=f_parts[i] if feats is not None else None)
-                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha') + (('feat',) if feats is not None else ())))
+                                  antialiasing=antialiasing, camera_grad=camera_grad, features=f_parts[i] if feats is not None else None,
+                                  contrib=row_of_pixel is not None)
+                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha') + (('feat',) if feats is not None else ()))
+                               + (tuple(r[k] for k in _CONTRIB_KEYS) if row_of_pixel is not None else ()))
                 else:
                     out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
                                        grad_arena=ga, antialiasing=antialiasing, camera_grad=camera_grad).unsqueeze(0),))
@@ -375,6 +421,10 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
         nv['alpha_pred'] = torch.cat([o[2] for o in out], dim=0)
     if feats is not None:
         nv['feat_pred'] = torch.cat([o[3] for o in out], dim=0)
+    if row_of_pixel is not None:  # the samples' statistics in packed row order (rows behind offs[bs] are never looked up: zeros)
+        tail = xyz.shape[0] - offs[bs]
+        stats = [torch.cat([o[-3 + k] for o in out] + [out[0][-3 + k].new_zeros((tail,))]) for k in range(3)]
+        _write_contrib_maps(data, stats, row_of_pixel)
     return data
 
 

@@ -52,7 +52,8 @@ extern "C" {
                                still 4 after the depth / alpha maps: GsrViewExt.reserved[4] became two pointer slots (out_depth | dL_ddepth,
                                   out_alpha | dL_dalpha; zero = none, what 4 did, same 80-byte struct) + gsr_workspace_bytes_depth_alpha
                                still 4 after the feature maps: GsrFeatures, gsr_workspace_bytes_features, gsr_forward_features,
-                                  gsr_backward_features (additive) */
+                                  gsr_backward_features (additive)
+                               still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -316,6 +317,35 @@ int gsr_backward_features(int P, int width, int height, const float *means3D, co
                           size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                           float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                           const GsrFeatures *feat);
+
+/* Per-Gaussian contribution statistics (opt-in).  A (pixel p, Gaussian i) pair is BLENDED when the forward adds i's colour to p -- the image's
+ * splats, sort order and power > 0 / alpha < 1/255 / T < 1e-4 decisions -- with the weight w(p, i) = alpha T that the image, the depth / alpha and
+ * the feature maps use (alpha from the compensated opacity with GSR_FLAG_ANTIALIAS).  Per Gaussian, indexed like radii:
+ *   weight_sum[i]  = sum_p w(p, i)       fp32
+ *   weight_max[i]  = max_p w(p, i), or 0 fp32
+ *   pixel_count[i] = #{p : (p, i) blended} int32
+ * Culled Gaussians (radii 0) and every Gaussian of an overflowed view get zeros.  Not differentiable.  No atomics: per (bin, splat) instance the
+ * forward keeps {sum, max, count} in the workspace's contribution tail, a gather streams each Gaussian's slots in slot order -- the same bits on every
+ * run.  Rendered by the VALU compositing family (the tiles flag is ignored for the view): the image, final T, the depth / alpha maps and what the
+ * backward reads have the bits of a plain VALU forward, so gsr_backward_ex on the same workspace gives the same gradients as without statistics.
+ * Each pointer may be NULL (not wanted); with a row range only the view's rows are written.  GPSGS_E_INVALID for pointers that are not 4-byte
+ * aligned or a non-NULL `reserved`; GPSGS_E_WORKSPACE for a workspace smaller than gsr_workspace_bytes_contrib (when any pointer is set).  Combines with the depth / alpha
+ * maps, antialiasing, shs, cov3D_precomp, row ranges and both list forms; not with feature maps (there is no entry point taking both). */
+typedef struct GsrContrib {
+    float *weight_sum;    /* DEVICE [rows] or NULL */
+    float *weight_max;    /* DEVICE [rows] or NULL */
+    int32_t *pixel_count; /* DEVICE [rows] or NULL */
+    void *reserved;       /* NULL */
+} GsrContrib;
+/* gsr_workspace_bytes_depth_alpha(..., 0) plus the 256-byte aligned contribution tail (instance_capacity x 16 bytes).  forward_only: the same size --
+ * the statistics need the per-Gaussian slot prefix of the backward tail, which the forward then also fills (such a forward counts the gradient-record
+ * slots against instance_capacity, as a training forward does).  0 on invalid arguments. */
+size_t gsr_workspace_bytes_contrib(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only);
+int gsr_forward_contrib(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                        const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                        const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                        void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                        void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrContrib *contrib);
 
 /* Visibility mask (upstream `_C.mark_visible`, reached through GaussianRasterizer.markVisible(positions) of the module the reference imports at
  * gaussian_renderer/__init__.py:14; the reference itself never calls it): present[i] = 1 iff point i passes the near-plane test of the forward
