@@ -189,6 +189,13 @@ extern "C" size_t gsr_workspace_bytes_contrib(int P, int width, int height, int6
     return L.total_extra + gsr_contrib_tail_bytes(instance_capacity);
 }
 
+extern "C" size_t gsr_workspace_bytes_absgrad(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity) {
+    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
+    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
+    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    return L.total_extra + gsr_absgrad_tail_bytes(instance_capacity);
+}
+
 namespace {
 // F-channel feature maps: the channel count of a GsrFeatures (0 = none), or -1 for an invalid one (range, NULL features for P > 0, misaligned pointers)
 int feature_channels(const GsrFeatures *feat, bool backward, int P) {
@@ -456,7 +463,7 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
                   const float *rotations, float scale_modifier, float tanfovx, float tanfovy, const float *viewmatrix, const float *projmatrix,
                   const float *bg, const int *radii, const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
                   float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes, int64_t instance_capacity,
-                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam, const GsrFeatures *feat = nullptr) {
+                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam, const GsrFeatures *feat = nullptr, const GsrAbsGrad *abs = nullptr) {
     (void)colors;  // already folded into the splat records of the workspace (so are the opacities -- read again only with antialiasing)
     const bool antialias = (flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
@@ -471,6 +478,12 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     const float *dL_dfeat = F > 0 ? feat->dL_dfeaturemap : nullptr;
     float *dL_dfeatures = F > 0 ? feat->dL_dfeatures : nullptr;
     const bool feat_sums = dL_dfeat && dL_dfeatures;  // the per-slot feature sums (part b) are formed
+    // absolute screen-space gradient: the VALU family's ABSGRAD kernels, 8 bytes per instance slot in the workspace's absgrad tail
+    if (abs && abs->reserved) return GPSGS_E_INVALID;
+    float2 *absgrad = abs ? reinterpret_cast<float2 *>(abs->absgrad) : nullptr;
+    if (reinterpret_cast<uintptr_t>(absgrad) & 3u) return GPSGS_E_INVALID;
+    if (absgrad && F > 0) return GPSGS_E_INVALID;  // (the two tails share an offset; no entry point passes both)
+    if (absgrad) flags &= ~GSR_FLAG_COMPOSITE_TILES;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
     if (P == 0) {
         if (cam) {  // nothing rendered: the camera gradients are zeros
@@ -494,6 +507,7 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
     if (workspace_bytes < (feat_sums ? L.total_extra + gsr_feature_tail_bytes(instance_capacity, F) : extras ? L.total_extra : L.total)) return GPSGS_E_WORKSPACE;
+    if (absgrad && workspace_bytes < L.total_extra + gsr_absgrad_tail_bytes(instance_capacity)) return GPSGS_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const GsrHeader *hdr = reinterpret_cast<const GsrHeader *>(at(workspace, L.header));
     const GsrBins bins = {reinterpret_cast<const uint32_t *>(at(workspace, L.bin_offset)), reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count)),
@@ -510,6 +524,7 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
     GsrGradAcc *inst_grad = reinterpret_cast<GsrGradAcc *>(at(workspace, L.inst_grad));
     float *inst_ddepth = extras ? reinterpret_cast<float *>(at(workspace, L.inst_ddepth)) : nullptr;
     float *inst_dfeat = feat_sums ? reinterpret_cast<float *>(at(workspace, L.total_extra)) : nullptr;
+    float2 *inst_absgrad = absgrad ? reinterpret_cast<float2 *>(at(workspace, L.total_extra)) : nullptr;  // (the contribution tail's place: dead by now)
     const uint32_t *row_range = ext ? ext->row_range : nullptr;
 
     // goff / gscan_part / cleared inst_valid were produced by the matching gsr_forward (training workspace)
@@ -525,6 +540,9 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
         else if (dL_dfeat)  // (a NULL feature-map gradient runs the plain kernel: the per-Gaussian gradients keep their bits)
             gsr_launch_composite_bwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop,
                                           inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, feat->features, F, row_range, dL_dfeat, inst_dfeat, s);
+        else if (absgrad)
+            gsr_launch_composite_bwd_absgrad(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop,
+                                             inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, inst_absgrad, s);
         else
             gsr_launch_composite_bwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
                                      dL_ddepth, dL_dalpha, inst_ddepth, s);
@@ -555,6 +573,12 @@ int backward_impl(int P, int width, int height, const float *means3D, const floa
         trace("feature_grad_gather", P, width, height, (long long)instance_capacity, flags);
         StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
         gsr_launch_feature_grad_gather(P, F, row_range, radii, goff, gscan_part, inst_valid, inst_dfeat, hdr, dL_dfeatures, s);
+    }
+    if (absgrad) {  // (the flags the compositing backward set are cleared only by the next forward's compositing launch)
+        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
+        trace("absgrad_gather", P, width, height, (long long)instance_capacity, flags);
+        StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
+        gsr_launch_absgrad_gather(P, row_range, radii, goff, gscan_part, inst_valid, inst_absgrad, hdr, absgrad, s);
     }
     return check(s, flags);
 }
@@ -591,6 +615,24 @@ extern "C" int gsr_backward_camera(int P, int width, int height, const float *me
     return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                          radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
                          instance_capacity, flags, stream, ext, want ? &cam : nullptr);
+}
+
+extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                    const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                    const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                                    const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                                    float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                                    int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                                    float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                                    const GsrAbsGrad *abs) {
+    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
+        return GPSGS_E_INVALID;
+    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
+    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
+    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
+                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
+                         instance_capacity, flags, stream, ext, want ? &cam : nullptr, nullptr, abs);
 }
 
 extern "C" int gsr_backward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,

@@ -44,6 +44,9 @@
 //   --- contribution tail (only in a workspace sized with gsr_workspace_bytes_contrib; every offset above is unchanged; never with a feature tail) ---
 //   inst_contrib[cap] 16 bytes per instance slot {sum of w, max of w, blended pixels (u32 bits), 0}, written by the CONTRIB forward for the instances
 //                  it blended anywhere and zero elsewhere (k_contrib_clear); independent of inst_valid, which stays the backward's
+//   --- absgrad tail (a workspace sized with gsr_workspace_bytes_absgrad or gsr_workspace_bytes_contrib; every offset above is unchanged) ---
+//   inst_absgrad[cap] 8 bytes per instance slot {sum_p |t_x|, sum_p |t_y|} at the contribution tail's offset (that tail is dead once the forward's
+//                  gather has run), written by the ABSGRAD backward for the slots whose inst_valid flag it sets
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -555,6 +558,18 @@ void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radi
                                const GsrHeader *hdr, float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s);
 // the contribution tail of a workspace: 16 bytes per instance slot, behind the depth / alpha tail (total_extra)
 static inline size_t gsr_contrib_tail_bytes(int64_t cap) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * 16); }
+// Absolute screen-space gradient (GsrAbsGrad; the VALU family only).  gsr_launch_composite_bwd_absgrad is gsr_launch_composite_bwd (the same records,
+// inst_dop, inst_ddepth and flags, bit for bit) plus {sum_p |t_x|, sum_p |t_y|} per record at its slot of inst_absgrad; gsr_launch_absgrad_gather sums
+// each Gaussian's flagged slots in slot order into absgrad [rows, 2] (zeros for culled Gaussians and an overflowed view).
+void gsr_launch_composite_bwd_absgrad(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                      const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
+                                      const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
+                                      GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
+                                      float2 *inst_absgrad, hipStream_t s);
+void gsr_launch_absgrad_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const uint8_t *inst_valid,
+                               const float2 *inst_absgrad, const GsrHeader *hdr, float2 *absgrad, hipStream_t s);
+// the absgrad tail of a training workspace: 8 bytes per instance slot, behind the depth / alpha tail (total_extra)
+static inline size_t gsr_absgrad_tail_bytes(int64_t cap) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * 8); }
 // development knob: GPSGS_DEBUG_LDS_PAD=<bytes> of unused dynamic LDS per compositing workgroup (caps the waves resident per CU, to
 // measure how the kernels scale with occupancy); 0 / unset in normal use
 #include <stdlib.h>

@@ -232,7 +232,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
 // c = z resp. c = 1 and background 0 would: cd gains z dL/ddepth + dL/dalpha, so dL/dalpha_i -- and with it dL/dopacity, dL/dconic, dL/dmean2D
 // -- folds into the existing record's sums.  The tenth per-(pixel, splat) term, dL/dz_i = sum_p w dL/ddepth, is row-reduced (4 DPP adds) beside
 // the nine-term reduce-scatter; its 4 row sums are parked in a fourth float4 per staged splat and flushed as inst_ddepth[slot] (no atomics).
-template <bool EXTRA>
+// ABSGRAD: the opt-in absolute screen-space gradient (GsrAbsGrad) -- per (pixel, splat) pair the magnitudes of the two terms whose signed sums are
+// dL/dmean2D, |s (A dx + B dy)| and |s (C dy + B dx)| with s = m_0.  Both go through ONE register: v_permlane32_swap folds the wave's halves (lanes
+// 0-31 then hold the x term, lanes 32-63 the y term; |.| is an input modifier of that add), four DPP adds make the row sums, and the two row sums per
+// component are parked in one more float4 per staged splat.  The flush lane adds them, scales by 0.5 W (2 / log2 e) resp. 0.5 H (2 / log2 e) once and
+// writes one float2 to inst_absgrad[slot], next to the record -- which, with inst_dop, inst_ddepth and the flag, is written exactly as without it.
+template <bool EXTRA, bool ABSGRAD = false>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
@@ -240,13 +245,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
                                                        const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ goff,
                                                        const uint32_t *__restrict__ gpart, uint8_t *__restrict__ inst_valid, float *__restrict__ inst_dop,
                                                        GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr,
-                                                       const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, float *__restrict__ inst_ddepth) {
-    constexpr int REC = EXTRA ? 4 : 3;  // float4s per staged splat in sAcc
+                                                       const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, float *__restrict__ inst_ddepth,
+                                                       float2 *__restrict__ inst_absgrad = nullptr) {
+    constexpr int AB = EXTRA ? 4 : 3;              // ABSGRAD: the float4 of the absolute sums
+    constexpr int REC = AB + (ABSGRAD ? 1 : 0);    // float4s per staged splat in sAcc
     __shared__ float4 sA[WAVES][WAVE];
     __shared__ float4 sB[WAVES][WAVE];
     __shared__ float sC[WAVES][WAVE];
     __shared__ float sD[WAVES][EXTRA ? WAVE : 1];
-    __shared__ float4 sAcc[WAVES][WAVE * REC];  // per staged splat: {dr,dg,db,dmx | dmy,cxx,cxy,cyy | 4 row sums of dop (| 4 row sums of dz)}
+    // per staged splat: {dr,dg,db,dmx | dmy,cxx,cxy,cyy | 4 row sums of dop (| 4 row sums of dz) (| 2 row sums of |t_x|, 2 of |t_y|)}
+    __shared__ float4 sAcc[WAVES][WAVE * REC];
     if (hdr->overflow) return;
     const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
     if (list_pos >= hdr->num_busy_wgs) return;  // idle workgroups sit at the end of wg_order
@@ -362,11 +370,23 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             const float m_xy = m_x * dy;
             const float m_yy = m_y * dy;
             const float red[9] = {g_r, g_g, g_b, m_x, m_y, m_xx, m_xy, m_yy, m_0};
+            float ra = 0.f;
+            if constexpr (ABSGRAD) {
+                // s (A dx + B dy) and s (C dy + B dx) up to the factor -2 / log2 e of the pre-scaled conic (applied at flush time); a lane the splat
+                // does not reach has m_0 = 0 and adds exact zeros.  (Formed in front of the reduce-scatter so that the two DPP chains interleave.)
+                const float hb = 0.5f * a.w;
+                const float tx = a.z * m_x + hb * m_y;
+                const float ty = b.x * m_y + hb * m_x;
+                ra = wave_row_sum(swap_absadd32(tx, ty));  // rows 0, 1: |t_x| of the row pairs (0, 2), (1, 3); rows 2, 3: |t_y|
+            }
             const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
             if (slot >= 0) wAccF[4 * REC * j + slot] = out;  // 12 lanes, 12 distinct words of this splat's record
             if (EXTRA) {
                 const float rz = wave_row_sum(w * dd);  // dL/dz share of this pixel: w dL/ddepth
                 if ((lane & 15) == 7) wAccF[4 * REC * j + 12 + (lane >> 4)] = rz;
+            }
+            if constexpr (ABSGRAD) {
+                if ((lane & 15) == 7) wAccF[4 * REC * j + 4 * AB + (lane >> 4)] = ra;
             }
         }
         wave_sync_lds();
@@ -388,6 +408,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             if (EXTRA) {
                 const float4 rz = wAcc[REC * lane + 3];
                 inst_ddepth[curRec] = (rz.x + rz.y) + (rz.z + rz.w);
+            }
+            if constexpr (ABSGRAD) {  // in the units of g_mx / g_my (NDC-scaled); a fixed order, never negative
+                const float4 ab = wAcc[REC * lane + AB];
+                inst_absgrad[curRec] = make_float2(ddelx_dx * (kA * (ab.x + ab.y)), ddely_dy * (kA * (ab.z + ab.w)));
             }
             inst_valid[curRec] = 1;
         }
@@ -900,6 +924,36 @@ __global__ __launch_bounds__(256) void k_contrib_gather(int P, const uint32_t *_
     if (pixel_count) pixel_count[r] = (int32_t)n;
 }
 
+// Absolute screen-space gradient, second half: each Gaussian's FLAGGED slots (the records the backward compositing launch just wrote) streamed in slot
+// order (k_preprocess_bwd's slot range) into absgrad[row]; one thread per Gaussian, a fixed summation order, no atomics.  Culled Gaussians, Gaussians
+// without a record and every Gaussian of an overflowed view (whose backward wrote nothing: the flags are not looked at) get exact zeros; rows outside
+// the view are not written.
+__global__ __launch_bounds__(256) void k_absgrad_gather(int P, const uint32_t *__restrict__ row_range, const int *__restrict__ radii,
+                                                        const uint32_t *__restrict__ goff, const uint32_t *__restrict__ gpart,
+                                                        const uint8_t *__restrict__ inst_valid, const float2 *__restrict__ inst_absgrad,
+                                                        const GsrHeader *__restrict__ hdr, float2 *__restrict__ absgrad) {
+    uint32_t row0;
+    int nP;
+    gsr_view_rows(row_range, P, row0, nP);
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= nP) return;
+    const size_t r = (size_t)row0 + (size_t)i;
+    float ax = 0.f, ay = 0.f;
+    if (hdr->overflow == 0u && radii[r] > 0) {
+        const int gb = i >> GSR_BIN_SHIFT;
+        const uint32_t gbase = gpart[gb];
+        const uint32_t s0 = gbase + goff[i];
+        const uint32_t s1 = ((i & (GSR_BIN_THREADS - 1)) != GSR_BIN_THREADS - 1 && i + 1 < P) ? gbase + goff[i + 1] : ((gb + 1) * GSR_BIN_THREADS < P ? gpart[gb + 1] : hdr->num_slots);
+        for (uint32_t k = s0; k < s1; k++)
+            if (inst_valid[k]) {
+                const float2 v = inst_absgrad[k];
+                ax += v.x;
+                ay += v.y;
+            }
+    }
+    absgrad[r] = make_float2(ax, ay);
+}
+
 }  // namespace
 
 void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
@@ -1015,4 +1069,26 @@ void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radi
     if (P <= 0) return;
     hipLaunchKernelGGL(k_contrib_gather, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, row_range, radii, goff, gpart, inst_contrib, hdr, weight_sum,
                        weight_max, pixel_count);
+}
+
+void gsr_launch_composite_bwd_absgrad(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
+                                      const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
+                                      const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
+                                      GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
+                                      float2 *inst_absgrad, hipStream_t s) {
+    const int wgs = (bx / WAVES) * by;
+    if (wgs <= 0) return;
+    if (inst_ddepth)
+        hipLaunchKernelGGL((k_composite_bwd<true, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
+                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, inst_absgrad);
+    else
+        hipLaunchKernelGGL((k_composite_bwd<false, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
+                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr, nullptr, nullptr, inst_absgrad);
+}
+
+void gsr_launch_absgrad_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const uint8_t *inst_valid,
+                               const float2 *inst_absgrad, const GsrHeader *hdr, float2 *absgrad, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_absgrad_gather, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, row_range, radii, goff, gpart, inst_valid, inst_absgrad, hdr,
+                       absgrad);
 }

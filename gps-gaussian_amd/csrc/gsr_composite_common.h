@@ -107,6 +107,10 @@ __device__ __forceinline__ float swap_add32(float a, float b) {  // lanes 0-31: 
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+__device__ __forceinline__ float swap_absadd32(float a, float b) {  // swap_add32 of |a|, |b|: the magnitudes ride on the add as input modifiers
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __builtin_fabsf(__uint_as_float(r[0])) + __builtin_fabsf(__uint_as_float(r[1]));
+}
 __device__ __forceinline__ float swap_add16(float a, float b) {  // even rows: a folded over row pairs, odd rows: b
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);

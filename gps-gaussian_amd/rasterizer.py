@@ -488,7 +488,7 @@ def _features(features, N, dev):
 
 def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, needs_grad, out_color=None, rows=None,
                   radii_out=None, shs=None, cov3D_precomp=None, depth_alpha=False, out_depth=None, out_alpha=None, antialiasing=False,
-                  features=None, out_feat=None, feat_grad=True, contrib=False, out_contrib=None):
+                  features=None, out_feat=None, feat_grad=True, contrib=False, out_contrib=None, absgrad=False, out_absgrad=None):
     """One view's forward through the C-ABI (capacity policy, early notification, overflow repair).  `ctx` is any attribute holder: the
     autograd ctx of _RasterizeGaussians, or a plain namespace when a caller drives several views itself (render_api._RenderBatch).
     Leaves on it: raster_settings, cap, family, extra_flags, rows, saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
@@ -505,9 +505,12 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     contiguous fp32 [F,H,W] tensor for it; feat_grad=False: the backward will not form dL/dfeatures (the workspace gets no feature tail).  The
     feature array is appended to ctx.saved.  contrib: also the per-Gaussian contribution statistics (include/gpsgs.h GsrContrib), weight_sum,
     weight_max fp32 [P] and pixel_count int32 [P], with the VALU family; not with features.  out_contrib: optional three preallocated contiguous
-    tensors for them -- a row-range view's are REQUIRED and batch-wide (its rows are written).
+    tensors for them -- a row-range view's are REQUIRED and batch-wide (its rows are written).  absgrad: the view's backward will also write the
+    absolute screen-space gradient (include/gpsgs.h GsrAbsGrad) -- the VALU family, a workspace with the absgrad tail, and a zero-filled fp32
+    [rows, 2] tensor left in ctx.absgrad_out and appended to the outputs; out_absgrad: that tensor preallocated (ALREADY zeroed) -- REQUIRED and
+    batch-wide for a row-range view.  Not with features.
     -> (color, radii), with depth_alpha (color, radii, depth [1,H,W], alpha [1,H,W]); with features the feature map is appended last; with contrib
-    the three statistics after everything else"""
+    the three statistics after everything else; with absgrad its tensor last of all"""
     rs = raster_settings
     lib = _capi.lib()
     if not means3D.is_cuda:
@@ -541,6 +544,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     fea = _features(features, N, dev) if features is not None else None
     if contrib and fea is not None:
         raise RuntimeError("gps_gaussian_amd: the contribution statistics cannot be combined with features in one call")
+    if absgrad and fea is not None:
+        raise RuntimeError(_ABSGRAD_FEATURES)
     view = _cam(rs.viewmatrix, 16, dev)
     proj = _cam(rs.projmatrix, 16, dev)
     bg = _cam(rs.bg, 3, dev)
@@ -549,8 +554,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     st = _dev_state(dev)
     mode = _check_mode()
     family = _composite_flag() | (_wave_priority_flag(st, torch._C._cuda_getCurrentRawStream(dev.index), deterministic=(mode == "none")) if rows is None else 0)
-    if depth_alpha or fea is not None or contrib:
-        family = 0  # the depth / alpha and feature maps and the statistics are made by the VALU kernels (forward and backward must agree on it)
+    if depth_alpha or fea is not None or contrib or absgrad:
+        family = 0  # the depth / alpha and feature maps, the statistics and absgrad are made by the VALU kernels (forward and backward must agree on it)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
     base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family | (_capi.GSR_FLAG_ANTIALIAS if antialiasing else 0)
     if mode != "none" and torch.cuda.is_current_stream_capturing():
@@ -595,6 +600,16 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
                 raise RuntimeError("gps_gaussian_amd: out_contrib must be contiguous [rows] tensors (fp32, fp32, int32) on the inputs' device")
             cst = _capi.GsrContrib()
             cst.weight_sum, cst.weight_max, cst.pixel_count = (t.data_ptr() for t in cstats)
+        agrad = None
+        if absgrad:
+            if out_absgrad is None:
+                if rows is not None:
+                    raise RuntimeError("gps_gaussian_amd: a row-range view needs its batch-wide absgrad array (out_absgrad)")
+                agrad = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+            else:
+                agrad = out_absgrad
+                if agrad.dtype is not torch.float32 or agrad.device != dev or tuple(agrad.shape) != (N, 2) or not agrad.is_contiguous():
+                    raise RuntimeError("gps_gaussian_amd: out_absgrad must be a contiguous fp32 [rows, 2] tensor on the inputs' device")
         if rows is None:
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
         else:
@@ -616,6 +631,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
                 nbytes = lib.gsr_workspace_bytes_contrib(P, W, H, cap, bin_cap, fwd_only)
             elif feat is not None and feat_grad and not fwd_only:  # the per-slot feature sums need the feature tail
                 nbytes = lib.gsr_workspace_bytes_features(P, W, H, cap, bin_cap, feat.channels, fwd_only)
+            elif absgrad and not fwd_only:  # the backward's absolute sums need the absgrad tail (with statistics: inside their larger tail)
+                nbytes = lib.gsr_workspace_bytes_absgrad(P, W, H, cap, bin_cap)
             else:
                 nbytes = (lib.gsr_workspace_bytes_depth_alpha if depth_alpha else lib.gsr_workspace_bytes_ex)(P, W, H, cap, bin_cap, fwd_only)
             st["last_ws_bytes"] = nbytes  # reported by last_stats(): what one view in flight holds (forward-only workspaces are ~3x smaller)
@@ -676,11 +693,16 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     ctx.rows = rows
     ctx.depth_alpha = bool(depth_alpha)
     ctx.antialias = antialiasing
+    ctx.absgrad_out = agrad
     ctx.saved = (m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos)
     if fea is not None:
         ctx.saved = ctx.saved + (fea,)
     out = (color, radii) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmap,) if fea is not None else ())
-    return out + cstats if contrib else out
+    out = out + cstats if contrib else out
+    return out + (agrad,) if absgrad else out
+
+
+_ABSGRAD_FEATURES = "gps_gaussian_amd: return_absgrad cannot be combined with features in one call (the feature backward is another kernel family)"
 
 
 def _map_grad(g):
@@ -699,7 +721,9 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
     maps of a depth_alpha forward ([H,W] or [1,H,W]; None = zero); grad_out_color may then be None too.  cam_out: None, or three contiguous fp32
     device tensors / None -- dL/d(viewmatrix [16], projmatrix [16], campos [3]) are WRITTEN into them (gsr_backward_camera: the per-Gaussian
     gradients keep their bits).  Features (the forward was given some: saved[13]): grad_feat is the feature map's gradient ([F,H,W], None = zero);
-    feat_out None, or a contiguous fp32 [rows, F] device tensor that dL/dfeatures is WRITTEN into (a row-range view: batch-wide, its rows written)."""
+    feat_out None, or a contiguous fp32 [rows, F] device tensor that dL/dfeatures is WRITTEN into (a row-range view: batch-wide, its rows written).
+    A forward with absgrad (ctx.absgrad_out): the view's rows of that tensor are OVERWRITTEN with the absolute screen-space gradient
+    (gsr_backward_absgrad: every other gradient keeps its bits)."""
     rs = ctx.raster_settings
     lib = _capi.lib()
     m3, col, opa, sca, rot, view, proj, bg, radii, ws = saved[:10]
@@ -720,6 +744,7 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
         g = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
     elif g.dtype is not torch.float32 or not g.is_contiguous() or g.requires_grad:
         g = g.detach().to(dtype=torch.float32).contiguous()
+    agrad = getattr(ctx, "absgrad_out", None)
     feat = None
     if fea is not None:
         F = int(fea.shape[1])
@@ -774,6 +799,14 @@ def _backward_impl(ctx, saved, grad_out_color, arena, color_grad=True, grad_dept
                 rc = lib.gsr_backward_features(*args, *((_ptr(t) for t in cam_out) if cam_out is not None else (None, None, None)), _ptr(scratch), nbytes,
                                                C.byref(feat))
                 _capi.check(rc, "gsr_backward_features")
+            elif agrad is not None:
+                nbytes = lib.gsr_camera_grad_scratch_bytes(P) if cam_out is not None else 0
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if cam_out is not None else None
+                ab = _capi.GsrAbsGrad()
+                ab.absgrad = agrad.data_ptr()
+                rc = lib.gsr_backward_absgrad(*args, *((_ptr(t) for t in cam_out) if cam_out is not None else (None, None, None)), _ptr(scratch), nbytes,
+                                              C.byref(ab))
+                _capi.check(rc, "gsr_backward_absgrad")
             elif cam_out is None:
                 rc = lib.gsr_backward_ex(*args)
                 _capi.check(rc, "gsr_backward_ex")
@@ -868,7 +901,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
                 return_depth_alpha=False, antialiasing=False, camera_grad=False, viewmatrix=None, projmatrix=None, campos=None, features=None,
-                return_contrib=False):
+                return_contrib=False, return_absgrad=False):
         # grad_arena (optional, internal to pts2render): five preallocated fp32 tensors [P,3],[P,3],[P,1],[P,3],[P,4] -- row slices
         # of batch-wide buffers -- that the backward writes dL/d(means3D, colours, opacities, scales, rotations) into instead of
         # fresh allocations, so that the batch's gradients arrive already concatenated (render_api._SplitRows)
@@ -884,9 +917,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.has_features = features is not None
         # return_contrib: the three per-Gaussian statistics are appended last, not differentiable (like radii)
         ctx.n_contrib_out = 3 if return_contrib else 0
+        # return_absgrad: one [P, 2] tensor after them, zero-filled here, not differentiable, overwritten in place by every backward; a callable
+        # (internal to pts2render) is then called with it, on the backward's stream
+        ctx.n_contrib_out += 1 if return_absgrad else 0
+        ctx.absgrad_sink = return_absgrad if callable(return_absgrad) else None
         out = _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, raster_settings, any(ctx.needs_input_grad),
                             shs=sh, cov3D_precomp=cov3Ds_precomp, depth_alpha=bool(return_depth_alpha), antialiasing=antialiasing,
-                            features=features, feat_grad=features is not None and ctx.needs_input_grad[16], contrib=bool(return_contrib))
+                            features=features, feat_grad=features is not None and ctx.needs_input_grad[16], contrib=bool(return_contrib),
+                            absgrad=bool(return_absgrad))
         if _debug_keep_ws:
             _tls.last_ws = dict(ws=ctx.saved[9], cap=ctx.cap, bin_cap=ctx.bin_cap)
         ctx.save_for_backward(*ctx.saved)
@@ -897,12 +935,12 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, *grad_maps):
-        # grad_maps: (dL/ddepth, dL/dalpha) with return_depth_alpha, then dL/dfeaturemap with features, then three Nones for the statistics
+        # grad_maps: (dL/ddepth, dL/dalpha) with return_depth_alpha, then dL/dfeaturemap with features, then Nones for the statistics and absgrad
         grad_maps = grad_maps[:len(grad_maps) - ctx.n_contrib_out]
         grad_depth, grad_alpha = grad_maps[:2] if ctx.return_depth_alpha else (None, None)
         grad_feat = grad_maps[-1] if ctx.has_features else None
         if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_feat is None:  # no output took part in the loss
-            return (None,) * 18
+            return (None,) * 19
         saved = ctx.saved_tensors
         cam_out = None
         if ctx.camera_grad:
@@ -913,16 +951,18 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_feat = torch.empty(tuple(fea.shape), dtype=torch.float32, device=fea.device)
         d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov = _backward_impl(ctx, saved, grad_out_color, ctx.grad_arena, ctx.color_grad,
                                                                            grad_depth, grad_alpha, cam_out, grad_feat, d_feat)
+        if ctx.absgrad_sink is not None:
+            ctx.absgrad_sink(ctx.absgrad_out)
         has_sh, has_cov = saved[10] is not None, saved[11] is not None
         d_cam = (None, None, None) if cam_out is None else tuple(_cam_grad_as(g, t) for g, t in zip(cam_out, ctx.cams))
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, return_depth_alpha,
         #  antialiasing, camera_grad, viewmatrix, projmatrix, campos)
         return (d_m3, d_m2, d_sh, (d_col if ctx.color_grad and not has_sh else None), d_op, (None if has_cov else d_sc), (None if has_cov else d_rot),
-                d_cov, None, None, None, None, None) + d_cam + (d_feat, None)
+                d_cov, None, None, None, None, None) + d_cam + (d_feat, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False):
+                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False, return_absgrad=False):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
     and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
@@ -935,7 +975,21 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return_contrib=True: also returns the per-Gaussian contribution statistics LAST -- contrib_weight (fp32 [P], the sum over pixels of the blend
     weight alpha T), contrib_max (fp32 [P], its maximum) and contrib_pixels (int32 [P], the pixels the Gaussian is blended into) -- from the image's
     own blend (the VALU kernels; zeros for culled Gaussians and for a view that overflowed unrepaired), not differentiable, bitwise reproducible
-    (include/gpsgs.h GsrContrib).  Combines with everything above except features (RuntimeError before anything is launched)."""
+    (include/gpsgs.h GsrContrib).  Combines with everything above except features (RuntimeError before anything is launched).
+    return_absgrad=True: also returns, LAST of all, absgrad (fp32 [P, 2]): the absolute screen-space gradient sum_p |dL_p/dmean2D_i| in the units of
+    means2D.grad[:, :2] (AbsGS's homodirectional gradient, gsplat's absgrad; include/gpsgs.h GsrAbsGrad).  The tensor is zero-filled by the forward, not
+    differentiable, and every backward through the node OVERWRITES it in place (it does not accumulate): read it after backward().  Zeros for culled
+    Gaussians and for a view that overflowed unrepaired; bitwise reproducible; every other output and gradient keeps the bits of the call without it
+    (VALU kernels).  Combines with everything above except features (RuntimeError before anything is launched)."""
+    if return_absgrad:
+        if features is not None:
+            raise RuntimeError(_ABSGRAD_FEATURES)
+        rs = raster_settings
+        cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos)) if camera_grad else (None, None, None)
+        aa = bool(antialiasing) or bool(getattr(rs, "antialiasing", False))
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, grad_arena, bool(return_depth_alpha), aa, bool(camera_grad), *cams, None, bool(return_contrib),
+                                         return_absgrad if callable(return_absgrad) else True)
     if return_contrib:
         rs = raster_settings
         cams = tuple(t if isinstance(t, torch.Tensor) else None for t in (rs.viewmatrix, rs.projmatrix, rs.campos)) if camera_grad else (None, None, None)
@@ -973,7 +1027,8 @@ class GaussianRasterizer(nn.Module):
             acc.late_apply()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False):
+                grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False,
+                return_absgrad=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
@@ -981,7 +1036,7 @@ class GaussianRasterizer(nn.Module):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         antialiasing = antialiasing or getattr(self.raster_settings, "antialiasing", False)
         if (shs is None and cov3D_precomp is None and grad_arena is None and not return_depth_alpha and not antialiasing and not camera_grad
-                and features is None and not return_contrib):
+                and features is None and not return_contrib and not return_absgrad):
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
             if out is not None:
@@ -991,9 +1046,11 @@ class GaussianRasterizer(nn.Module):
         # with sh_degree = 3 and campos (:46-47): both inputs are part of the module it imports.
         # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing and camera_grad: the Python host path (not
         # the compiled one)
-        # features [P, F]: the feature map is appended to the outputs; return_contrib: the three statistics after it (rasterize_gaussians)
+        # features [P, F]: the feature map is appended to the outputs; return_contrib: the three statistics after it; return_absgrad: the absolute
+        # screen-space gradient last of all, filled by the backward (rasterize_gaussians)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad, features, return_contrib)
+                                   self.raster_settings, grad_arena, return_depth_alpha, antialiasing, camera_grad, features, return_contrib,
+                                   return_absgrad)
 
 
     def markVisible(self, positions):

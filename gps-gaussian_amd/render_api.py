@@ -102,14 +102,16 @@ class _RenderBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False, camera_grad=False,
-                view_all=None, proj_all=None, campos_all=None, features=None, contrib=False):
+                view_all=None, proj_all=None, campos_all=None, features=None, contrib=False, absgrad=False):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
         # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
         # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS;
         # camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds them) get
         # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True)); features: packed [N, F] (pack.pack_features), the
         # feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...)); contrib: then the per-Gaussian statistics
-        # weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its rows)
+        # weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its rows); absgrad: last of
+        # all the absolute screen-space gradient [N, 2], zeros here, each view's rows overwritten by every backward
+        # (rasterizer.rasterize_gaussians(return_absgrad=True)); a callable is then called with it at the end of the backward, on its stream
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
@@ -120,6 +122,7 @@ class _RenderBatch(torch.autograd.Function):
         radii = torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
         cstats = (torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev), torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev),
                   torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)) if contrib else None
+        agrad = torch.zeros((xyz.shape[0], 2), dtype=torch.float32, device=dev) if absgrad else None
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
         side = _streams(dev, bs) if (bs > 1 and not torch.cuda.is_current_stream_capturing()) else [cur] * bs
@@ -135,7 +138,7 @@ class _RenderBatch(torch.autograd.Function):
                                       rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
                                       out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None,
                                       antialiasing=antialiasing, features=features, out_feat=fmaps[i] if fmaps is not None else None,
-                                      feat_grad=feat_grad, contrib=bool(contrib), out_contrib=cstats)
+                                      feat_grad=feat_grad, contrib=bool(contrib), out_contrib=cstats, absgrad=bool(absgrad), out_absgrad=agrad)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -157,21 +160,23 @@ class _RenderBatch(torch.autograd.Function):
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
         ctx.depth_alpha, ctx.has_features, ctx.feat_grad = bool(depth_alpha), features is not None, feat_grad
         ctx.feat_shape = tuple(features.shape) if features is not None else None
-        ctx.n_contrib_out = 3 if contrib else 0
+        ctx.n_contrib_out = (3 if contrib else 0) + (1 if absgrad else 0)
+        ctx.absgrad_out, ctx.absgrad_sink = agrad, (absgrad if callable(absgrad) else None)
         ctx.set_materialize_grads(False)
         outs = (out,) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmaps,) if fmaps is not None else ())
-        if cstats is not None:
-            ctx.mark_non_differentiable(*cstats)
-            outs = outs + cstats
+        nondiff = (cstats if cstats is not None else ()) + ((agrad,) if agrad is not None else ())
+        if nondiff:
+            ctx.mark_non_differentiable(*nondiff)
+            outs = outs + nondiff
         return outs if len(outs) > 1 else out
 
     @staticmethod
     def backward(ctx, gout, *gmaps):
-        gmaps = gmaps[:len(gmaps) - ctx.n_contrib_out]  # (the statistics are not differentiable)
+        gmaps = gmaps[:len(gmaps) - ctx.n_contrib_out]  # (the statistics and absgrad are not differentiable)
         gdepth, galpha = gmaps[:2] if ctx.depth_alpha else (None, None)
         gfeat = gmaps[-1] if ctx.has_features else None
         if gout is None and gdepth is None and galpha is None and gfeat is None:
-            return (None,) * 16
+            return (None,) * 17
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
@@ -202,10 +207,12 @@ class _RenderBatch(torch.autograd.Function):
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
+        if ctx.absgrad_sink is not None:  # (every view's rows of ctx.absgrad_out are written: the holders carry the tensor)
+            ctx.absgrad_sink(ctx.absgrad_out)
         d_cam = (None, None, None)
         if cam_all is not None:
             d_cam = tuple(_RZ._cam_grad_as(c, t) for c, t in zip(cam_all, ctx.cams))
-        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat, None)
+        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat, None, None)
 
 
 def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
@@ -233,7 +240,7 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
 
 
 def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False,
-              features=None, contrib=False):
+              features=None, contrib=False, absgrad=False):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
@@ -243,17 +250,22 @@ def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color,
     (1 - alpha) bg_f), differentiable in the features and the geometry (rasterizer.rasterize_gaussians).  contrib=True: also the per-Gaussian
     contribution statistics of the view, 'contrib_weight' (fp32 [P], sum over pixels of alpha T), 'contrib_max' (fp32 [P], its maximum) and
     'contrib_pixels' (int32 [P], pixels blended into), not differentiable (rasterizer.rasterize_gaussians(return_contrib=True)); not with
-    features."""
+    features.  absgrad=True: also 'absgrad' (fp32 [P, 2]), the absolute screen-space gradient sum_p |dL_p/dmean2D_i| in the units of the screen-space
+    gradient: zeros until a backward through the view has run, then overwritten in place by each one; not differentiable
+    (rasterizer.rasterize_gaussians(return_absgrad=True)); not with features."""
     nv = data['novel_view']
     bg = _bg_tensor(bg_color, pts_xyz.device)
     means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
     out = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
-                     camera_grad=camera_grad, features=features, return_contrib=contrib)
+                     camera_grad=camera_grad, features=features, return_contrib=contrib, return_absgrad=absgrad)
     r = {'img': out[0], 'depth': out[2], 'alpha': out[3]}
     if features is not None:
         r['feat'] = out[4]
+    if absgrad:
+        r['absgrad'] = out[-1]
+        out = out[:-1]
     if contrib:
         r['contrib_weight'], r['contrib_max'], r['contrib_pixels'] = out[-3:]
     return r
@@ -290,7 +302,30 @@ def _write_contrib_maps(data, stats, row_of_pixel):
             data[view][key] = maps[:, v].reshape(-1, 1, H, W)
 
 
-def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None, with_contrib=False):
+def _absgrad_maps(data):
+    """data['lmain' | 'rmain']['absgrad'] = zeros [B,2,H,W] (pts2render(with_absgrad=True)) -> the two maps"""
+    from .pack import VIEWS
+
+    maps = []
+    for view in VIEWS:
+        img = data[view]['img']
+        data[view]['absgrad'] = torch.zeros((img.shape[0], 2, int(img.shape[2]), int(img.shape[3])), dtype=torch.float32, device=img.device)
+        maps.append(data[view]['absgrad'])
+    return maps
+
+
+def _fill_absgrad_maps(maps, absgrad, rows, first_row=0):
+    """absgrad [n, 2] of the packed rows first_row .. first_row + n -> the source pixels of maps[v] ([b,2,H,W] each); rows: pack_views' row_of_pixel
+    [b, views, S2] of the same samples (a pixel whose pts_valid is false: -1 -> 0).  Device index ops only, no host synchronisation; runs inside the
+    render node's backward."""
+    idx = rows.to(torch.int64) - first_row
+    vals = torch.where((idx >= 0).unsqueeze(-1), absgrad[idx.clamp(min=0)], absgrad.new_zeros(()))  # [b, views, S2, 2]
+    for v, m in enumerate(maps):
+        m.copy_(vals[:, v].permute(0, 2, 1).reshape(m.shape))
+
+
+def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None, with_contrib=False,
+               with_absgrad=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
     antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
@@ -302,6 +337,9 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     with_contrib=True (opt-in): every Gaussian's contribution statistics in the novel view (render_ex(contrib=True)) go back to the source pixel it
     came from -- data['lmain'] and data['rmain'] get 'contrib_weight', 'contrib_max' (fp32) and 'contrib_pixels' (int32), each [B,1,H,W], 0 where
     pts_valid is false.  Not differentiable; not with feature_key (RuntimeError before anything is launched).
+    with_absgrad=True (opt-in): data['lmain'] and data['rmain'] get 'absgrad' [B,2,H,W], zeros now; the BACKWARD of the render node writes every
+    Gaussian's absolute screen-space gradient (render_ex(absgrad=True)) to the source pixel it came from, 0 where pts_valid is false -- overwritten by
+    each backward, with device index ops only.  Not differentiable; not with feature_key (RuntimeError mentioning features, before any launch).
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -315,7 +353,9 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     feats = row_of_pixel = None
     if with_contrib and feature_key is not None:
         raise RuntimeError("gps_gaussian_amd: with_contrib cannot be combined with feature_key")
-    if with_contrib:
+    if with_absgrad and feature_key is not None:
+        raise RuntimeError("gps_gaussian_amd: with_absgrad cannot be combined with feature_key (features)")
+    if with_contrib or with_absgrad:
         xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
     elif feature_key is None:
         xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
@@ -330,7 +370,17 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        if with_contrib:
+        if with_absgrad:
+            amaps = _absgrad_maps(data)
+            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
+                                     bool(camera_grad), *cams, None, bool(with_contrib), lambda a: _fill_absgrad_maps(amaps, a, row_of_pixel))
+            nv['img_pred'] = out[0]
+            if with_depth_alpha:
+                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
+            if with_contrib:
+                _write_contrib_maps(data, out[-4:-1], row_of_pixel)
+        elif with_contrib:
             cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
             out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
                                      bool(camera_grad), *cams, None, True)
@@ -363,12 +413,14 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
             nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         return data
     return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad, feats,
-                            row_of_pixel if with_contrib else None)
+                            row_of_pixel if with_contrib else None, row_of_pixel if with_absgrad else None)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None, row_of_pixel=None):
+def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None, row_of_pixel=None,
+                     absgrad_rows=None):
     """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream.  row_of_pixel (pack_views'): the
-    contribution statistics are wanted (pts2render(with_contrib=True))."""
+    contribution statistics are wanted (pts2render(with_contrib=True)); absgrad_rows (pack_views' row_of_pixel too): the absgrad maps are
+    (pts2render(with_absgrad=True)) -- every sample's node fills its slice of them in its backward."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
     # ONE split per packed tensor (its backward is one concatenation of the per-sample gradients); B Python slices would make
@@ -393,6 +445,7 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
     # batch loop is host-bound, tools/stage2_ab.py -- the reason _RenderBatch exists)
     concurrent = bs > 1 and not torch.cuda.is_current_stream_capturing() and os.environ.get("GPSGS_PTS2RENDER_STREAMS", "0") == "1"
     side = _streams(dev, bs) if concurrent else [cur] * bs
+    amaps = _absgrad_maps(data) if absgrad_rows is not None else None
     with _RZ.defer_capacity_checks():
         for i in range(bs):
             # arena order expected by the rasteriser: means3D, colours, opacities, scales, rotations
@@ -400,10 +453,14 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
             if side[i] is not cur:
                 side[i].wait_stream(cur)
             with torch.cuda.stream(side[i]):
-                if with_depth_alpha or feats is not None or row_of_pixel is not None:
+                if with_depth_alpha or feats is not None or row_of_pixel is not None or amaps is not None:
+                    sink = False
+                    if amaps is not None:  # sample i's rows start at offs[i] of the packed order row_of_pixel speaks of
+                        def sink(a, i=i):
+                            _fill_absgrad_maps([m[i:i + 1] for m in amaps], a, absgrad_rows[i:i + 1], offs[i])
                     r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
                                   antialiasing=antialiasing, camera_grad=camera_grad, features=f_parts[i] if feats is not None else None,
-                                  contrib=row_of_pixel is not None)
+                                  contrib=row_of_pixel is not None, absgrad=sink)
                     out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha') + (('feat',) if feats is not None else ()))
                                + (tuple(r[k] for k in _CONTRIB_KEYS) if row_of_pixel is not None else ()))
                 else:

@@ -53,7 +53,8 @@ extern "C" {
                                   out_alpha | dL_dalpha; zero = none, what 4 did, same 80-byte struct) + gsr_workspace_bytes_depth_alpha
                                still 4 after the feature maps: GsrFeatures, gsr_workspace_bytes_features, gsr_forward_features,
                                   gsr_backward_features (additive)
-                               still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive) */
+                               still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive)
+                               still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -346,6 +347,41 @@ int gsr_forward_contrib(int P, int width, int height, const float *means3D, cons
                         const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                         void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                         void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrContrib *contrib);
+
+/* Absolute screen-space gradient (opt-in; AbsGS's "homodirectional gradient", gsplat's absgrad).  dL_dmeans2D[i, 0:2] is a SIGNED sum over the pixels
+ * Gaussian i covers and cancels where the loss pulls the two sides of a Gaussian apart; this is the sum of the per-pixel magnitudes.  In the backward's
+ * own conventions (straight through min(0.99, .), every discrete decision held constant, d = mean2D_i - pixel): a (pixel p, Gaussian i) pair receives
+ * gradient when its list position is in front of p's last contributor, not power > 0, and alpha >= 1/255; with s = opacity_i dL/dalpha G (opacity_i the
+ * compensated one with GSR_FLAG_ANTIALIAS; dL/dalpha including the depth / alpha maps' gradients when ext passes them) and the conic (A, B, C)
+ *   t_x(p, i) = 0.5 W s (-A d_x - B d_y)        t_y(p, i) = 0.5 H s (-C d_y - B d_x)
+ *   dL_dmeans2D[i, 0:2] = ( sum_p t_x , sum_p t_y )          (as without it, bit for bit)
+ *   absgrad[i, 0:2]     = ( sum_p |t_x| , sum_p |t_y| )      fp32, in dL_dmeans2D's units (NDC-scaled), never negative
+ * indexed like radii; exactly 0 for culled Gaussians (radii 0), for Gaussians no pixel gives gradient to and for every Gaussian of an overflowed view.
+ * Every call OVERWRITES the view's rows (with a row range only those).  No atomics: per (bin, splat) record the backward compositing kernel keeps the
+ * two sums in the workspace's absgrad tail, a gather streams each Gaussian's flagged slots in slot order -- the same bits on every run.  Made by the VALU
+ * compositing family: the tiles flag is ignored by this call, and the FORWARD that filled the workspace must have run without
+ * GSR_FLAG_COMPOSITE_TILES too (the two families round the exponent differently).  Every other output of the call -- all gradients -- has the bits of
+ * gsr_backward_camera; a NULL `abs` or a NULL abs->absgrad IS gsr_backward_camera.  GPSGS_E_INVALID for a pointer that is not 4-byte aligned or a
+ * non-NULL `reserved`; GPSGS_E_WORKSPACE for a workspace smaller than gsr_workspace_bytes_absgrad.  No host synchronisation.  Combines with the depth /
+ * alpha gradients, antialiasing, camera gradients, shs, cov3D_precomp, row ranges, both list forms and GSR_FLAG_NO_COLOR_GRAD; not with feature maps
+ * (there is no entry point taking both). */
+typedef struct GsrAbsGrad {
+    float *absgrad; /* DEVICE [rows, 2], written; NULL = not wanted */
+    void *reserved; /* NULL */
+} GsrAbsGrad;
+/* gsr_workspace_bytes_depth_alpha(..., 0) plus the 256-byte aligned absgrad tail (instance_capacity x 8 bytes); size the FORWARD's workspace with it.
+ * The tail takes the place of the contribution tail, which is dead once gsr_forward_contrib has returned its statistics: a workspace sized with
+ * gsr_workspace_bytes_contrib (never smaller) serves a view that wants both.  0 on invalid arguments. */
+size_t gsr_workspace_bytes_absgrad(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity);
+/* gsr_backward_camera's argument list, then the GsrAbsGrad */
+int gsr_backward_absgrad(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                         const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                         const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                         const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                         float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                         int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                         float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                         const GsrAbsGrad *abs);
 
 /* Visibility mask (upstream `_C.mark_visible`, reached through GaussianRasterizer.markVisible(positions) of the module the reference imports at
  * gaussian_renderer/__init__.py:14; the reference itself never calls it): present[i] = 1 iff point i passes the near-plane test of the forward
