@@ -142,10 +142,16 @@ extern "C" int gsr_supported_flags(void) {
 
 extern "C" const char *gpsgs_build_info(void) { return "gfx950 hipcc " __VERSION__ " built " __DATE__; }
 
-extern "C" size_t gsr_workspace_bytes(int P, int width, int height, int64_t instance_capacity) {
+namespace {
+// What every gsr_workspace_bytes_* function reports: 0 for invalid arguments (a bin capacity that direct lists cannot have included), the forward-only
+// size, or the training layout (`extra`: with the depth / alpha slot array) plus the opt-in `tail` behind it.
+size_t workspace_size(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only, bool extra, size_t tail) {
     if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    return gsr_layout(P, width, height, instance_capacity).total;
+    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
+    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    return forward_only ? L.total_fwd : (extra ? L.total_extra : L.total) + tail;
 }
+}  // namespace
 
 extern "C" int gsr_direct_lists_ok(int width, int height, uint32_t bin_capacity) {
     if (width <= 0 || height <= 0 || bin_capacity == 0u || bin_capacity > GSR_DIRECT_MAX_CAP || (bin_capacity & 63u)) return 0;
@@ -154,46 +160,34 @@ extern "C" int gsr_direct_lists_ok(int width, int height, uint32_t bin_capacity)
     return (L.NB <= GSR_DIRECT_MAX_BINS && nt <= GSR_DIRECT_MAX_BINS) ? 1 : 0;
 }
 
-extern "C" size_t gsr_workspace_bytes_ex(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return forward_only ? L.total_fwd : L.total;
-}
-
-extern "C" size_t gsr_workspace_bytes_depth_alpha(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return forward_only ? L.total_fwd : L.total_extra;
+extern "C" size_t gsr_workspace_bytes(int P, int width, int height, int64_t instance_capacity) {
+    return workspace_size(P, width, height, instance_capacity, 0u, 0, false, 0);
 }
 
 extern "C" size_t gsr_workspace_bytes_forward_only(int P, int width, int height, int64_t instance_capacity) {
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    return gsr_layout(P, width, height, instance_capacity).total_fwd;
+    return workspace_size(P, width, height, instance_capacity, 0u, 1, false, 0);
+}
+
+extern "C" size_t gsr_workspace_bytes_ex(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, false, 0);
+}
+
+extern "C" size_t gsr_workspace_bytes_depth_alpha(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, true, 0);
 }
 
 extern "C" size_t gsr_workspace_bytes_features(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int channels, int forward_only) {
     if (channels < 1 || channels > GSR_MAX_FEATURES) return 0;
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return forward_only ? L.total_fwd : L.total_extra + gsr_feature_tail_bytes(instance_capacity, channels);
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, true, gsr_feature_tail_bytes(instance_capacity, channels));
 }
 
 extern "C" size_t gsr_workspace_bytes_contrib(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
     (void)forward_only;  // (the same size: the statistics read the slot prefix of the backward tail)
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return L.total_extra + gsr_contrib_tail_bytes(instance_capacity);
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, 0, true, gsr_contrib_tail_bytes(instance_capacity));
 }
 
 extern "C" size_t gsr_workspace_bytes_absgrad(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity) {
-    if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
-    if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return L.total_extra + gsr_absgrad_tail_bytes(instance_capacity);
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, 0, true, gsr_absgrad_tail_bytes(instance_capacity));
 }
 
 namespace {
@@ -600,6 +594,21 @@ extern "C" size_t gsr_camera_grad_scratch_bytes(int P) {
     return sizeof(float) * (size_t)GSR_CAMGRAD_TERMS * (size_t)((P + 255) / 256);  // one partial per term and preprocess_bwd workgroup
 }
 
+namespace {
+// The camera arguments of gsr_backward_camera / _absgrad / _features: misaligned outputs or a scratch slab too small for P are refused; `want`
+// points at `cam` when any of the three gradients is asked for and stays NULL otherwise (the call is then gsr_backward_ex).
+int camera_args(int P, float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes, GsrCamGrad &cam,
+                const GsrCamGrad *&want) {
+    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
+        return GPSGS_E_INVALID;
+    if (!(dL_dviewmatrix || dL_dprojmatrix || dL_dcampos)) return GPSGS_OK;
+    if (P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
+    cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    want = &cam;
+    return GPSGS_OK;
+}
+}  // namespace
+
 extern "C" int gsr_backward_camera(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
                                    const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
                                    const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
@@ -607,14 +616,13 @@ extern "C" int gsr_backward_camera(int P, int width, int height, const float *me
                                    float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                    int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                    float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes) {
-    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
-        return GPSGS_E_INVALID;
-    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
-    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
-    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    GsrCamGrad cam;
+    const GsrCamGrad *want = nullptr;
+    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
+    if (rc != GPSGS_OK) return rc;
     return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                          radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want ? &cam : nullptr);
+                         instance_capacity, flags, stream, ext, want);
 }
 
 extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -625,14 +633,13 @@ extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *m
                                     int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                     float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                     const GsrAbsGrad *abs) {
-    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
-        return GPSGS_E_INVALID;
-    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
-    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
-    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    GsrCamGrad cam;
+    const GsrCamGrad *want = nullptr;
+    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
+    if (rc != GPSGS_OK) return rc;
     return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                          radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want ? &cam : nullptr, nullptr, abs);
+                         instance_capacity, flags, stream, ext, want, nullptr, abs);
 }
 
 extern "C" int gsr_backward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -643,14 +650,13 @@ extern "C" int gsr_backward_features(int P, int width, int height, const float *
                                      int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                      float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                      const GsrFeatures *feat) {
-    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
-        return GPSGS_E_INVALID;
-    const bool want = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
-    if (want && P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
-    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    GsrCamGrad cam;
+    const GsrCamGrad *want = nullptr;
+    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
+    if (rc != GPSGS_OK) return rc;
     return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
                          radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want ? &cam : nullptr, feat);
+                         instance_capacity, flags, stream, ext, want, feat);
 }
 
 extern "C" int gsr_backward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,

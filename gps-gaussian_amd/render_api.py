@@ -87,6 +87,10 @@ class _Holder:
     pass
 
 
+def _row(t, i):
+    return t[i] if t is not None else None
+
+
 class _RenderBatch(torch.autograd.Function):
     """All samples of a pts2render batch as ONE autograd node: B raster forwards enqueued back to back on B HIP streams (the views
     are independent and one view leaves the chip under-occupied: DESIGN.md section 4), their exact capacity checks collected and run
@@ -101,28 +105,32 @@ class _RenderBatch(torch.autograd.Function):
     Numerically it IS the per-sample path: the same kernels on the same rows (tests/test_gpu_pack.py compares the bits)."""
 
     @staticmethod
-    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, depth_alpha=False, antialiasing=False, camera_grad=False,
-                view_all=None, proj_all=None, campos_all=None, features=None, contrib=False, absgrad=False):
+    def forward(ctx, xyz, rgb, rot, scale, opacity, offsets, settings, cap_rows, opts=_RZ._DEFAULT_OPTIONS, view_all=None, proj_all=None,
+                campos_all=None, features=None):
         # xyz .. opacity: packed [N, C] fp32 (pack.pack_views); offsets: B + 1 row offsets, int32 ON THE DEVICE; settings: B
-        # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); depth_alpha: also return the depth and
-        # alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with GSR_FLAG_ANTIALIAS;
-        # camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds them) get
-        # the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True)); features: packed [N, F] (pack.pack_features), the
-        # feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...)); contrib: then the per-Gaussian statistics
-        # weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its rows); absgrad: last of
-        # all the absolute screen-space gradient [N, 2], zeros here, each view's rows overwritten by every backward
-        # (rasterizer.rasterize_gaussians(return_absgrad=True)); a callable is then called with it at the end of the backward, on its stream
+        # GaussianRasterizationSettings; cap_rows: upper bound of a sample's rows (views x pixels); opts (rasterizer._ViewOptions) -- depth_alpha:
+        # also return the depth and alpha maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_depth_alpha=True)); antialiasing: every view with
+        # GSR_FLAG_ANTIALIAS; camera_grad: view_all / proj_all / campos_all ([B,4,4], [B,4,4], [B,3]: the batch's novel cameras as the caller holds
+        # them) get the per-sample camera gradients (rasterizer.rasterize_gaussians(camera_grad=True)); features: packed [N, F]
+        # (pack.pack_features), the feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...)); contrib: then the
+        # per-Gaussian statistics weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its
+        # rows); absgrad: last of all the absolute screen-space gradient [N, 2], zeros here, each view's rows overwritten by every backward
+        # (rasterizer.rasterize_gaussians(return_absgrad=True)); opts.absgrad_sink is then called with it at the end of the backward, on its stream
+        # -> rasterizer._pack_outputs of the batch-wide rasterizer._Outputs (no radii)
         bs = len(settings)
         dev = xyz.device
         H, W = int(settings[0].image_height), int(settings[0].image_width)
-        out = torch.empty((bs, 3, H, W), dtype=torch.float32, device=dev)
-        dmaps = (torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev), torch.empty((bs, 1, H, W), dtype=torch.float32, device=dev)) if depth_alpha else None
-        fmaps = torch.empty((bs, features.shape[1], H, W), dtype=torch.float32, device=dev) if features is not None else None
-        feat_grad = features is not None and ctx.needs_input_grad[14]
-        radii = torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
-        cstats = (torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev), torch.empty((xyz.shape[0],), dtype=torch.float32, device=dev),
-                  torch.empty((xyz.shape[0],), dtype=torch.int32, device=dev)) if contrib else None
-        agrad = torch.zeros((xyz.shape[0], 2), dtype=torch.float32, device=dev) if absgrad else None
+        N, f32 = xyz.shape[0], torch.float32
+        out = torch.empty((bs, 3, H, W), dtype=f32, device=dev)
+        depth = torch.empty((bs, 1, H, W), dtype=f32, device=dev) if opts.depth_alpha else None
+        alpha = torch.empty((bs, 1, H, W), dtype=f32, device=dev) if opts.depth_alpha else None
+        fmaps = torch.empty((bs, features.shape[1], H, W), dtype=f32, device=dev) if opts.features else None
+        feat_grad = opts.features and ctx.needs_input_grad[12]
+        radii = torch.empty((N,), dtype=torch.int32, device=dev)  # batch-wide, like the inputs
+        cstats = (torch.empty((N,), dtype=f32, device=dev), torch.empty((N,), dtype=f32, device=dev),
+                  torch.empty((N,), dtype=torch.int32, device=dev)) if opts.contrib else (None, None, None)
+        agrad = torch.zeros((N, 2), dtype=f32, device=dev) if opts.absgrad else None
+        outs = _RZ._Outputs(out, None, depth, alpha, fmaps, *cstats, agrad)
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
         side = _streams(dev, bs) if (bs > 1 and not torch.cuda.is_current_stream_capturing()) else [cur] * bs
@@ -134,11 +142,10 @@ class _RenderBatch(torch.autograd.Function):
                 if side[i] is not cur:
                     side[i].wait_stream(cur)
                 with torch.cuda.stream(side[i]):
-                    _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, out_color=out[i],
-                                      rows=_RZ._Rows(offsets, i, cap_rows), radii_out=radii, depth_alpha=bool(depth_alpha),
-                                      out_depth=dmaps[0][i] if depth_alpha else None, out_alpha=dmaps[1][i] if depth_alpha else None,
-                                      antialiasing=antialiasing, features=features, out_feat=fmaps[i] if fmaps is not None else None,
-                                      feat_grad=feat_grad, contrib=bool(contrib), out_contrib=cstats, absgrad=bool(absgrad), out_absgrad=agrad)
+                    _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, opts,
+                                      out=dict(color=out[i], radii=radii, depth=_row(depth, i), alpha=_row(alpha, i), feat=_row(fmaps, i),
+                                               contrib=cstats, absgrad=agrad),
+                                      rows=_RZ._Rows(offsets, i, cap_rows), features=features, feat_grad=feat_grad)
                 views.append(h)
         for i in range(bs):
             if side[i] is not cur:
@@ -147,72 +154,61 @@ class _RenderBatch(torch.autograd.Function):
         # per-view holders keep only what is not an input: camera matrices, background, radii, workspace.  (pack_views hands out
         # contiguous fp32, which _forward_impl uses as is; should an input ever have been converted on the way in, the holder keeps the
         # converted tensors instead.)
-        packed = (xyz, rgb, opacity, scale, rot)  # order of _forward_impl's saved tuple: m3, col, opa, sca, rot
         for h in views:
-            same = all(sv.data_ptr() == t.data_ptr() and sv.numel() == t.numel() for sv, t in zip(h.saved[:5], packed))
-            h.tail, h.own = h.saved[5:], (None if same else h.saved[:5])
-            h.saved = None
+            s = h.saved
+            pairs = ((s.m3, xyz), (s.col, rgb), (s.opa, opacity), (s.sca, scale), (s.rot, rot))
+            if all(sv.data_ptr() == t.data_ptr() and sv.numel() == t.numel() for sv, t in pairs):
+                h.saved = s._replace(m3=None, col=None, opa=None, sca=None, rot=None)
         ctx.save_for_backward(xyz, rgb, rot, scale, opacity)
-        ctx.views, ctx.side = views, side
-        ctx.camera_grad = bool(camera_grad)
-        ctx.cams = (view_all, proj_all, campos_all) if camera_grad else None
+        ctx.views, ctx.side, ctx.opts = views, side, opts
+        ctx.cams = (view_all, proj_all, campos_all) if opts.camera_grad else None
         ctx.color_grad = bool(ctx.needs_input_grad[1])  # False in stage 2: pack_views marks rgb non-differentiable when no image needs a gradient
         ctx.shapes = tuple(tuple(t.shape) for t in (xyz, rgb, rot, scale, opacity))
-        ctx.depth_alpha, ctx.has_features, ctx.feat_grad = bool(depth_alpha), features is not None, feat_grad
-        ctx.feat_shape = tuple(features.shape) if features is not None else None
-        ctx.n_contrib_out = (3 if contrib else 0) + (1 if absgrad else 0)
-        ctx.absgrad_out, ctx.absgrad_sink = agrad, (absgrad if callable(absgrad) else None)
+        ctx.feat_shape = tuple(features.shape) if feat_grad else None
+        ctx.absgrad_out = agrad
         ctx.set_materialize_grads(False)
-        outs = (out,) + ((dmaps[0], dmaps[1]) if depth_alpha else ()) + ((fmaps,) if fmaps is not None else ())
-        nondiff = (cstats if cstats is not None else ()) + ((agrad,) if agrad is not None else ())
-        if nondiff:
-            ctx.mark_non_differentiable(*nondiff)
-            outs = outs + nondiff
-        return outs if len(outs) > 1 else out
+        ctx.mark_non_differentiable(*_RZ._non_differentiable(outs))
+        return _RZ._pack_outputs(outs)
 
     @staticmethod
-    def backward(ctx, gout, *gmaps):
-        gmaps = gmaps[:len(gmaps) - ctx.n_contrib_out]  # (the statistics and absgrad are not differentiable)
-        gdepth, galpha = gmaps[:2] if ctx.depth_alpha else (None, None)
-        gfeat = gmaps[-1] if ctx.has_features else None
-        if gout is None and gdepth is None and galpha is None and gfeat is None:
-            return (None,) * 17
+    def backward(ctx, *grads):
+        opts = ctx.opts
+        g = _RZ._unpack_outputs(opts, grads, radii=False)  # (None for the statistics and absgrad: not differentiable)
+        if g.color is None and g.depth is None and g.alpha is None and g.feat is None:
+            return (None,) * len(ctx.needs_input_grad)
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
-        g = gout.detach().to(dtype=torch.float32).contiguous() if gout is not None else None
-        gd = gdepth.detach().to(dtype=torch.float32).contiguous() if gdepth is not None else None
-        ga = galpha.detach().to(dtype=torch.float32).contiguous() if galpha is not None else None
-        gf = gfeat.detach().to(dtype=torch.float32).contiguous() if gfeat is not None else None
-        d_feat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev) if ctx.feat_grad else None  # batch-wide, each view writes its rows
+        f32c = _RZ._map_grad  # fp32, contiguous
+        g = _RZ._Outputs(color=f32c(g.color), depth=f32c(g.depth), alpha=f32c(g.alpha), feat=f32c(g.feat))
+        d_feat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev) if ctx.feat_shape is not None else None  # batch-wide, each view writes its rows
         # one gradient buffer per packed tensor (+ one for the unused screen-space gradient); every view's backward writes its own
         # rows, rows behind offsets[-1] (the unused tail of the packed capacity) are never read by the pack backward
         d_xyz, d_rgb, d_rot, d_scale, d_op = (torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes)
         d_m2 = torch.empty(ctx.shapes[0], dtype=torch.float32, device=dev)
         # camera gradients: [B, 16], [B, 16], [B, 3] on the device, sample i's rows written by its own backward
         cam_all = None
-        if ctx.camera_grad:
+        if opts.camera_grad:
             cam_all = tuple(torch.empty((len(views), n), dtype=torch.float32, device=dev) if w and t is not None else None
-                            for w, t, n in zip(ctx.needs_input_grad[11:14], ctx.cams, (16, 16, 3)))
+                            for w, t, n in zip(ctx.needs_input_grad[9:12], ctx.cams, (16, 16, 3)))
         cur = torch.cuda.current_stream(dev)
         for i, h in enumerate(views):
             if side[i] is not cur:
                 side[i].wait_stream(cur)
-            ins = h.own if h.own is not None else (xyz, rgb, opacity.reshape(-1), scale, rot)
-            with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.ws_box in there)
-                _RZ._backward_impl(h, tuple(ins) + tuple(h.tail), g[i] if g is not None else None, (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2),
-                                   ctx.color_grad, gd[i] if gd is not None else None, ga[i] if ga is not None else None,
-                                   None if cam_all is None else tuple(c[i] if c is not None else None for c in cam_all),
-                                   gf[i] if gf is not None else None, d_feat)
+            s = h.saved if h.saved.m3 is not None else h.saved._replace(m3=xyz, col=rgb, opa=opacity.reshape(-1), sca=scale, rot=rot)
+            with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.view.ws_box in there)
+                _RZ._backward_impl(h, s, _RZ._Outputs(color=_row(g.color, i), depth=_row(g.depth, i), alpha=_row(g.alpha, i), feat=_row(g.feat, i)),
+                                   (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2), ctx.color_grad,
+                                   None if cam_all is None else tuple(_row(c, i) for c in cam_all), d_feat)
         for i in range(len(views)):
             if side[i] is not cur:
                 cur.wait_stream(side[i])
-        if ctx.absgrad_sink is not None:  # (every view's rows of ctx.absgrad_out are written: the holders carry the tensor)
-            ctx.absgrad_sink(ctx.absgrad_out)
+        if opts.absgrad_sink is not None:  # (every view's rows of ctx.absgrad_out are written: the holders carry the tensor)
+            opts.absgrad_sink(ctx.absgrad_out)
         d_cam = (None, None, None)
         if cam_all is not None:
             d_cam = tuple(_RZ._cam_grad_as(c, t) for c, t in zip(cam_all, ctx.cams))
-        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, None, None) + d_cam + (d_feat, None, None)
+        return (d_xyz, (d_rgb if ctx.color_grad else None), d_rot, d_scale, d_op, None, None, None, None, *d_cam, d_feat)[:len(ctx.needs_input_grad)]
 
 
 def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False):
@@ -220,23 +216,27 @@ def render(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, gr
     (grad_arena: internal, see pts2render.)  antialiasing=True: the opacity-compensated 2D filter (rasterizer.rasterize_gaussians).
     camera_grad=True: data['novel_view']['world_view_transform'], ['full_proj_transform'] and ['camera_center'] receive the gradient of
     sample idx's camera (through their [idx] slices) when they require one."""
-    nv = data['novel_view']
+    opts = _RZ._view_options(None, False, antialiasing, camera_grad)
+    return _render_view(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena, opts, retain_grad=True).color
+
+
+def _render_view(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena, opts, features=None, retain_grad=False):
+    """One novel view with the opt-ins of `opts` (a rasterizer._ViewOptions) -> rasterizer._Outputs.  Through the GaussianRasterizer module, as the
+    reference's render() goes: constructing it is what arms the opt-in accelerate hooks on first use.  retain_grad: the screen-space points keep
+    their gradient, as the reference's render() asks (render_ex never did)."""
     bg = _bg_tensor(bg_color, pts_xyz.device)
     screenspace_points = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
-    try:
-        screenspace_points.retain_grad()
-    except Exception:
-        pass
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(nv['height'][idx]), image_width=int(nv['width'][idx]),
-        tanfovx=math.tan(_scalar(nv['FovX'][idx]) * 0.5), tanfovy=math.tan(_scalar(nv['FovY'][idx]) * 0.5),
-        bg=bg, scale_modifier=1.0, viewmatrix=nv['world_view_transform'][idx], projmatrix=nv['full_proj_transform'][idx],
-        sh_degree=3, campos=nv['camera_center'][idx], prefiltered=False, debug=False)
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
-    rendered_image, _ = rasterizer(means3D=pts_xyz, means2D=screenspace_points, shs=None, colors_precomp=pts_rgb,
-                                   opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena,
-                                   antialiasing=antialiasing, camera_grad=camera_grad)
-    return rendered_image
+    if retain_grad:
+        try:
+            screenspace_points.retain_grad()
+        except Exception:
+            pass
+    rasterizer = GaussianRasterizer(raster_settings=_settings(data['novel_view'], idx, bg))
+    out = rasterizer(means3D=pts_xyz, means2D=screenspace_points, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
+                     rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=opts.depth_alpha,
+                     antialiasing=opts.antialiasing, camera_grad=opts.camera_grad, features=features, return_contrib=opts.contrib,
+                     return_absgrad=opts.absgrad_sink or opts.absgrad)
+    return _RZ._unpack_outputs(opts, out)
 
 
 def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False,
@@ -253,21 +253,15 @@ def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color,
     features.  absgrad=True: also 'absgrad' (fp32 [P, 2]), the absolute screen-space gradient sum_p |dL_p/dmean2D_i| in the units of the screen-space
     gradient: zeros until a backward through the view has run, then overwritten in place by each one; not differentiable
     (rasterizer.rasterize_gaussians(return_absgrad=True)); not with features."""
-    nv = data['novel_view']
-    bg = _bg_tensor(bg_color, pts_xyz.device)
-    means2D = torch.zeros_like(pts_xyz, dtype=torch.float32, requires_grad=True, device=pts_xyz.device) + 0
-    rasterizer = GaussianRasterizer(raster_settings=_settings(nv, idx, bg))
-    out = rasterizer(means3D=pts_xyz, means2D=means2D, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
-                     rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=True, antialiasing=antialiasing,
-                     camera_grad=camera_grad, features=features, return_contrib=contrib, return_absgrad=absgrad)
-    r = {'img': out[0], 'depth': out[2], 'alpha': out[3]}
-    if features is not None:
-        r['feat'] = out[4]
-    if absgrad:
-        r['absgrad'] = out[-1]
-        out = out[:-1]
-    if contrib:
-        r['contrib_weight'], r['contrib_max'], r['contrib_pixels'] = out[-3:]
+    opts = _RZ._view_options(None, True, antialiasing, camera_grad, features, contrib, absgrad)
+    o = _render_view(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena, opts, features)
+    r = {'img': o.color, 'depth': o.depth, 'alpha': o.alpha}
+    if opts.features:
+        r['feat'] = o.feat
+    if opts.absgrad:
+        r['absgrad'] = o.absgrad
+    if opts.contrib:
+        r['contrib_weight'], r['contrib_max'], r['contrib_pixels'] = o.contrib_weight, o.contrib_max, o.contrib_pixels
     return r
 
 
@@ -324,6 +318,19 @@ def _fill_absgrad_maps(maps, absgrad, rows, first_row=0):
         m.copy_(vals[:, v].permute(0, 2, 1).reshape(m.shape))
 
 
+def _write_outputs(data, o, row_of_pixel):
+    """The batch-wide rasterizer._Outputs of a pts2render call -> data['novel_view']['img_pred'], 'depth_pred' / 'alpha_pred', 'feat_pred' and the
+    contribution maps of the source views.  (The absgrad maps exist already -- _absgrad_maps -- and are filled by the backward.)"""
+    nv = data['novel_view']
+    nv['img_pred'] = o.color
+    if o.depth is not None:
+        nv['depth_pred'], nv['alpha_pred'] = o.depth, o.alpha
+    if o.feat is not None:
+        nv['feat_pred'] = o.feat
+    if o.contrib_weight is not None:
+        _write_contrib_maps(data, (o.contrib_weight, o.contrib_max, o.contrib_pixels), row_of_pixel)
+
+
 def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None, with_contrib=False,
                with_absgrad=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
@@ -355,14 +362,14 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         raise RuntimeError("gps_gaussian_amd: with_contrib cannot be combined with feature_key")
     if with_absgrad and feature_key is not None:
         raise RuntimeError("gps_gaussian_amd: with_absgrad cannot be combined with feature_key (features)")
-    if with_contrib or with_absgrad:
+    if with_contrib or with_absgrad or feature_key is not None:
         xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
-    elif feature_key is None:
-        xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
+        if feature_key is not None:
+            from .pack import pack_features
+            feats = pack_features(data, feature_key, row_of_pixel)
     else:
-        from .pack import pack_features
-        xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
-        feats = pack_features(data, feature_key, row_of_pixel)
+        xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
+    opts = _RZ._view_options(None, with_depth_alpha, antialiasing, camera_grad, feats, with_contrib, with_absgrad)
     nv = data['novel_view']
     dev = xyz.device
     sizes_hw = {(int(nv['height'][i]), int(nv['width'][i])) for i in range(bs)}
@@ -370,57 +377,23 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         bg = _bg_tensor(bg_color, dev)
         view, proj = _to_device_once(nv['world_view_transform'], dev), _to_device_once(nv['full_proj_transform'], dev)
         settings = [_settings(nv, i, bg, view, proj) for i in range(bs)]
-        if with_absgrad:
+        if opts.absgrad:
             amaps = _absgrad_maps(data)
-            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
-            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
-                                     bool(camera_grad), *cams, None, bool(with_contrib), lambda a: _fill_absgrad_maps(amaps, a, row_of_pixel))
-            nv['img_pred'] = out[0]
-            if with_depth_alpha:
-                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
-            if with_contrib:
-                _write_contrib_maps(data, out[-4:-1], row_of_pixel)
-        elif with_contrib:
-            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
-            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
-                                     bool(camera_grad), *cams, None, True)
-            nv['img_pred'] = out[0]
-            if with_depth_alpha:
-                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
-            _write_contrib_maps(data, out[-3:], row_of_pixel)
-        elif feats is not None:
-            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if camera_grad else (None, None, None)
-            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
-                                     bool(camera_grad), *cams, feats)
-            nv['img_pred'] = out[0]
-            if with_depth_alpha:
-                nv['depth_pred'], nv['alpha_pred'] = out[1], out[2]
-            nv['feat_pred'] = out[-1]
-        elif camera_grad:
-            cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center'])
-            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, bool(with_depth_alpha), bool(antialiasing),
-                                     True, *cams)
-            if with_depth_alpha:
-                nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = out
-            else:
-                nv['img_pred'] = out
-        elif with_depth_alpha:
-            nv['img_pred'], nv['depth_pred'], nv['alpha_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, True,
-                                                                                    bool(antialiasing))
-        elif antialiasing:
-            nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, False, True)
+            opts = opts._replace(absgrad_sink=lambda a: _fill_absgrad_maps(amaps, a, row_of_pixel))
+        cams = (nv['world_view_transform'], nv['full_proj_transform'], nv['camera_center']) if opts.camera_grad else (None, None, None)
+        if opts == _RZ._DEFAULT_OPTIONS:  # the default call keeps the eight arguments it always had (rasterizer._rasterize says why)
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
         else:
-            nv['img_pred'] = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs)  # no read-back of the offsets
+            out = _RenderBatch.apply(xyz, rgb, rot, scale, opacity, offsets, settings, xyz.shape[0] // bs, opts, *cams, feats)
+        _write_outputs(data, _RZ._unpack_outputs(opts, out, radii=False), row_of_pixel)
         return data
-    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), with_depth_alpha, antialiasing, camera_grad, feats,
-                            row_of_pixel if with_contrib else None, row_of_pixel if with_absgrad else None)
+    return _pts2render_loop(data, bg_color, (xyz, rgb, rot, scale, opacity), offsets.tolist(), opts, feats, row_of_pixel)
 
 
-def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antialiasing=False, camera_grad=False, feats=None, row_of_pixel=None,
-                     absgrad_rows=None):
-    """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream.  row_of_pixel (pack_views'): the
-    contribution statistics are wanted (pts2render(with_contrib=True)); absgrad_rows (pack_views' row_of_pixel too): the absgrad maps are
-    (pts2render(with_absgrad=True)) -- every sample's node fills its slice of them in its backward."""
+def _pts2render_loop(data, bg_color, packed, offs, opts=_RZ._DEFAULT_OPTIONS, feats=None, row_of_pixel=None):
+    """The per-sample form: one render() (one rasteriser autograd node) per sample, on the current stream.  opts: the call's
+    rasterizer._ViewOptions; row_of_pixel (pack_views'): needed with opts.contrib (the statistics go back to their source pixels) and with
+    opts.absgrad (every sample's node fills its slice of the absgrad maps in its backward)."""
     bs = data['lmain']['img'].shape[0]
     xyz, rgb, rot, scale, opacity = packed
     # ONE split per packed tensor (its backward is one concatenation of the per-sample gradients); B Python slices would make
@@ -445,43 +418,39 @@ def _pts2render_loop(data, bg_color, packed, offs, with_depth_alpha=False, antia
     # batch loop is host-bound, tools/stage2_ab.py -- the reason _RenderBatch exists)
     concurrent = bs > 1 and not torch.cuda.is_current_stream_capturing() and os.environ.get("GPSGS_PTS2RENDER_STREAMS", "0") == "1"
     side = _streams(dev, bs) if concurrent else [cur] * bs
-    amaps = _absgrad_maps(data) if absgrad_rows is not None else None
+    amaps = _absgrad_maps(data) if opts.absgrad else None
+    # any map or statistic is wanted: every sample is rendered as render_ex renders it, with the depth / alpha maps too; else as render() does
+    full = opts.depth_alpha or opts.features or opts.contrib or opts.absgrad
+    view_opts = opts._replace(depth_alpha=True) if full else opts
     with _RZ.defer_capacity_checks():
         for i in range(bs):
             # arena order expected by the rasteriser: means3D, colours, opacities, scales, rotations
             ga = (a_parts[0][i], a_parts[1][i], a_parts[4][i], a_parts[3][i], a_parts[2][i]) if a_parts is not None else None
             if side[i] is not cur:
                 side[i].wait_stream(cur)
+            sink = None
+            if amaps is not None:  # sample i's rows start at offs[i] of the packed order row_of_pixel speaks of
+                def sink(a, i=i):
+                    _fill_absgrad_maps([m[i:i + 1] for m in amaps], a, row_of_pixel[i:i + 1], offs[i])
             with torch.cuda.stream(side[i]):
-                if with_depth_alpha or feats is not None or row_of_pixel is not None or amaps is not None:
-                    sink = False
-                    if amaps is not None:  # sample i's rows start at offs[i] of the packed order row_of_pixel speaks of
-                        def sink(a, i=i):
-                            _fill_absgrad_maps([m[i:i + 1] for m in amaps], a, absgrad_rows[i:i + 1], offs[i])
-                    r = render_ex(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color, grad_arena=ga,
-                                  antialiasing=antialiasing, camera_grad=camera_grad, features=f_parts[i] if feats is not None else None,
-                                  contrib=row_of_pixel is not None, absgrad=sink)
-                    out.append(tuple(r[k].unsqueeze(0) for k in ('img', 'depth', 'alpha') + (('feat',) if feats is not None else ()))
-                               + (tuple(r[k] for k in _CONTRIB_KEYS) if row_of_pixel is not None else ()))
-                else:
-                    out.append((render(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color=bg_color,
-                                       grad_arena=ga, antialiasing=antialiasing, camera_grad=camera_grad).unsqueeze(0),))
+                out.append(_render_view(data, i, parts[0][i], parts[1][i], parts[2][i], parts[3][i], parts[4][i], bg_color, ga,
+                                        view_opts._replace(absgrad_sink=sink), f_parts[i] if feats is not None else None, retain_grad=not full))
     for i in range(bs):
         if side[i] is not cur:
             cur.wait_stream(side[i])
-            for t in out[i]:
+            for t in _RZ._pack_outputs(out[i]):
                 t.record_stream(cur)
-    nv = data['novel_view']
-    nv['img_pred'] = torch.cat([o[0] for o in out], dim=0)
-    if with_depth_alpha:
-        nv['depth_pred'] = torch.cat([o[1] for o in out], dim=0)
-        nv['alpha_pred'] = torch.cat([o[2] for o in out], dim=0)
-    if feats is not None:
-        nv['feat_pred'] = torch.cat([o[3] for o in out], dim=0)
-    if row_of_pixel is not None:  # the samples' statistics in packed row order (rows behind offs[bs] are never looked up: zeros)
-        tail = xyz.shape[0] - offs[bs]
-        stats = [torch.cat([o[-3 + k] for o in out] + [out[0][-3 + k].new_zeros((tail,))]) for k in range(3)]
-        _write_contrib_maps(data, stats, row_of_pixel)
+
+    def batch(name):
+        return torch.cat([getattr(o, name).unsqueeze(0) for o in out], dim=0)
+
+    def packed_rows(name):  # the samples' statistics in packed row order (rows behind offs[bs] are never looked up: zeros)
+        return torch.cat([getattr(o, name) for o in out] + [getattr(out[0], name).new_zeros((xyz.shape[0] - offs[bs],))])
+
+    stats = {k: packed_rows(k) for k in _CONTRIB_KEYS} if opts.contrib else {}
+    whole = _RZ._Outputs(color=batch('color'), depth=batch('depth') if opts.depth_alpha else None, alpha=batch('alpha') if opts.depth_alpha else None,
+                         feat=batch('feat') if opts.features else None, **stats)
+    _write_outputs(data, whole, row_of_pixel)
     return data
 
 

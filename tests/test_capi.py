@@ -66,6 +66,50 @@ def test_workspace_bytes_monotone_and_aligned():
     assert lib.gsr_workspace_bytes(-1, 16, 16, 1) == 0
 
 
+# (P, W, H, cap, bin_cap, forward_only, F) -> gsr_workspace_bytes, _forward_only, _ex, _depth_alpha, _features, _contrib, _absgrad, recorded from the library
+# of commit 346b1f4 (before the seven functions shared one helper): bin_cap 0 / 1024 (and 64), F = 1 / 64, images that cannot have direct lists
+# (4096^2), the largest capacity, and arguments each function refuses (0): a bin capacity no direct list can have, F = 0 / 65, a negative P / width /
+# height / capacity
+_RECORDED_SIZES = [
+    ((30000, 256, 256, 1048576, 0, 0, 3), (54450688, 15533056, 54450688, 58644992, 71227904, 75422208, 67033600)),
+    ((30000, 256, 256, 1048576, 0, 1, 3), (54450688, 15533056, 15533056, 15533056, 15533056, 75422208, 67033600)),
+    ((30000, 256, 256, 1048576, 1024, 0, 1), (54450688, 15533056, 54450944, 58645248, 62839552, 75422464, 67033856)),
+    ((30000, 256, 256, 1048576, 1024, 1, 64), (54450688, 15533056, 15533056, 15533056, 15533056, 75422464, 67033856)),
+    ((600000, 1024, 1024, 5242880, 1024, 0, 64), (316044032, 119652352, 454462464, 475433984, 1817611264, 559320064, 517377024)),
+    ((600000, 1024, 1024, 5242880, 0, 0, 1), (316044032, 119652352, 316044032, 337015552, 357987072, 420901632, 378958592)),
+    ((200, 44, 28, 65536, 1024, 0, 3), (3246080, 819968, 2853120, 3115264, 3901696, 4163840, 3639552)),
+    ((200, 44, 28, 65536, 0, 1, 3), (3246080, 819968, 819968, 819968, 819968, 4556800, 4032512)),
+    ((1, 8, 8, 1024, 0, 0, 3), (61952, 23552, 61952, 66048, 78336, 82432, 74240)),
+    ((0, 8, 8, 0, 0, 0, 1), (13056, 11776, 13056, 13312, 13568, 13568, 13568)),
+    ((0, 0, 0, 0, 0, 0, 1), (13056, 11776, 13056, 13312, 13568, 13568, 13568)),
+    ((1, 1, 1, 1, 64, 0, 64), (13056, 11776, 15872, 16128, 16384, 16384, 16384)),
+    ((288, 24, 20, 65536, 1024, 0, 3), (3245568, 819200, 2606848, 2868992, 3655424, 3917568, 3393280)),
+    ((100000, 2048, 2048, 4194304, 1024, 0, 8), (248799232, 93208832, 1003781120, 1020558336, 1154776064, 1087667200, 1054112768)),
+    ((100000, 4096, 4096, 4194304, 1024, 0, 8), (353400832, 197810432, 0, 0, 0, 0, 0)),
+    ((100000, 4096, 4096, 4194304, 0, 0, 8), (353400832, 197810432, 353400832, 370178048, 504395776, 437286912, 403732480)),
+    ((5, 1000, 7, 2147483647, 0, 1, 2), (105226768128, 25769872640, 25769872640, 25769872640, 25769872640, 148176441088, 130996571904)),
+    ((30000, 256, 256, 1048576, 100, 0, 3), (54450688, 15533056, 0, 0, 0, 0, 0)),
+    ((30000, 256, 256, 1048576, 2048, 0, 3), (54450688, 15533056, 0, 0, 0, 0, 0)),
+    ((30000, 256, 256, 1048576, 0, 0, 0), (54450688, 15533056, 54450688, 58644992, 0, 75422208, 67033600)),
+    ((30000, 256, 256, 1048576, 0, 0, 65), (54450688, 15533056, 54450688, 58644992, 0, 75422208, 67033600)),
+    ((-1, 256, 256, 1048576, 0, 0, 3), (0, 0, 0, 0, 0, 0, 0)),
+    ((30000, -1, 256, 1048576, 1024, 0, 3), (0, 0, 0, 0, 0, 0, 0)),
+    ((30000, 256, -1, 1048576, 0, 1, 3), (0, 0, 0, 0, 0, 0, 0)),
+    ((30000, 256, 256, -1, 0, 0, 3), (0, 0, 0, 0, 0, 0, 0)),
+]
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    lib = _capi.lib()
+    for (P, W, H, cap, bcap, fo, F), want in _RECORDED_SIZES:
+        got = (lib.gsr_workspace_bytes(P, W, H, cap), lib.gsr_workspace_bytes_forward_only(P, W, H, cap), lib.gsr_workspace_bytes_ex(P, W, H, cap, bcap, fo),
+               lib.gsr_workspace_bytes_depth_alpha(P, W, H, cap, bcap, fo), lib.gsr_workspace_bytes_features(P, W, H, cap, bcap, F, fo),
+               lib.gsr_workspace_bytes_contrib(P, W, H, cap, bcap, fo), lib.gsr_workspace_bytes_absgrad(P, W, H, cap, bcap))
+        assert got == want, (P, W, H, cap, bcap, fo, F)
+    for k in range(7):  # every function has a case it sizes and one it refuses
+        assert any(w[k] > 0 for _, w in _RECORDED_SIZES) and any(w[k] == 0 for _, w in _RECORDED_SIZES)
+
+
 def test_workspace_bytes_ex_and_the_limits_of_direct_lists():
     lib = _capi.lib()
     for args in ((1000, 256, 256, 10000), (600000, 1024, 1024, 4_000_000), (0, 16, 16, 0)):

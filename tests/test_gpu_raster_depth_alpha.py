@@ -321,11 +321,12 @@ def test_misaligned_output_pointers():
     # torch outputs at an odd element offset (4- but not 16-byte aligned): written exactly like aligned ones
     from types import SimpleNamespace
     rs = RZ.GaussianRasterizationSettings(H, W, g["tanfovx"], g["tanfovy"], t["bg"], 1.0, t["view"], t["proj"], 3, torch.zeros(3, device=dev), False, False)
-    ref = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, depth_alpha=True)
+    opts = RZ._view_options(rs, depth_alpha=True)
+    ref = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, opts)
     big = torch.full((2 * H * W + 3,), -7.0, device=dev)
     od, oa = big[1:1 + H * W].view(H, W), big[2 + H * W:2 + 2 * H * W].view(H, W)
-    out = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, depth_alpha=True,
-                           out_depth=od, out_alpha=oa)
+    out = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, opts,
+                           out=dict(depth=od, alpha=oa))
     torch.cuda.synchronize()
     assert torch.equal(out[2], ref[2].reshape(H, W)) and torch.equal(out[3], ref[3].reshape(H, W))
     assert float(big[0]) == -7.0 and float(big[1 + H * W]) == -7.0 and float(big[-1]) == -7.0
