@@ -10,9 +10,6 @@
 
 namespace {
 
-inline uint8_t *at(void *ws, size_t off) { return reinterpret_cast<uint8_t *>(ws) + off; }
-inline const uint8_t *at(const void *ws, size_t off) { return reinterpret_cast<const uint8_t *>(ws) + off; }
-
 // GPSGS_TRACE=1 (environment): every rasteriser stage announces itself on stderr before its launch and is synchronised after it --
 // a device fault then names the stage that was running (a GPU memory fault aborts the process; there is nothing to return).
 inline bool trace_on() {
@@ -143,13 +140,12 @@ extern "C" int gsr_supported_flags(void) {
 extern "C" const char *gpsgs_build_info(void) { return "gfx950 hipcc " __VERSION__ " built " __DATE__; }
 
 namespace {
-// What every gsr_workspace_bytes_* function reports: 0 for invalid arguments (a bin capacity that direct lists cannot have included), the forward-only
-// size, or the training layout (`extra`: with the depth / alpha slot array) plus the opt-in `tail` behind it.
-size_t workspace_size(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only, bool extra, size_t tail) {
+// What every gsr_workspace_bytes_* function reports: 0 for invalid arguments (a bin capacity that direct lists cannot have included), else what a call
+// with these needs demands (gsr_workspace_need)
+size_t workspace_size(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, const GsrWorkspaceNeed &need) {
     if (P < 0 || width < 0 || height < 0 || instance_capacity < 0) return 0;
     if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return 0;
-    const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
-    return forward_only ? L.total_fwd : (extra ? L.total_extra : L.total) + tail;
+    return gsr_workspace_need(gsr_layout(P, width, height, instance_capacity, bin_capacity), instance_capacity, need);
 }
 }  // namespace
 
@@ -161,36 +157,85 @@ extern "C" int gsr_direct_lists_ok(int width, int height, uint32_t bin_capacity)
 }
 
 extern "C" size_t gsr_workspace_bytes(int P, int width, int height, int64_t instance_capacity) {
-    return workspace_size(P, width, height, instance_capacity, 0u, 0, false, 0);
+    return workspace_size(P, width, height, instance_capacity, 0u, {false, false, 0, false, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_forward_only(int P, int width, int height, int64_t instance_capacity) {
-    return workspace_size(P, width, height, instance_capacity, 0u, 1, false, 0);
+    return workspace_size(P, width, height, instance_capacity, 0u, {true, false, 0, false, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_ex(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
-    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, false, 0);
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, {forward_only != 0, false, 0, false, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_depth_alpha(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
-    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, true, 0);
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, {forward_only != 0, true, 0, false, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_features(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int channels, int forward_only) {
     if (channels < 1 || channels > GSR_MAX_FEATURES) return 0;
-    return workspace_size(P, width, height, instance_capacity, bin_capacity, forward_only, true, gsr_feature_tail_bytes(instance_capacity, channels));
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, {forward_only != 0, true, channels, false, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_contrib(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, int forward_only) {
     (void)forward_only;  // (the same size: the statistics read the slot prefix of the backward tail)
-    return workspace_size(P, width, height, instance_capacity, bin_capacity, 0, true, gsr_contrib_tail_bytes(instance_capacity));
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, {false, true, 0, true, false});
 }
 
 extern "C" size_t gsr_workspace_bytes_absgrad(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity) {
-    return workspace_size(P, width, height, instance_capacity, bin_capacity, 0, true, gsr_absgrad_tail_bytes(instance_capacity));
+    return workspace_size(P, width, height, instance_capacity, bin_capacity, {false, true, 0, false, true});
 }
 
 namespace {
+// What the forward and backward entry points receive: the view (GSR_VIEW_CALL fills it from the argument names they all share), then each direction's own
+struct ViewCall {
+    int P, width, height;
+    const float *means3D, *colors, *opacities, *scales, *rotations;
+    float scale_modifier, tanfovx, tanfovy;
+    const float *viewmatrix, *projmatrix, *bg;
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t instance_capacity;
+    unsigned flags;
+    void *stream;
+    const GsrViewExt *ext;
+};
+#define GSR_VIEW_CALL(ext_)                                                                                                                          \
+    {P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg, workspace, workspace_bytes, \
+     instance_capacity, flags, stream, ext_}
+struct ForwardCall : ViewCall {
+    float *out_color;
+    int *radii;
+    void *host_header_out;
+    uint32_t notify_seq;
+    const GsrFeatures *feat;     // gsr_forward_features
+    const GsrContrib *contrib;   // gsr_forward_contrib
+};
+struct BackwardCall : ViewCall {
+    const int *radii;
+    const float *dL_dpix;
+    float *dL_dmeans3D, *dL_dmeans2D, *dL_dcolors, *dL_dopacity, *dL_dscales, *dL_drotations;
+    const GsrCamGrad *cam;    // gsr_backward_camera / _features / _absgrad with a camera gradient asked for
+    const GsrFeatures *feat;  // gsr_backward_features
+    const GsrAbsGrad *abs;    // gsr_backward_absgrad
+};
+
+// One stage of a call: announced (GPSGS_TRACE), bracketed by an event pair (GSR_FLAG_TIMING), launched, checked
+struct Stages {
+    const ViewCall &c;
+    unsigned flags;  // (the call's, less the tile family where an option has only VALU kernels)
+    hipStream_t s;
+    template <typename Launch>
+    int operator()(const char *name, int stage, Launch &&launch) const {
+        trace(name, c.P, c.width, c.height, (long long)c.instance_capacity, flags);
+        {
+            StageTimer t(flags, stage, s);
+            launch();
+        }
+        return check(s, flags);
+    }
+};
+
 // F-channel feature maps: the channel count of a GsrFeatures (0 = none), or -1 for an invalid one (range, NULL features for P > 0, misaligned pointers)
 int feature_channels(const GsrFeatures *feat, bool backward, int P) {
     if (!feat || feat->channels == 0) return 0;
@@ -202,206 +247,162 @@ int feature_channels(const GsrFeatures *feat, bool backward, int P) {
     return feat->channels;
 }
 
-// gsr_forward_ex, and with feat (gsr_forward_features) the feature maps too
-int forward_impl(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
-                 const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
-                 const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
-                 void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
-                 void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat, const GsrContrib *contrib = nullptr) {
-    const int F = feature_channels(feat, false, P);
+// Self-check between the sort and the compositing (GPSGS_TRACE / GSR_FLAG_DEBUG; synchronises; never in normal operation)
+int validate_lists(int P, int NB, const GsrWorkspace &w, hipStream_t s) {
+    // everything on the caller's stream `s` and checked: PyTorch's side streams do not synchronise with the NULL stream, so a NULL-stream memset of
+    // the counters could land AFTER k_validate_lists' atomics and hide a real inconsistency.  The five counters live in a small
+    // device buffer allocated once per process (a debug forward is never captured, but it no longer allocates per call either).
+    GsrHeader h;
+    unsigned long long h_out[5] = {0, 0, 0, 0, 0};
+    static unsigned long long *d_out_by_dev[64] = {nullptr};
+    int devid = 0;
+    if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return GPSGS_E_LAUNCH;
+    unsigned long long *d_out;
+    {
+        static std::mutex mu;
+        std::lock_guard<std::mutex> g(mu);
+        if (!d_out_by_dev[devid] && hipMalloc(&d_out_by_dev[devid], sizeof(h_out)) != hipSuccess) return GPSGS_E_LAUNCH;
+        d_out = d_out_by_dev[devid];
+    }
+    if (hipMemcpyAsync(&h, w.hdr, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipMemsetAsync(d_out, 0, sizeof(h_out), s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return GPSGS_E_LAUNCH;
+    if (!h.overflow) hipLaunchKernelGGL(k_validate_lists, dim3((NB + 255) / 256), dim3(256), 0, s, P, NB, w.bins, w.bin_cursor, w.point_list, w.splats, d_out);
+    if (hipMemcpyAsync(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return GPSGS_E_LAUNCH;
+    const bool bad = h_out[0] || h_out[1] || h_out[4];
+    if (trace_on() || bad) {
+        fprintf(stderr, "[gpsgs] header: R=%llu overflow=%u longest=%u busy=%u slots=%u points=%u | lists: ids out of range %llu, out of order %llu, non-finite records %llu, "
+                        "bins whose scatter cursor missed its end %llu (longest list with a bad id %llu)\n",
+                (unsigned long long)h.num_rendered, h.overflow, h.max_tile_count, h.num_busy_wgs, h.num_slots, h.num_points, h_out[0], h_out[1], h_out[2], h_out[4], h_out[3]);
+        fflush(stderr);
+    }
+    return bad ? GPSGS_E_INTERNAL : GPSGS_OK;
+}
+
+inline bool misaligned(const void *a, const void *b = nullptr, const void *c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 3u) != 0;
+}
+
+int forward_impl(const ForwardCall &c) {
+    const int P = c.P, width = c.width, height = c.height;
+    const int64_t instance_capacity = c.instance_capacity;
+    const GsrViewExt *ext = c.ext;
+    const int F = feature_channels(c.feat, false, P);
     if (F < 0) return GPSGS_E_INVALID;
-    if (F > 0) flags &= ~GSR_FLAG_COMPOSITE_TILES;  // feature maps: the VALU kernels only (as the depth / alpha maps)
     // contribution statistics (any pointer may be NULL): the VALU family's CONTRIB forward, 16 bytes per instance slot in the workspace's tail
-    float *c_sum = contrib ? contrib->weight_sum : nullptr, *c_max = contrib ? contrib->weight_max : nullptr;
-    int32_t *c_cnt = contrib ? contrib->pixel_count : nullptr;
-    if ((reinterpret_cast<uintptr_t>(c_sum) | reinterpret_cast<uintptr_t>(c_max) | reinterpret_cast<uintptr_t>(c_cnt)) & 3u) return GPSGS_E_INVALID;
-    const bool stats = c_sum || c_max || c_cnt;
-    if (stats && F > 0) return GPSGS_E_INVALID;  // (the two tails share an offset; no entry point passes both)
-    if (stats) flags &= ~GSR_FLAG_COMPOSITE_TILES;
-    const uint32_t *row_range = ext ? ext->row_range : nullptr;
-    const uint32_t order_hint = ext ? ext->order_hint : 0u;
-    // opt-in depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
+    const GsrContrib con = c.contrib ? *c.contrib : GsrContrib{};
+    if (con.reserved || misaligned(con.weight_sum, con.weight_max, con.pixel_count)) return GPSGS_E_INVALID;
+    // opt-in depth / alpha maps
     float *out_depth = ext ? ext->out_depth : nullptr, *out_alpha = ext ? ext->out_alpha : nullptr;
-    if ((reinterpret_cast<uintptr_t>(out_depth) | reinterpret_cast<uintptr_t>(out_alpha)) & 3u) return GPSGS_E_INVALID;
-    if (out_depth || out_alpha) flags &= ~GSR_FLAG_COMPOSITE_TILES;
+    if (misaligned(out_depth, out_alpha)) return GPSGS_E_INVALID;
+    const bool stats = con.weight_sum || con.weight_max || con.pixel_count;
+    if (!gsr_one_tail(F, stats, false)) return GPSGS_E_INVALID;  // (no entry point passes both)
+    // feature maps, statistics, depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
+    const unsigned flags = (F > 0 || stats || out_depth || out_alpha) ? c.flags & ~GSR_FLAG_COMPOSITE_TILES : c.flags;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0 || instance_capacity > 0x7fffffffLL) return GPSGS_E_INVALID;
     if (width > 65535 * GSR_TILE || height > 65535 * GSR_TILE) return GPSGS_E_INVALID;
-    if (!out_color || !workspace) return GPSGS_E_INVALID;
+    if (!c.out_color || !c.workspace) return GPSGS_E_INVALID;
     const float *shs = ext ? ext->shs : nullptr, *cov3D_precomp = ext ? ext->cov3D_precomp : nullptr;
-    if (P > 0 && (!means3D || !opacities || !viewmatrix || !projmatrix || !bg || !radii)) return GPSGS_E_INVALID;
+    if (P > 0 && (!c.means3D || !c.opacities || !c.viewmatrix || !c.projmatrix || !c.bg || !c.radii)) return GPSGS_E_INVALID;
     // exactly one of (colors, shs) and exactly one of (scales + rotations, cov3D_precomp): upstream's GaussianRasterizer.forward raises on both
-    if (P > 0 && ((shs != nullptr) == (colors != nullptr) || (cov3D_precomp != nullptr) == (scales != nullptr && rotations != nullptr))) return GPSGS_E_INVALID;
-    if (P > 0 && cov3D_precomp && (scales || rotations)) return GPSGS_E_INVALID;
+    if (P > 0 && ((shs != nullptr) == (c.colors != nullptr) || (cov3D_precomp != nullptr) == (c.scales != nullptr && c.rotations != nullptr))) return GPSGS_E_INVALID;
+    if (P > 0 && cov3D_precomp && (c.scales || c.rotations)) return GPSGS_E_INVALID;
     if (shs && (!ext->campos || ext->sh_degree > 3u || ext->sh_coeffs > 16u || (ext->sh_degree + 1u) * (ext->sh_degree + 1u) > ext->sh_coeffs)) return GPSGS_E_INVALID;
     const uint32_t bin_cap = ext ? ext->bin_capacity : 0u;  // direct lists: a fixed-capacity segment per bin (GsrBins)
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
-    if (workspace_bytes < L.total_fwd) return GPSGS_E_WORKSPACE;  // the backward tail is optional for a forward
-    if (stats && workspace_bytes < L.total_extra + gsr_contrib_tail_bytes(instance_capacity)) return GPSGS_E_WORKSPACE;  // (then a training workspace)
-    hipStream_t s = (hipStream_t)stream;
+    if (c.workspace_bytes < gsr_workspace_need(L, instance_capacity, {true, false, 0, stats, false})) return GPSGS_E_WORKSPACE;  // the backward tail is optional, but not for the statistics
+    hipStream_t s = (hipStream_t)c.stream;
     uint32_t *host_hdr = nullptr;
-    if (host_header_out) {  // must be pinned (hipHostMalloc / hipHostRegister) memory the device can write
+    if (c.host_header_out) {  // must be pinned (hipHostMalloc / hipHostRegister) memory the device can write
         void *dptr = nullptr;
-        if (notify_seq == 0 || hipHostGetDevicePointer(&dptr, host_header_out, 0) != hipSuccess || !dptr) {
+        if (c.notify_seq == 0 || hipHostGetDevicePointer(&dptr, c.host_header_out, 0) != hipSuccess || !dptr) {
             (void)hipGetLastError();
             return GPSGS_E_INVALID;
         }
         host_hdr = static_cast<uint32_t *>(dptr);
     }
-    GsrHeader *hdr = reinterpret_cast<GsrHeader *>(at(workspace, L.header));
-    uint32_t *bin_count = reinterpret_cast<uint32_t *>(at(workspace, L.bin_count));
-    uint32_t *bin_count_fb = reinterpret_cast<uint32_t *>(at(workspace, L.bin_count_fb));
-    uint32_t *bin_offset = reinterpret_cast<uint32_t *>(at(workspace, L.bin_offset));
-    uint32_t *bin_cursor = reinterpret_cast<uint32_t *>(at(workspace, L.bin_cursor));
-    uint32_t *wg_order = reinterpret_cast<uint32_t *>(at(workspace, L.wg_order));
-    uint4 *scan_part = reinterpret_cast<uint4 *>(at(workspace, L.scan_part));
-    GsrSplat *splats = reinterpret_cast<GsrSplat *>(at(workspace, L.splats));
-    uint4 *binrec = reinterpret_cast<uint4 *>(at(workspace, L.binrec));
-    uint32_t *wg_tab = reinterpret_cast<uint32_t *>(at(workspace, L.wg_tab));
-    uint64_t *keys = reinterpret_cast<uint64_t *>(at(workspace, L.keys));
-    uint32_t *point_list = reinterpret_cast<uint32_t *>(at(workspace, L.point_list));
-    float *final_T = reinterpret_cast<float *>(at(workspace, L.final_T));
-    uint32_t *n_contrib = reinterpret_cast<uint32_t *>(at(workspace, L.n_contrib));
+    // a workspace that includes the backward tail gets the per-Gaussian slot prefix and cleared record flags from the forward
+    const bool training = c.workspace_bytes >= L.total;
+    const GsrWorkspace w = gsr_workspace_map(c.workspace, L, training);
 
     // header + scan partials (their ready flags) + bin_count + bin_count_fb (+ bin_cursor with direct lists, where no scan initialises it) are adjacent
     {
         const size_t zb = (bin_cap ? L.bin_offset : L.bin_cursor) - L.header;  // sections are 256-byte aligned: a whole number of 16-byte words
-        if ((zb & 15u) == 0 && (reinterpret_cast<uintptr_t>(hdr) & 15u) == 0) {
+        if ((zb & 15u) == 0 && (reinterpret_cast<uintptr_t>(w.hdr) & 15u) == 0) {
             const uint32_t n16 = (uint32_t)(zb >> 4);
-            hipLaunchKernelGGL(k_zero16, dim3((n16 + 255u) / 256u), dim3(256), 0, s, reinterpret_cast<uint4 *>(hdr), n16);
+            hipLaunchKernelGGL(k_zero16, dim3((n16 + 255u) / 256u), dim3(256), 0, s, reinterpret_cast<uint4 *>(w.hdr), n16);
             if (hipGetLastError() != hipSuccess) return GPSGS_E_LAUNCH;  // stale scan flags / bin counts would corrupt the whole view
-        } else if (hipMemsetAsync(hdr, 0, zb, s) != hipSuccess) {
+        } else if (hipMemsetAsync(w.hdr, 0, zb, s) != hipSuccess) {
             return GPSGS_E_LAUNCH;
         }
     }
     if (P == 0) {  // upstream returns its zero-initialised image (NOT the background) when there is nothing to draw
-        if (hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
-        if (out_depth && hipMemsetAsync(out_depth, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
-        if (out_alpha && hipMemsetAsync(out_alpha, 0, sizeof(float) * (size_t)width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
-        if (F > 0 && hipMemsetAsync(feat->out_features, 0, sizeof(float) * (size_t)F * width * height, s) != hipSuccess) return GPSGS_E_LAUNCH;
-        if (hipMemsetAsync(bin_offset, 0, (size_t)(L.NB + 1) * 4, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        const size_t map_bytes = sizeof(float) * (size_t)width * height;
+        if (hipMemsetAsync(c.out_color, 0, 3 * map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (out_depth && hipMemsetAsync(out_depth, 0, map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (out_alpha && hipMemsetAsync(out_alpha, 0, map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (F > 0 && hipMemsetAsync(c.feat->out_features, 0, (size_t)F * map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (hipMemsetAsync(w.bin_offset, 0, (size_t)(L.NB + 1) * 4, s) != hipSuccess) return GPSGS_E_LAUNCH;
         return check(s, flags);
     }
+    const uint32_t *row_range = ext ? ext->row_range : nullptr;
+    const uint32_t order_hint = ext ? ext->order_hint : 0u;
     GsrFwdParams q;
     q.P = P; q.W = width; q.H = height; q.gx = L.gx; q.gy = L.gy; q.bx = L.bx; q.by = L.by; q.bx_real = L.bx_real;
-    q.means3D = means3D; q.colors = colors; q.opacities = opacities; q.scales = scales; q.rotations = rotations;
-    q.scale_modifier = scale_modifier; q.tanfovx = tanfovx; q.tanfovy = tanfovy;
-    q.view = viewmatrix; q.proj = projmatrix; q.bg = bg; q.out_color = out_color; q.radii = radii; q.cap = instance_capacity;
+    q.means3D = c.means3D; q.colors = c.colors; q.opacities = c.opacities; q.scales = c.scales; q.rotations = c.rotations;
+    q.scale_modifier = c.scale_modifier; q.tanfovx = c.tanfovx; q.tanfovy = c.tanfovy;
+    q.view = c.viewmatrix; q.proj = c.projmatrix; q.bg = c.bg; q.out_color = c.out_color; q.radii = c.radii; q.cap = instance_capacity;
     q.row_range = row_range;
     q.shs = shs; q.campos = shs ? ext->campos : nullptr; q.cov3D_precomp = cov3D_precomp;
     q.sh_degree = shs ? ext->sh_degree : 0u; q.sh_coeffs = shs ? ext->sh_coeffs : 0u;
     q.antialias = (flags & GSR_FLAG_ANTIALIAS) ? 1 : 0;  // (k_preprocess<true>: the record's opacity is opacity * k)
-    const GsrBins bins = {bin_offset, bin_count, bin_count_fb, bin_cap};
-    // a workspace that includes the backward tail gets the per-Gaussian slot prefix and cleared record flags from the forward
-    const bool training = workspace_bytes >= L.total;
-    q.goff = training ? reinterpret_cast<uint32_t *>(at(workspace, L.goff)) : nullptr;
-    q.gpart = training ? reinterpret_cast<uint32_t *>(at(workspace, L.gscan_part)) : nullptr;
-    uint8_t *inst_valid_fwd = training ? reinterpret_cast<uint8_t *>(at(workspace, L.inst_valid)) : nullptr;
+    q.goff = w.goff; q.gpart = w.gscan_part;
     const int n_gblocks = (P + GSR_BIN_THREADS - 1) / GSR_BIN_THREADS;
+    const bool no_large_sort = (flags & GSR_FLAG_NO_LARGE_SORT) != 0, self_check = trace_on() || (flags & GSR_FLAG_DEBUG);
 
     // direct lists + tile family: the forward compositing waves sort their own lists (no sort launch).  Not with the debug self-check, which inspects the
     // sorted lists between the two; GPSGS_FUSED_SORT=0 keeps the separate launch (development: A/B timing)
     static const bool fused_sort_env = [] { const char *e = getenv("GPSGS_FUSED_SORT"); return !(e && e[0] == '0'); }();
-    const bool fused_sort = bin_cap && (flags & GSR_FLAG_COMPOSITE_TILES) && fused_sort_env && !(trace_on() || (flags & GSR_FLAG_DEBUG));
+    const bool fused_sort = bin_cap && (flags & GSR_FLAG_COMPOSITE_TILES) && fused_sort_env && !self_check;
+    const Stages stage = {c, flags, s};
     int rc;
-    {
-        trace("preprocess", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_PREPROCESS, s);
-        gsr_launch_preprocess(q, splats, binrec, wg_tab, bin_count, bin_count_fb, hdr, s);
-    }
-    if ((rc = check(s, flags)) != GPSGS_OK) return rc;
+    if ((rc = stage("preprocess", GSR_STAGE_PREPROCESS, [&] { gsr_launch_preprocess(q, w.splats, w.binrec, w.wg_tab, w.bin_count, w.bin_count_fb, w.hdr, s); })) != GPSGS_OK)
+        return rc;
     if (bin_cap) {
         // direct lists: the scatter needs no offsets (slot = bin x capacity + recorded base + rank), its first workgroups publish the header (also towards the
         // host) and do what is left of the scan (work order, slot prefix) beside the scattering ones
-        {
-            trace("scatter (direct lists)", P, width, height, (long long)instance_capacity, flags);
-            StageTimer t(flags, GSR_STAGE_SCATTER, s);
-            gsr_launch_scatter_direct(P, row_range, L.bx, L.by, L.NB, splats, binrec, wg_tab, bin_count, bin_count_fb, bin_cursor, bin_cap, keys, hdr, instance_capacity, q.gpart,
-                                      training ? reinterpret_cast<uint32_t *>(at(workspace, L.gprefix)) : nullptr, n_gblocks, wg_order, scan_part, order_hint, host_hdr, notify_seq, s);
-        }
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        if (!fused_sort) {
-            trace("sort (direct lists)", P, width, height, (long long)instance_capacity, flags);
-            StageTimer t(flags, GSR_STAGE_SORT, s);
-            gsr_launch_sort_direct(L.NB, bins, wg_order, keys, point_list, hdr, s);
-        }
+        rc = stage("scatter (direct lists)", GSR_STAGE_SCATTER, [&] {
+            gsr_launch_scatter_direct(P, row_range, L.bx, L.by, L.NB, w.splats, w.binrec, w.wg_tab, w.bin_count, w.bin_count_fb, w.bin_cursor, bin_cap, w.keys, w.hdr,
+                                      instance_capacity, w.gscan_part, w.gprefix, n_gblocks, w.wg_order, w.scan_part, order_hint, host_hdr, c.notify_seq, s);
+        });
+        if (rc == GPSGS_OK && !fused_sort)
+            rc = stage("sort (direct lists)", GSR_STAGE_SORT, [&] { gsr_launch_sort_direct(L.NB, w.bins, w.wg_order, w.keys, w.point_list, w.hdr, s); });
     } else {
-        {
-            trace("scan", P, width, height, (long long)instance_capacity, flags);
-            StageTimer t(flags, GSR_STAGE_SCAN, s);
-            gsr_launch_scan(bin_count, bin_count_fb, bin_offset, bin_cursor, wg_order, scan_part, L.NB, L.bx, L.by, instance_capacity, hdr, q.gpart, n_gblocks, host_hdr, notify_seq,
-                            (flags & GSR_FLAG_NO_LARGE_SORT) != 0, order_hint, s);
-        }
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        {
-            trace("scatter", P, width, height, (long long)instance_capacity, flags);
-            StageTimer t(flags, GSR_STAGE_SCATTER, s);
-            gsr_launch_scatter(P, row_range, L.bx, splats, binrec, wg_tab, bin_offset, bin_cursor, keys, hdr, s);
-        }
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        {
-            trace("sort", P, width, height, (long long)instance_capacity, flags);
-            StageTimer t(flags, GSR_STAGE_SORT, s);
-            gsr_launch_sort(L.NB, bin_offset, wg_order, keys, point_list, hdr, (flags & GSR_FLAG_NO_LARGE_SORT) != 0, s);
-        }
+        rc = stage("scan", GSR_STAGE_SCAN, [&] {
+            gsr_launch_scan(w.bin_count, w.bin_count_fb, w.bin_offset, w.bin_cursor, w.wg_order, w.scan_part, L.NB, L.bx, L.by, instance_capacity, w.hdr, w.gscan_part, n_gblocks,
+                            host_hdr, c.notify_seq, no_large_sort, order_hint, s);
+        });
+        if (rc == GPSGS_OK)
+            rc = stage("scatter", GSR_STAGE_SCATTER, [&] { gsr_launch_scatter(P, row_range, L.bx, w.splats, w.binrec, w.wg_tab, w.bin_offset, w.bin_cursor, w.keys, w.hdr, s); });
+        if (rc == GPSGS_OK)
+            rc = stage("sort", GSR_STAGE_SORT, [&] { gsr_launch_sort(L.NB, w.bin_offset, w.wg_order, w.keys, w.point_list, w.hdr, no_large_sort, s); });
     }
-    if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-    if (trace_on() || (flags & GSR_FLAG_DEBUG)) {  // self-check between the sort and the compositing (synchronises; never in normal operation)
-        // everything on the caller's stream `s` and checked: PyTorch's side streams do not synchronise with the NULL stream, so a NULL-stream memset of
-        // the counters could land AFTER k_validate_lists' atomics and hide a real inconsistency.  The five counters live in a small
-        // device buffer allocated once per process (a debug forward is never captured, but it no longer allocates per call either).
-        GsrHeader h;
-        unsigned long long h_out[5] = {0, 0, 0, 0, 0};
-        static unsigned long long *d_out_by_dev[64] = {nullptr};
-        int devid = 0;
-        if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return GPSGS_E_LAUNCH;
-        unsigned long long *d_out;
-        {
-            static std::mutex mu;
-            std::lock_guard<std::mutex> g(mu);
-            if (!d_out_by_dev[devid] && hipMalloc(&d_out_by_dev[devid], sizeof(h_out)) != hipSuccess) return GPSGS_E_LAUNCH;
-            d_out = d_out_by_dev[devid];
-        }
-        if (hipMemcpyAsync(&h, hdr, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipMemsetAsync(d_out, 0, sizeof(h_out), s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return GPSGS_E_LAUNCH;
-        if (!h.overflow) hipLaunchKernelGGL(k_validate_lists, dim3((L.NB + 255) / 256), dim3(256), 0, s, P, L.NB, bins, bin_cursor, point_list, splats, d_out);
-        if (hipMemcpyAsync(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return GPSGS_E_LAUNCH;
-        const bool bad = h_out[0] || h_out[1] || h_out[4];
-        if (trace_on() || bad) {
-            fprintf(stderr, "[gpsgs] header: R=%llu overflow=%u longest=%u busy=%u slots=%u points=%u | lists: ids out of range %llu, out of order %llu, non-finite records %llu, "
-                            "bins whose scatter cursor missed its end %llu (longest list with a bad id %llu)\n",
-                    (unsigned long long)h.num_rendered, h.overflow, h.max_tile_count, h.num_busy_wgs, h.num_slots, h.num_points, h_out[0], h_out[1], h_out[2], h_out[4], h_out[3]);
-            fflush(stderr);
-        }
-        if (bad) return GPSGS_E_INTERNAL;
-    }
-    {
-        trace("composite_fwd", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_COMPOSITE_FWD, s);
-        if (flags & GSR_FLAG_COMPOSITE_TILES)
-            gsr_launch_composite_fwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, training,
-                                           (flags & GSR_FLAG_WAVE_PRIORITY) != 0, fused_sort ? keys : nullptr, s);
-        else if (F > 0)
-            gsr_launch_composite_fwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd,
-                                          out_depth, out_alpha, feat->features, F, row_range, feat->out_features, s);
-        else if (stats) {
-            float4 *inst_contrib = reinterpret_cast<float4 *>(at(workspace, L.total_extra));
-            gsr_launch_contrib_clear(inst_contrib, instance_capacity, hdr, s);
-            gsr_launch_composite_fwd_contrib(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd,
-                                             out_depth, out_alpha, q.goff, reinterpret_cast<const uint32_t *>(at(workspace, L.gprefix)), inst_contrib, s);
-        } else
-            gsr_launch_composite_fwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, out_color, final_T, n_contrib, hdr, inst_valid_fwd, out_depth,
-                                     out_alpha, s);
-    }
-    if (stats) {
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        trace("contrib_gather", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_COMPOSITE_FWD, s);
-        gsr_launch_contrib_gather(P, row_range, radii, q.goff, reinterpret_cast<const uint32_t *>(at(workspace, L.gprefix)),
-                                  reinterpret_cast<const float4 *>(at(workspace, L.total_extra)), hdr, c_sum, c_max, c_cnt, s);
-    }
-    return check(s, flags);
+    if (rc == GPSGS_OK && self_check) rc = validate_lists(P, L.NB, w, s);
+    if (rc != GPSGS_OK) return rc;
+    GsrCompositeFwd k = {width, height, L.bx, L.by, w.splats, w.bins, w.wg_order, w.point_list, c.bg, c.out_color, w.final_T, w.n_contrib, w.hdr, w.inst_valid, s, out_depth, out_alpha};
+    if (F > 0) { k.features = c.feat->features; k.F = F; k.row_range = row_range; k.out_feat = c.feat->out_features; }
+    if (stats) { k.goff = w.goff; k.gpart = w.gprefix; k.inst_contrib = static_cast<float4 *>(w.tail); }
+    rc = stage("composite_fwd", GSR_STAGE_COMPOSITE_FWD, [&] {
+        if (flags & GSR_FLAG_COMPOSITE_TILES) return gsr_launch_composite_fwd_tiles(k, training, (flags & GSR_FLAG_WAVE_PRIORITY) != 0, fused_sort ? w.keys : nullptr);
+        if (k.inst_contrib) gsr_launch_contrib_clear(k.inst_contrib, instance_capacity, w.hdr, s);
+        gsr_launch_composite_fwd(k);
+    });
+    if (rc == GPSGS_OK && k.inst_contrib)
+        rc = stage("contrib_gather", GSR_STAGE_COMPOSITE_FWD, [&] {
+            gsr_launch_contrib_gather(P, row_range, c.radii, k.goff, k.gpart, k.inst_contrib, w.hdr, con.weight_sum, con.weight_max, con.pixel_count, s);
+        });
+    return rc;
 }
 }  // namespace
 
@@ -410,8 +411,7 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
                               const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                               void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                               void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext) {
-    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, nullptr);
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, nullptr});
 }
 
 extern "C" int gsr_forward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -419,8 +419,7 @@ extern "C" int gsr_forward_features(int P, int width, int height, const float *m
                                     const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                     void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                     void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
-    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, feat);
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, feat, nullptr});
 }
 
 extern "C" int gsr_forward_contrib(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -428,9 +427,7 @@ extern "C" int gsr_forward_contrib(int P, int width, int height, const float *me
                                    const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                    void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                    void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrContrib *contrib) {
-    if (contrib && contrib->reserved) return GPSGS_E_INVALID;
-    return forward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                        out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, ext, nullptr, contrib);
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, contrib});
 }
 
 extern "C" int gsr_forward_notify(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -438,143 +435,121 @@ extern "C" int gsr_forward_notify(int P, int width, int height, const float *mea
                                   const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                   void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                   void *host_header_out, uint32_t notify_seq) {
-    return gsr_forward_ex(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix,
-                          bg, out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, host_header_out, notify_seq, nullptr);
+    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, host_header_out, notify_seq, nullptr, nullptr});
 }
 
 extern "C" int gsr_forward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
                            const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
                            const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                            void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream) {
-    return gsr_forward_ex(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix,
-                          bg, out_color, radii, workspace, workspace_bytes, instance_capacity, flags, stream, nullptr, 0u, nullptr);
+    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, nullptr, 0u, nullptr, nullptr});
+}
+
+extern "C" size_t gsr_camera_grad_scratch_bytes(int P) {
+    if (P <= 0) return 0;
+    return sizeof(float) * (size_t)GSR_CAMGRAD_TERMS * (size_t)((P + 255) / 256);  // one partial per term and preprocess_bwd workgroup
 }
 
 namespace {
 // gsr_backward_ex, and with cam (gsr_backward_camera) the camera gradients too: the same validation, the same launches up to the preprocess
 // backward, which then runs its CAMGRAD instantiation (bit-identical per-Gaussian results) and the fixed-order sum of the workgroup partials
-int backward_impl(int P, int width, int height, const float *means3D, const float *colors, const float *opacities, const float *scales,
-                  const float *rotations, float scale_modifier, float tanfovx, float tanfovy, const float *viewmatrix, const float *projmatrix,
-                  const float *bg, const int *radii, const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                  float *dL_dopacity, float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes, int64_t instance_capacity,
-                  unsigned flags, void *stream, const GsrViewExt *ext, const GsrCamGrad *cam, const GsrFeatures *feat = nullptr, const GsrAbsGrad *abs = nullptr) {
-    (void)colors;  // already folded into the splat records of the workspace (so are the opacities -- read again only with antialiasing)
-    const bool antialias = (flags & GSR_FLAG_ANTIALIAS) != 0;
+int backward_impl(const BackwardCall &c) {
+    // (c.colors: already folded into the splat records of the workspace; so are the opacities -- read again only with antialiasing)
+    const int P = c.P, width = c.width, height = c.height;
+    const int64_t instance_capacity = c.instance_capacity;
+    const GsrViewExt *ext = c.ext;
+    const bool antialias = (c.flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
     const float *dL_ddepth = ext ? ext->dL_ddepth : nullptr, *dL_dalpha = ext ? ext->dL_dalpha : nullptr;
     const bool extras = dL_ddepth || dL_dalpha;
-    if ((reinterpret_cast<uintptr_t>(dL_ddepth) | reinterpret_cast<uintptr_t>(dL_dalpha)) & 3u) return GPSGS_E_INVALID;
-    if (extras) flags &= ~GSR_FLAG_COMPOSITE_TILES;
+    if (misaligned(dL_ddepth, dL_dalpha)) return GPSGS_E_INVALID;
     // feature maps (either gradient pointer may be NULL): the VALU family's feature kernels, cap x F more floats in the workspace's feature tail
-    const int F = feature_channels(feat, true, P);
+    const int F = feature_channels(c.feat, true, P);
     if (F < 0) return GPSGS_E_INVALID;
-    if (F > 0) flags &= ~GSR_FLAG_COMPOSITE_TILES;
-    const float *dL_dfeat = F > 0 ? feat->dL_dfeaturemap : nullptr;
-    float *dL_dfeatures = F > 0 ? feat->dL_dfeatures : nullptr;
+    const float *dL_dfeat = F > 0 ? c.feat->dL_dfeaturemap : nullptr;
+    float *dL_dfeatures = F > 0 ? c.feat->dL_dfeatures : nullptr;
     const bool feat_sums = dL_dfeat && dL_dfeatures;  // the per-slot feature sums (part b) are formed
     // absolute screen-space gradient: the VALU family's ABSGRAD kernels, 8 bytes per instance slot in the workspace's absgrad tail
-    if (abs && abs->reserved) return GPSGS_E_INVALID;
-    float2 *absgrad = abs ? reinterpret_cast<float2 *>(abs->absgrad) : nullptr;
-    if (reinterpret_cast<uintptr_t>(absgrad) & 3u) return GPSGS_E_INVALID;
-    if (absgrad && F > 0) return GPSGS_E_INVALID;  // (the two tails share an offset; no entry point passes both)
-    if (absgrad) flags &= ~GSR_FLAG_COMPOSITE_TILES;
+    if (c.abs && c.abs->reserved) return GPSGS_E_INVALID;
+    float2 *absgrad = c.abs ? reinterpret_cast<float2 *>(c.abs->absgrad) : nullptr;
+    if (misaligned(absgrad) || !gsr_one_tail(F, false, absgrad != nullptr)) return GPSGS_E_INVALID;  // (no entry point passes both)
+    const unsigned flags = (extras || F > 0 || absgrad) ? c.flags & ~GSR_FLAG_COMPOSITE_TILES : c.flags;  // options only the VALU kernels have
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
+    hipStream_t s = (hipStream_t)c.stream;
     if (P == 0) {
-        if (cam) {  // nothing rendered: the camera gradients are zeros
-            const float *outs[3] = {cam->d_view, cam->d_proj, cam->d_campos};
+        if (c.cam) {  // nothing rendered: the camera gradients are zeros
+            float *outs[3] = {c.cam->d_view, c.cam->d_proj, c.cam->d_campos};
             const size_t n[3] = {16, 16, 3};
             for (int k = 0; k < 3; k++)
-                if (outs[k] && hipMemsetAsync(const_cast<float *>(outs[k]), 0, n[k] * sizeof(float), (hipStream_t)stream) != hipSuccess) return GPSGS_E_LAUNCH;
-            return check((hipStream_t)stream, flags);
+                if (outs[k] && hipMemsetAsync(outs[k], 0, n[k] * sizeof(float), s) != hipSuccess) return GPSGS_E_LAUNCH;
+            return check(s, flags);
         }
         return GPSGS_OK;
     }
-    if (cam && cam->scratch && (reinterpret_cast<uintptr_t>(cam->scratch) & 3u)) return GPSGS_E_INVALID;
+    if (c.cam && c.cam->scratch && misaligned(c.cam->scratch)) return GPSGS_E_INVALID;
     const float *shs = ext ? ext->shs : nullptr, *cov3D_precomp = ext ? ext->cov3D_precomp : nullptr;
-    if (!means3D || !viewmatrix || !projmatrix || !bg || !radii || !dL_dpix || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity || !workspace) return GPSGS_E_INVALID;
-    if (!shs && !dL_dcolors) return GPSGS_E_INVALID;
-    if (antialias && !opacities) return GPSGS_E_INVALID;  // dL/dk = g * opacity
-    if (cov3D_precomp ? (!ext->dL_dcov3D || scales || rotations) : (!scales || !rotations || !dL_dscales || !dL_drotations)) return GPSGS_E_INVALID;
+    if (!c.means3D || !c.viewmatrix || !c.projmatrix || !c.bg || !c.radii || !c.dL_dpix || !c.dL_dmeans3D || !c.dL_dmeans2D || !c.dL_dopacity || !c.workspace)
+        return GPSGS_E_INVALID;
+    if (!shs && !c.dL_dcolors) return GPSGS_E_INVALID;
+    if (antialias && !c.opacities) return GPSGS_E_INVALID;  // dL/dk = g * opacity
+    if (cov3D_precomp ? (!ext->dL_dcov3D || c.scales || c.rotations) : (!c.scales || !c.rotations || !c.dL_dscales || !c.dL_drotations)) return GPSGS_E_INVALID;
     if (shs && (!ext->campos || !ext->dL_dsh || ext->sh_degree > 3u || ext->sh_coeffs > 16u || (ext->sh_degree + 1u) * (ext->sh_degree + 1u) > ext->sh_coeffs))
         return GPSGS_E_INVALID;
     const uint32_t bin_cap = ext ? ext->bin_capacity : 0u;  // must be what the forward was given
     if (bin_cap && !gsr_direct_lists_ok(width, height, bin_cap)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_cap);
-    if (workspace_bytes < (feat_sums ? L.total_extra + gsr_feature_tail_bytes(instance_capacity, F) : extras ? L.total_extra : L.total)) return GPSGS_E_WORKSPACE;
-    if (absgrad && workspace_bytes < L.total_extra + gsr_absgrad_tail_bytes(instance_capacity)) return GPSGS_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const GsrHeader *hdr = reinterpret_cast<const GsrHeader *>(at(workspace, L.header));
-    const GsrBins bins = {reinterpret_cast<const uint32_t *>(at(workspace, L.bin_offset)), reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count)),
-                          reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count_fb)), bin_cap};
-    const uint32_t *wg_order = reinterpret_cast<const uint32_t *>(at(workspace, L.wg_order));
-    const GsrSplat *splats = reinterpret_cast<const GsrSplat *>(at(workspace, L.splats));
-    const uint32_t *point_list = reinterpret_cast<const uint32_t *>(at(workspace, L.point_list));
-    const float *final_T = reinterpret_cast<const float *>(at(workspace, L.final_T));
-    const uint32_t *n_contrib = reinterpret_cast<const uint32_t *>(at(workspace, L.n_contrib));
-    uint32_t *goff = reinterpret_cast<uint32_t *>(at(workspace, L.goff));
-    uint32_t *gscan_part = reinterpret_cast<uint32_t *>(at(workspace, L.gprefix));  // (the slot prefix per binning workgroup)
-    uint8_t *inst_valid = reinterpret_cast<uint8_t *>(at(workspace, L.inst_valid));
-    float *inst_dop = reinterpret_cast<float *>(at(workspace, L.inst_dop));
-    GsrGradAcc *inst_grad = reinterpret_cast<GsrGradAcc *>(at(workspace, L.inst_grad));
-    float *inst_ddepth = extras ? reinterpret_cast<float *>(at(workspace, L.inst_ddepth)) : nullptr;
-    float *inst_dfeat = feat_sums ? reinterpret_cast<float *>(at(workspace, L.total_extra)) : nullptr;
-    float2 *inst_absgrad = absgrad ? reinterpret_cast<float2 *>(at(workspace, L.total_extra)) : nullptr;  // (the contribution tail's place: dead by now)
+    if (c.workspace_bytes < gsr_workspace_need(L, instance_capacity, {false, extras, feat_sums ? F : 0, false, absgrad != nullptr})) return GPSGS_E_WORKSPACE;
+    // goff / gprefix / cleared inst_valid were produced by the matching gsr_forward (training workspace)
+    const GsrWorkspace w = gsr_workspace_map(c.workspace, L, true);
     const uint32_t *row_range = ext ? ext->row_range : nullptr;
+    GsrCompositeBwd k = {width, height, L.bx, L.by, w.splats, w.bins, w.wg_order, w.point_list, c.bg, c.dL_dpix, w.final_T, w.n_contrib, w.goff, w.gprefix, w.inst_valid, w.inst_dop,
+                         w.inst_grad, w.hdr, s, dL_ddepth, dL_dalpha, extras ? w.inst_ddepth : nullptr};
+    if (F > 0) { k.features = c.feat->features; k.F = F; k.row_range = row_range; k.dL_dfeat = dL_dfeat; k.inst_dfeat = feat_sums ? static_cast<float *>(w.tail) : nullptr; }
+    if (absgrad) k.inst_absgrad = static_cast<float2 *>(w.tail);  // (the contribution tail's place: dead by now)
 
-    // goff / gscan_part / cleared inst_valid were produced by the matching gsr_forward (training workspace)
-    int rc;
-    {
-        trace("composite_bwd", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_COMPOSITE_BWD, s);
-        // must be the same family as the forward that filled the workspace: the two designs round the exponent differently, and the
-        // backward has to repeat the forward's per-pixel decisions
-        if (flags & GSR_FLAG_COMPOSITE_TILES)
-            gsr_launch_composite_bwd_tiles(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
-                                           (flags & GSR_FLAG_NO_COLOR_GRAD) == 0, (flags & GSR_FLAG_WAVE_PRIORITY) != 0, s);
-        else if (dL_dfeat)  // (a NULL feature-map gradient runs the plain kernel: the per-Gaussian gradients keep their bits)
-            gsr_launch_composite_bwd_feat(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop,
-                                          inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, feat->features, F, row_range, dL_dfeat, inst_dfeat, s);
-        else if (absgrad)
-            gsr_launch_composite_bwd_absgrad(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop,
-                                             inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, inst_absgrad, s);
-        else
-            gsr_launch_composite_bwd(width, height, L.bx, L.by, splats, bins, wg_order, point_list, bg, dL_dpix, final_T, n_contrib, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr,
-                                     dL_ddepth, dL_dalpha, inst_ddepth, s);
-    }
-    if ((rc = check(s, flags)) != GPSGS_OK) return rc;
+    const Stages stage = {c, flags, s};
+    // must be the same family as the forward that filled the workspace: the two designs round the exponent differently, and the
+    // backward has to repeat the forward's per-pixel decisions
+    int rc = stage("composite_bwd", GSR_STAGE_COMPOSITE_BWD, [&] {
+        if (flags & GSR_FLAG_COMPOSITE_TILES) gsr_launch_composite_bwd_tiles(k, (flags & GSR_FLAG_NO_COLOR_GRAD) == 0, (flags & GSR_FLAG_WAVE_PRIORITY) != 0);
+        else gsr_launch_composite_bwd(k);
+    });
+    if (rc != GPSGS_OK) return rc;
     GsrBwdParams b;
     b.P = P; b.W = width; b.H = height;
-    b.means3D = means3D; b.scales = scales; b.rotations = rotations;
-    b.scale_modifier = scale_modifier; b.tanfovx = tanfovx; b.tanfovy = tanfovy;
-    b.view = viewmatrix; b.proj = projmatrix; b.radii = radii;
-    b.dL_dmeans3D = dL_dmeans3D; b.dL_dmeans2D = dL_dmeans2D; b.dL_dcolors = dL_dcolors; b.dL_dopacity = dL_dopacity;
-    b.dL_dscales = dL_dscales; b.dL_drotations = dL_drotations;
-    b.row_range = ext ? ext->row_range : nullptr;
+    b.means3D = c.means3D; b.scales = c.scales; b.rotations = c.rotations;
+    b.scale_modifier = c.scale_modifier; b.tanfovx = c.tanfovx; b.tanfovy = c.tanfovy;
+    b.view = c.viewmatrix; b.proj = c.projmatrix; b.radii = c.radii;
+    b.dL_dmeans3D = c.dL_dmeans3D; b.dL_dmeans2D = c.dL_dmeans2D; b.dL_dcolors = c.dL_dcolors; b.dL_dopacity = c.dL_dopacity;
+    b.dL_dscales = c.dL_dscales; b.dL_drotations = c.dL_drotations;
+    b.row_range = row_range;
     b.shs = shs; b.campos = shs ? ext->campos : nullptr; b.cov3D_precomp = cov3D_precomp;
     b.sh_degree = shs ? ext->sh_degree : 0u; b.sh_coeffs = shs ? ext->sh_coeffs : 0u;
     b.dL_dsh = shs ? ext->dL_dsh : nullptr; b.dL_dcov3D = cov3D_precomp ? ext->dL_dcov3D : nullptr;
-    b.inst_ddepth = inst_ddepth;
+    b.inst_ddepth = k.inst_ddepth;
     b.antialias = antialias ? 1 : 0;
-    b.opacities = opacities;
+    b.opacities = c.opacities;
     b.dop_in_record = ((flags & GSR_FLAG_COMPOSITE_TILES) && (flags & GSR_FLAG_NO_COLOR_GRAD)) ? 1 : 0;  // what k_composite_bwd_tiles<false> just wrote
-    {
-        trace("preprocess_bwd", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
-        gsr_launch_preprocess_bwd(b, splats, goff, gscan_part, inst_valid, inst_dop, inst_grad, hdr, s, cam);
+    rc = stage("preprocess_bwd", GSR_STAGE_PREPROCESS_BWD, [&] { gsr_launch_preprocess_bwd(b, w.splats, w.goff, w.gprefix, w.inst_valid, w.inst_dop, w.inst_grad, w.hdr, s, c.cam); });
+    if (rc == GPSGS_OK && dL_dfeatures)
+        rc = stage("feature_grad_gather", GSR_STAGE_PREPROCESS_BWD,
+                   [&] { gsr_launch_feature_grad_gather(P, F, row_range, c.radii, w.goff, w.gprefix, w.inst_valid, k.inst_dfeat, w.hdr, dL_dfeatures, s); });
+    if (rc == GPSGS_OK && absgrad)  // (the flags the compositing backward set are cleared only by the next forward's compositing launch)
+        rc = stage("absgrad_gather", GSR_STAGE_PREPROCESS_BWD,
+                   [&] { gsr_launch_absgrad_gather(P, row_range, c.radii, w.goff, w.gprefix, w.inst_valid, k.inst_absgrad, w.hdr, absgrad, s); });
+    return rc;
+}
+
+// gsr_backward_camera / _absgrad / _features: the camera arguments first -- misaligned outputs or a scratch slab too small for P are refused; c.cam is set when
+// any of the three gradients is asked for and stays NULL otherwise (the call is then gsr_backward_ex)
+int backward_with_camera(BackwardCall c, float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes) {
+    if (misaligned(dL_dviewmatrix, dL_dprojmatrix, dL_dcampos)) return GPSGS_E_INVALID;
+    const GsrCamGrad cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    if (dL_dviewmatrix || dL_dprojmatrix || dL_dcampos) {
+        if (c.P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(c.P))) return GPSGS_E_WORKSPACE;
+        c.cam = &cam;
     }
-    if (dL_dfeatures) {
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        trace("feature_grad_gather", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
-        gsr_launch_feature_grad_gather(P, F, row_range, radii, goff, gscan_part, inst_valid, inst_dfeat, hdr, dL_dfeatures, s);
-    }
-    if (absgrad) {  // (the flags the compositing backward set are cleared only by the next forward's compositing launch)
-        if ((rc = check(s, flags)) != GPSGS_OK) return rc;
-        trace("absgrad_gather", P, width, height, (long long)instance_capacity, flags);
-        StageTimer t(flags, GSR_STAGE_PREPROCESS_BWD, s);
-        gsr_launch_absgrad_gather(P, row_range, radii, goff, gscan_part, inst_valid, inst_absgrad, hdr, absgrad, s);
-    }
-    return check(s, flags);
+    return backward_impl(c);
 }
 }  // namespace
 
@@ -584,30 +559,8 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
                                const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
                                float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
-    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, nullptr);
+    return backward_impl({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr});
 }
-
-extern "C" size_t gsr_camera_grad_scratch_bytes(int P) {
-    if (P <= 0) return 0;
-    return sizeof(float) * (size_t)GSR_CAMGRAD_TERMS * (size_t)((P + 255) / 256);  // one partial per term and preprocess_bwd workgroup
-}
-
-namespace {
-// The camera arguments of gsr_backward_camera / _absgrad / _features: misaligned outputs or a scratch slab too small for P are refused; `want`
-// points at `cam` when any of the three gradients is asked for and stays NULL otherwise (the call is then gsr_backward_ex).
-int camera_args(int P, float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes, GsrCamGrad &cam,
-                const GsrCamGrad *&want) {
-    if ((reinterpret_cast<uintptr_t>(dL_dviewmatrix) | reinterpret_cast<uintptr_t>(dL_dprojmatrix) | reinterpret_cast<uintptr_t>(dL_dcampos)) & 3u)
-        return GPSGS_E_INVALID;
-    if (!(dL_dviewmatrix || dL_dprojmatrix || dL_dcampos)) return GPSGS_OK;
-    if (P > 0 && (!scratch || scratch_bytes < gsr_camera_grad_scratch_bytes(P))) return GPSGS_E_WORKSPACE;
-    cam = {static_cast<float *>(scratch), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
-    want = &cam;
-    return GPSGS_OK;
-}
-}  // namespace
 
 extern "C" int gsr_backward_camera(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
                                    const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
@@ -616,13 +569,8 @@ extern "C" int gsr_backward_camera(int P, int width, int height, const float *me
                                    float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                    int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                    float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes) {
-    GsrCamGrad cam;
-    const GsrCamGrad *want = nullptr;
-    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
-    if (rc != GPSGS_OK) return rc;
-    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want);
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr},
+                                dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
 extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -633,13 +581,8 @@ extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *m
                                     int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                     float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                     const GsrAbsGrad *abs) {
-    GsrCamGrad cam;
-    const GsrCamGrad *want = nullptr;
-    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
-    if (rc != GPSGS_OK) return rc;
-    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want, nullptr, abs);
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, abs},
+                                dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
 extern "C" int gsr_backward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -650,13 +593,8 @@ extern "C" int gsr_backward_features(int P, int width, int height, const float *
                                      int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                      float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                      const GsrFeatures *feat) {
-    GsrCamGrad cam;
-    const GsrCamGrad *want = nullptr;
-    const int rc = camera_args(P, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes, cam, want);
-    if (rc != GPSGS_OK) return rc;
-    return backward_impl(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                         radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                         instance_capacity, flags, stream, ext, want, feat);
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, feat, nullptr},
+                                dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
 extern "C" int gsr_backward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -665,10 +603,9 @@ extern "C" int gsr_backward(int P, int width, int height, const float *means3D, 
                             const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
                             float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                             int64_t instance_capacity, unsigned flags, void *stream) {
-    return gsr_backward_ex(P, width, height, means3D, colors, opacities, scales, rotations, scale_modifier, tanfovx, tanfovy, viewmatrix, projmatrix, bg,
-                           radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, workspace, workspace_bytes,
-                           instance_capacity, flags, stream, nullptr);
+    return backward_impl({GSR_VIEW_CALL(nullptr), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr});
 }
+#undef GSR_VIEW_CALL
 
 extern "C" int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present, void *stream) {
     (void)projmatrix;  // upstream's in_frustum() projects the point too, but tests only the view-space depth
@@ -722,9 +659,10 @@ extern "C" int gsr_debug_count_records(const void *workspace, size_t workspace_b
     if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
     if (workspace_bytes < L.total) return GPSGS_E_WORKSPACE;  // a forward-only workspace has no record flags (they lie beyond its end)
+    const GsrWorkspace w = gsr_workspace_map(const_cast<void *>(workspace), L, true);
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(out2_device, 0, 16, s) != hipSuccess) return GPSGS_E_LAUNCH;
-    hipLaunchKernelGGL(k_count_flags, dim3(1024), dim3(256), 0, s, at(workspace, L.inst_valid), reinterpret_cast<const GsrHeader *>(at(workspace, L.header)), out2_device);
+    hipLaunchKernelGGL(k_count_flags, dim3(1024), dim3(256), 0, s, w.inst_valid, w.hdr, out2_device);
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
 
@@ -761,17 +699,14 @@ extern "C" int gsr_export_state(const void *workspace, int P, int width, int hei
     if (!workspace || P < 0 || width <= 0 || height <= 0) return GPSGS_E_INVALID;
     if (bin_capacity && !gsr_direct_lists_ok(width, height, bin_capacity)) return GPSGS_E_INVALID;
     const GsrLayout L = gsr_layout(P, width, height, instance_capacity, bin_capacity);
+    const GsrWorkspace w = gsr_workspace_map(const_cast<void *>(workspace), L, false);
     hipStream_t s = (hipStream_t)stream;
     const int n = P > L.NB ? P : L.NB;
-    const GsrBins bins = {reinterpret_cast<const uint32_t *>(at(workspace, L.bin_offset)), reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count)),
-                          reinterpret_cast<const uint32_t *>(at(workspace, L.bin_count_fb)), bin_capacity};
-    if (n > 0)
-        hipLaunchKernelGGL(k_export, dim3((n + 255) / 256), dim3(256), 0, s, P, L.NB, reinterpret_cast<const GsrSplat *>(at(workspace, L.splats)), bins, depth, xy,
-                           conic_opacity, rect, tile_ranges);
+    if (n > 0) hipLaunchKernelGGL(k_export, dim3((n + 255) / 256), dim3(256), 0, s, P, L.NB, w.splats, w.bins, depth, xy, conic_opacity, rect, tile_ranges);
     const size_t npix = (size_t)width * height;
     if (point_list && L.key_cap > 0)  // point_list [key capacity]: the instance capacity, or bins x bin_capacity (direct lists: every bin's segment, gaps included)
-        (void)hipMemcpyAsync(point_list, at(workspace, L.point_list), (size_t)L.key_cap * 4, hipMemcpyDeviceToDevice, s);
-    if (final_T) (void)hipMemcpyAsync(final_T, at(workspace, L.final_T), npix * 4, hipMemcpyDeviceToDevice, s);
-    if (n_contrib) (void)hipMemcpyAsync(n_contrib, at(workspace, L.n_contrib), npix * 4, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(point_list, w.point_list, (size_t)L.key_cap * 4, hipMemcpyDeviceToDevice, s);
+    if (final_T) (void)hipMemcpyAsync(final_T, w.final_T, npix * 4, hipMemcpyDeviceToDevice, s);
+    if (n_contrib) (void)hipMemcpyAsync(n_contrib, w.n_contrib, npix * 4, hipMemcpyDeviceToDevice, s);
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }

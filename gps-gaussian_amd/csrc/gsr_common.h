@@ -519,57 +519,119 @@ void gsr_launch_sort(int NB, const uint32_t *bin_offset, const uint32_t *wg_orde
 void gsr_launch_sort_direct(int NB, GsrBins bins, const uint32_t *wg_order, uint64_t *keys, uint32_t *point_list, const GsrHeader *hdr, hipStream_t s);
 #define GSR_DIRECT_MAX_BINS 65536  // direct lists: the scan waves of the scatter launch poll each other's partials (all resident: <= 1,024 of them)
 #define GSR_DIRECT_MAX_CAP 1024    // ... and a bin's list is sorted by ONE wave (k_sort_wave's classes)
-void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                              const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib, const GsrHeader *hdr,
-                              uint8_t *inst_valid /* training workspace: the record flags are cleared here; NULL otherwise */,
-                              float *out_depth, float *out_alpha /* [H, W] each, NULL = not wanted; either set: the EXTRA instantiation */, hipStream_t s);
-void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                              const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T, const uint32_t *n_contrib,
-                              const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop, GsrGradAcc *inst_grad, const GsrHeader *hdr,
-                              const float *dL_ddepth, const float *dL_dalpha /* [H, W], NULL = zero */,
-                              float *inst_ddepth /* non-NULL: the EXTRA instantiation, which writes dL/dz per record slot */, hipStream_t s);
-// F-channel feature maps (GsrFeatures; the VALU family only).  Forward: the image, final_T, n_contrib (and the depth / alpha maps) exactly as
-// gsr_launch_composite_fwd writes them, plus out_feat [F, H, W]; features [rows, F] follow row_range.  Backward: the geometry kernel (the features'
-// share of cd, dL_dfeat [F, H, W] non-NULL) in place of gsr_launch_composite_bwd, then, with inst_dfeat (cap x F floats) non-NULL, the per-slot
-// feature sums; gsr_launch_feature_grad_gather turns those into dL_dfeatures [rows, F] (inst_dfeat NULL: zeros).
-void gsr_launch_composite_fwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                   const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                                   const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const float *features, int F,
-                                   const uint32_t *row_range, float *out_feat, hipStream_t s);
-void gsr_launch_composite_bwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                   const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                                   const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                                   GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
-                                   const float *features, int F, const uint32_t *row_range, const float *dL_dfeat, float *inst_dfeat, hipStream_t s);
+// One compositing launch of either family: what every instantiation takes, then the optional blocks (all NULL / 0 = off)
+struct GsrCompositeFwd {
+    int W, H, bx, by;
+    const GsrSplat *splats;
+    GsrBins bins;
+    const uint32_t *wg_order;
+    uint32_t *point_list;  // (written only by the tile family's fused sort)
+    const float *bg;
+    float *out_color, *final_T;
+    uint32_t *n_contrib;
+    const GsrHeader *hdr;
+    uint8_t *inst_valid;  // training workspace: the record flags are cleared here; NULL otherwise
+    hipStream_t s;
+    float *out_depth, *out_alpha;  // [H, W] each, NULL = not wanted; either set: the EXTRA instantiations
+    // F-channel feature maps (GsrFeatures), F > 0: out_feat [F, H, W] beside the image, final_T, n_contrib and maps; features [rows, F] follow row_range
+    const float *features;
+    int F;
+    const uint32_t *row_range;
+    float *out_feat;
+    // contribution statistics (GsrContrib), inst_contrib non-NULL: the same outputs plus {sum w, max w, pixels} per blended instance at its slot
+    const uint32_t *goff, *gpart;
+    float4 *inst_contrib;
+};
+struct GsrCompositeBwd {
+    int W, H, bx, by;
+    const GsrSplat *splats;
+    GsrBins bins;
+    const uint32_t *wg_order, *point_list;
+    const float *bg, *dL_dpix, *final_T;
+    const uint32_t *n_contrib, *goff, *gpart;
+    uint8_t *inst_valid;
+    float *inst_dop;
+    GsrGradAcc *inst_grad;
+    const GsrHeader *hdr;
+    hipStream_t s;
+    const float *dL_ddepth, *dL_dalpha;  // [H, W], NULL = zero
+    float *inst_ddepth;                  // non-NULL: the EXTRA instantiations, which write dL/dz per record slot
+    // feature maps, dL_dfeat [F, H, W] non-NULL: the geometry kernel with the features' share of cd (NULL: the plain kernel, the per-Gaussian gradients keep
+    // their bits), then with inst_dfeat (cap x F floats) non-NULL the per-slot feature sums (gsr_launch_feature_grad_gather: NULL = zeros)
+    const float *features;
+    int F;
+    const uint32_t *row_range;
+    const float *dL_dfeat;
+    float *inst_dfeat;
+    float2 *inst_absgrad;  // absgrad (GsrAbsGrad), non-NULL: the same records, inst_dop, inst_ddepth and flags bit for bit, plus {sum_p |t_x|, sum_p |t_y|} per slot
+};
+// the VALU family (gsr_composite.hip): the instantiation follows from the optional blocks that are set
+void gsr_launch_composite_fwd(const GsrCompositeFwd &c);
+void gsr_launch_composite_bwd(const GsrCompositeBwd &c);
+// the gathers sum each Gaussian's slots in slot order into its [rows] outputs (zeros for culled Gaussians and an overflowed view); gsr_launch_contrib_clear
+// zeroes the contribution tail's slots [0, num_slots) of a view that did not overflow, in front of the CONTRIB forward
 void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart,
                                     const uint8_t *inst_valid, const float *inst_dfeat, const GsrHeader *hdr, float *dL_dfeatures, hipStream_t s);
-// the feature tail of a training workspace: F floats per instance slot, behind the depth / alpha tail (total_extra)
-static inline size_t gsr_feature_tail_bytes(int64_t cap, int F) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * (size_t)F * 4); }
-// Per-Gaussian contribution statistics (GsrContrib; the VALU family only).  gsr_launch_contrib_clear zeroes the tail's slots [0, num_slots) of a
-// view that did not overflow; gsr_launch_composite_fwd_contrib is gsr_launch_composite_fwd (same image, final_T, n_contrib, maps, cleared flags) plus
-// {sum w, max w, pixels} per blended instance at its slot (goff / gpart of a training workspace); gsr_launch_contrib_gather sums each Gaussian's
-// slots in slot order into the three [rows] outputs (each may be NULL; zeros for culled Gaussians and an overflowed view).
 void gsr_launch_contrib_clear(float4 *inst_contrib, int64_t cap, const GsrHeader *hdr, hipStream_t s);
-void gsr_launch_composite_fwd_contrib(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                      const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                                      const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const uint32_t *goff,
-                                      const uint32_t *gpart, float4 *inst_contrib, hipStream_t s);
 void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const float4 *inst_contrib,
                                const GsrHeader *hdr, float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s);
-// the contribution tail of a workspace: 16 bytes per instance slot, behind the depth / alpha tail (total_extra)
-static inline size_t gsr_contrib_tail_bytes(int64_t cap) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * 16); }
-// Absolute screen-space gradient (GsrAbsGrad; the VALU family only).  gsr_launch_composite_bwd_absgrad is gsr_launch_composite_bwd (the same records,
-// inst_dop, inst_ddepth and flags, bit for bit) plus {sum_p |t_x|, sum_p |t_y|} per record at its slot of inst_absgrad; gsr_launch_absgrad_gather sums
-// each Gaussian's flagged slots in slot order into absgrad [rows, 2] (zeros for culled Gaussians and an overflowed view).
-void gsr_launch_composite_bwd_absgrad(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                      const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                                      const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                                      GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
-                                      float2 *inst_absgrad, hipStream_t s);
 void gsr_launch_absgrad_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const uint8_t *inst_valid,
                                const float2 *inst_absgrad, const GsrHeader *hdr, float2 *absgrad, hipStream_t s);
-// the absgrad tail of a training workspace: 8 bytes per instance slot, behind the depth / alpha tail (total_extra)
-static inline size_t gsr_absgrad_tail_bytes(int64_t cap) { return gsr_align_up((size_t)(cap > 0 ? cap : 1) * 8); }
+
+// The three opt-in tails -- F floats (feature sums), 16 bytes (contribution statistics), 8 bytes (absgrad) per instance slot -- all start at total_extra, so
+// a call asks for at most one of these options (the absgrad tail is the contribution tail's place: dead once the forward's gather has run)
+static inline bool gsr_one_tail(int F, bool contrib, bool absgrad) { return (F > 0) + contrib + absgrad <= 1; }
+// What a call asks of the workspace ...
+struct GsrWorkspaceNeed {
+    bool forward_only;  // no backward tail
+    bool extras;        // the depth / alpha slot array (inst_ddepth)
+    int F;              // > 0: the feature tail
+    bool contrib, absgrad;
+};
+// ... and the bytes that takes: what the gsr_workspace_bytes_* functions report and what gsr_forward_* / gsr_backward_* demand
+static inline size_t gsr_workspace_need(const GsrLayout &L, int64_t cap, const GsrWorkspaceNeed &n) {
+    const size_t slots = (size_t)(cap > 0 ? cap : 1);
+    if (n.contrib) return L.total_extra + gsr_align_up(slots * 16);  // (a forward-only one too: the statistics read the slot prefix of the backward tail)
+    if (n.absgrad) return L.total_extra + gsr_align_up(slots * 8);
+    if (n.forward_only) return L.total_fwd;
+    if (n.F > 0) return L.total_extra + gsr_align_up(slots * (size_t)n.F * 4);
+    return n.extras ? L.total_extra : L.total;
+}
+
+// The workspace as typed section pointers.  training = it holds the backward tail (at least L.total bytes): the sections behind total_fwd stay NULL otherwise.
+struct GsrWorkspace {
+    GsrHeader *hdr;
+    uint32_t *bin_count, *bin_count_fb, *bin_offset, *bin_cursor, *wg_order;
+    uint4 *scan_part;
+    GsrSplat *splats;
+    uint4 *binrec;
+    uint32_t *wg_tab;
+    uint64_t *keys;
+    uint32_t *point_list;
+    float *final_T;
+    uint32_t *n_contrib, *goff, *gscan_part, *gprefix;
+    uint8_t *inst_valid;
+    float *inst_dop;
+    GsrGradAcc *inst_grad;
+    float *inst_ddepth;
+    void *tail;  // total_extra: inst_dfeat, inst_contrib or inst_absgrad
+    GsrBins bins;
+};
+static inline GsrWorkspace gsr_workspace_map(void *workspace, const GsrLayout &L, bool training) {
+    uint8_t *const base = static_cast<uint8_t *>(workspace);
+    const auto at = [base](size_t off, bool have = true) { return have ? static_cast<void *>(base + off) : nullptr; };
+    GsrWorkspace w;
+    w.hdr = (GsrHeader *)at(L.header);
+    w.bin_count = (uint32_t *)at(L.bin_count); w.bin_count_fb = (uint32_t *)at(L.bin_count_fb); w.bin_offset = (uint32_t *)at(L.bin_offset);
+    w.bin_cursor = (uint32_t *)at(L.bin_cursor); w.wg_order = (uint32_t *)at(L.wg_order); w.scan_part = (uint4 *)at(L.scan_part);
+    w.splats = (GsrSplat *)at(L.splats); w.binrec = (uint4 *)at(L.binrec); w.wg_tab = (uint32_t *)at(L.wg_tab);
+    w.keys = (uint64_t *)at(L.keys); w.point_list = (uint32_t *)at(L.point_list); w.final_T = (float *)at(L.final_T); w.n_contrib = (uint32_t *)at(L.n_contrib);
+    w.goff = (uint32_t *)at(L.goff, training); w.gscan_part = (uint32_t *)at(L.gscan_part, training); w.gprefix = (uint32_t *)at(L.gprefix, training);
+    w.inst_valid = (uint8_t *)at(L.inst_valid, training); w.inst_dop = (float *)at(L.inst_dop, training); w.inst_grad = (GsrGradAcc *)at(L.inst_grad, training);
+    w.inst_ddepth = (float *)at(L.inst_ddepth, training); w.tail = at(L.total_extra, training);
+    w.bins = {w.bin_offset, w.bin_count, w.bin_count_fb, L.bin_cap};
+    return w;
+}
 // development knob: GPSGS_DEBUG_LDS_PAD=<bytes> of unused dynamic LDS per compositing workgroup (caps the waves resident per CU, to
 // measure how the kernels scale with occupancy); 0 / unset in normal use
 #include <stdlib.h>
@@ -579,19 +641,12 @@ static inline unsigned gsr_debug_lds_pad() {
     return (unsigned)v;
 }
 // exponents from bf16 matrix-core tiles (gsr_composite_tiles.hip): same arguments, same results within rounding
-void gsr_launch_composite_fwd_tiles(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                    uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib, const GsrHeader *hdr,
-                                    uint8_t *inst_valid /* training workspace: the record flags are cleared here; NULL otherwise */,
-                                    bool keep_state /* false: inference workspace, final_T / n_contrib are not produced */,
+void gsr_launch_composite_fwd_tiles(const GsrCompositeFwd &c, bool keep_state /* false: inference workspace, final_T / n_contrib are not produced */,
                                     bool wave_prio /* GSR_FLAG_WAVE_PRIORITY */,
-                                    const uint64_t *unsorted_keys /* direct lists: every wave sorts its own bin's list first (keys -> point_list); NULL: point_list is sorted */,
-                                    hipStream_t s);
+                                    const uint64_t *unsorted_keys /* direct lists: every wave sorts its own bin's list first (keys -> point_list); NULL: point_list is sorted */);
 int gsr_set_wg_trace(unsigned long long *rows_device);  // development aid: per-workgroup timeline of the tile compositing kernels (NULL = off)
-void gsr_launch_composite_bwd_tiles(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                    const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T, const uint32_t *n_contrib,
-                                    const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop, GsrGradAcc *inst_grad, const GsrHeader *hdr,
-                                    bool color_grad /* false: GSR_FLAG_NO_COLOR_GRAD, the colour sums are left out (zeros in the records) */,
-                                    bool wave_prio /* GSR_FLAG_WAVE_PRIORITY */, hipStream_t s);
+void gsr_launch_composite_bwd_tiles(const GsrCompositeBwd &c, bool color_grad /* false: GSR_FLAG_NO_COLOR_GRAD, the colour sums are left out (zeros in the records) */,
+                                    bool wave_prio /* GSR_FLAG_WAVE_PRIORITY */);
 void gsr_launch_selftest(float *out4, hipStream_t s);
 struct GsrBwdParams {
     int P, W, H;

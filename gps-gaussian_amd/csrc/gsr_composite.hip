@@ -956,85 +956,57 @@ __global__ __launch_bounds__(256) void k_absgrad_gather(int P, const uint32_t *_
 
 }  // namespace
 
-void gsr_launch_composite_fwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                              const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                              const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0) return;
-    if (out_depth || out_alpha)
-        hipLaunchKernelGGL(k_composite_fwd<true>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color,
-                           final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha);
-    else
-        hipLaunchKernelGGL(k_composite_fwd<false>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color,
-                           final_T, n_contrib, hdr, inst_valid, nullptr, nullptr);
-}
-
-void gsr_launch_composite_bwd(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                              const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                              const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                              GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
-                              hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0) return;
-    if (inst_ddepth)
-        hipLaunchKernelGGL(k_composite_bwd<true>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
-                           final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth);
-    else
-        hipLaunchKernelGGL(k_composite_bwd<false>, dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, dL_dpix,
-                           final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr, nullptr, nullptr);
-}
-
 // feature chunk width of the forward and the per-slot sums: the smallest of 4 / 8 / 16 that holds F, 16-channel chunks beyond
 static int feat_chunk(int F) { return F <= 4 ? 4 : F <= 8 ? 8 : 16; }
 
-void gsr_launch_composite_fwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                   const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                                   const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const float *features, int F,
-                                   const uint32_t *row_range, float *out_feat, hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0 || F <= 0) return;
-    const int nf = feat_chunk(F);
-    const dim3 grid(wgs, (F + nf - 1) / nf), block(64 * WAVES);
-    const bool ex = out_depth || out_alpha;
-#define GSR_FWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_fwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, \
-                                              out_color, final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha, features, F, row_range, out_feat)
-    if (ex) {
+// The launch records unpacked into the kernels' parameter lists; LAUNCH(true / false, ...) by the run-time `extra`.  One helper per option, in the order the
+// options were added: the kernels stand in the code object in the order of their first use, and that order is kept.
+#define GSR_FWD_ARGS c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, c.bg, c.out_color, c.final_T, c.n_contrib, c.hdr, c.inst_valid, c.out_depth, c.out_alpha
+#define GSR_BWD_ARGS c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, c.bg, c.dL_dpix, c.final_T, c.n_contrib, c.goff, c.gpart, c.inst_valid, c.inst_dop, \
+                     c.inst_grad, c.hdr, extra ? c.dL_ddepth : nullptr, extra ? c.dL_dalpha : nullptr, c.inst_ddepth
+#define GSR_FWD(E, C) hipLaunchKernelGGL((k_composite_fwd<E, C>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.goff, c.gpart, c.inst_contrib)
+#define GSR_BWD(E, A) hipLaunchKernelGGL((k_composite_bwd<E, A>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.inst_absgrad)
+#define GSR_FWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_fwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.features, c.F, c.row_range, c.out_feat)
+#define GSR_BWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_bwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.features, c.F, c.row_range, c.dL_dfeat)
+#define GSR_FEATGRAD(N) hipLaunchKernelGGL((k_composite_bwd_featgrad<N>), dim3(grid.x, (c.F + N - 1) / N), block, gsr_debug_lds_pad(), c.s, c.W, c.H, c.bx, c.splats, c.bins, \
+                                           c.wg_order, c.point_list, c.final_T, c.n_contrib, c.goff, c.gpart, c.hdr, c.F, c.dL_dfeat, c.inst_dfeat)
+#define GSR_PICK_EXTRA(LAUNCH, OPT) do { if (extra) LAUNCH(true, OPT); else LAUNCH(false, OPT); } while (0)
+static const dim3 block(64 * WAVES);
+
+static void fwd_plain(const GsrCompositeFwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_FWD, false); }
+static void bwd_plain(const GsrCompositeBwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_BWD, false); }
+static void fwd_feat(const GsrCompositeFwd &c, dim3 grid, bool extra) {
+    const int nf = feat_chunk(c.F);
+    grid.y = (c.F + nf - 1) / nf;
+    if (extra) {
         if (nf == 4) GSR_FWD_FEAT(true, 4); else if (nf == 8) GSR_FWD_FEAT(true, 8); else GSR_FWD_FEAT(true, 16);
     } else {
         if (nf == 4) GSR_FWD_FEAT(false, 4); else if (nf == 8) GSR_FWD_FEAT(false, 8); else GSR_FWD_FEAT(false, 16);
     }
-#undef GSR_FWD_FEAT
+}
+static void bwd_feat(const GsrCompositeBwd &c, dim3 grid, bool extra) {
+    if (extra) {
+        if (c.F <= 4) GSR_BWD_FEAT(true, 4); else if (c.F <= 8) GSR_BWD_FEAT(true, 8); else if (c.F <= 16) GSR_BWD_FEAT(true, 16);
+        else if (c.F <= 32) GSR_BWD_FEAT(true, 32); else GSR_BWD_FEAT(true, 64);
+    } else {
+        if (c.F <= 4) GSR_BWD_FEAT(false, 4); else if (c.F <= 8) GSR_BWD_FEAT(false, 8); else if (c.F <= 16) GSR_BWD_FEAT(false, 16);
+        else if (c.F <= 32) GSR_BWD_FEAT(false, 32); else GSR_BWD_FEAT(false, 64);
+    }
+    if (!c.inst_dfeat) return;
+    const int nf = feat_chunk(c.F);
+    if (nf == 4) GSR_FEATGRAD(4); else if (nf == 8) GSR_FEATGRAD(8); else GSR_FEATGRAD(16);
+}
+static void fwd_contrib(const GsrCompositeFwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_FWD, true); }
+static void bwd_absgrad(const GsrCompositeBwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_BWD, true); }
+
+void gsr_launch_composite_fwd(const GsrCompositeFwd &c) {
+    const int wgs = (c.bx / WAVES) * c.by;
+    if (wgs > 0) (c.F > 0 ? fwd_feat : c.inst_contrib ? fwd_contrib : fwd_plain)(c, dim3(wgs), c.out_depth || c.out_alpha);
 }
 
-void gsr_launch_composite_bwd_feat(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                   const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                                   const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                                   GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
-                                   const float *features, int F, const uint32_t *row_range, const float *dL_dfeat, float *inst_dfeat, hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0 || F <= 0 || !dL_dfeat) return;
-    {
-        const dim3 grid(wgs), block(64 * WAVES);
-#define GSR_BWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_bwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, \
-                                              dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, \
-                                              features, F, row_range, dL_dfeat)
-        if (inst_ddepth) {
-            if (F <= 4) GSR_BWD_FEAT(true, 4); else if (F <= 8) GSR_BWD_FEAT(true, 8); else if (F <= 16) GSR_BWD_FEAT(true, 16);
-            else if (F <= 32) GSR_BWD_FEAT(true, 32); else GSR_BWD_FEAT(true, 64);
-        } else {
-            if (F <= 4) GSR_BWD_FEAT(false, 4); else if (F <= 8) GSR_BWD_FEAT(false, 8); else if (F <= 16) GSR_BWD_FEAT(false, 16);
-            else if (F <= 32) GSR_BWD_FEAT(false, 32); else GSR_BWD_FEAT(false, 64);
-        }
-#undef GSR_BWD_FEAT
-    }
-    if (inst_dfeat) {
-        const int nf = feat_chunk(F);
-        const dim3 grid(wgs, (F + nf - 1) / nf), block(64 * WAVES);
-#define GSR_FEATGRAD(N) hipLaunchKernelGGL((k_composite_bwd_featgrad<N>), grid, block, gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, \
-                                           final_T, n_contrib, goff, gpart, hdr, F, dL_dfeat, inst_dfeat)
-        if (nf == 4) GSR_FEATGRAD(4); else if (nf == 8) GSR_FEATGRAD(8); else GSR_FEATGRAD(16);
-#undef GSR_FEATGRAD
-    }
+void gsr_launch_composite_bwd(const GsrCompositeBwd &c) {
+    const int wgs = (c.bx / WAVES) * c.by;
+    if (wgs > 0) (c.dL_dfeat && c.F > 0 ? bwd_feat : c.inst_absgrad ? bwd_absgrad : bwd_plain)(c, dim3(wgs), c.inst_ddepth != nullptr);
 }
 
 void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart,
@@ -1050,40 +1022,11 @@ void gsr_launch_contrib_clear(float4 *inst_contrib, int64_t cap, const GsrHeader
     hipLaunchKernelGGL(k_contrib_clear, dim3((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, inst_contrib, hdr);
 }
 
-void gsr_launch_composite_fwd_contrib(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                      const uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                                      const GsrHeader *hdr, uint8_t *inst_valid, float *out_depth, float *out_alpha, const uint32_t *goff,
-                                      const uint32_t *gpart, float4 *inst_contrib, hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0) return;
-    if (out_depth || out_alpha)
-        hipLaunchKernelGGL((k_composite_fwd<true, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           out_color, final_T, n_contrib, hdr, inst_valid, out_depth, out_alpha, goff, gpart, inst_contrib);
-    else
-        hipLaunchKernelGGL((k_composite_fwd<false, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           out_color, final_T, n_contrib, hdr, inst_valid, nullptr, nullptr, goff, gpart, inst_contrib);
-}
-
 void gsr_launch_contrib_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const float4 *inst_contrib,
                                const GsrHeader *hdr, float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s) {
     if (P <= 0) return;
     hipLaunchKernelGGL(k_contrib_gather, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, row_range, radii, goff, gpart, inst_contrib, hdr, weight_sum,
                        weight_max, pixel_count);
-}
-
-void gsr_launch_composite_bwd_absgrad(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                      const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                                      const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                                      GsrGradAcc *inst_grad, const GsrHeader *hdr, const float *dL_ddepth, const float *dL_dalpha, float *inst_ddepth,
-                                      float2 *inst_absgrad, hipStream_t s) {
-    const int wgs = (bx / WAVES) * by;
-    if (wgs <= 0) return;
-    if (inst_ddepth)
-        hipLaunchKernelGGL((k_composite_bwd<true, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, dL_ddepth, dL_dalpha, inst_ddepth, inst_absgrad);
-    else
-        hipLaunchKernelGGL((k_composite_bwd<false, true>), dim3(wgs), dim3(64 * WAVES), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, nullptr, nullptr, nullptr, inst_absgrad);
 }
 
 void gsr_launch_absgrad_gather(int P, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart, const uint8_t *inst_valid,

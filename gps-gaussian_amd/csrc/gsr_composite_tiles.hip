@@ -536,24 +536,19 @@ __global__ __launch_bounds__(64) void k_selftest_tiles(float *__restrict__ out) 
 
 }  // namespace
 
-void gsr_launch_composite_fwd_tiles(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                    uint32_t *point_list, const float *bg, float *out_color, float *final_T, uint32_t *n_contrib,
-                                    const GsrHeader *hdr, uint8_t *inst_valid, bool keep_state, bool wave_prio, const uint64_t *unsorted_keys, hipStream_t s) {
-    const int wgs = bx * by;
+void gsr_launch_composite_fwd_tiles(const GsrCompositeFwd &c, bool keep_state, bool wave_prio, const uint64_t *unsorted_keys) {
+    const int wgs = c.bx * c.by;
     if (wgs <= 0) return;
-#define GSR_FWD_TILES_LAUNCH(KEEP_, SORT_)                                                                                                                       \
-    hipLaunchKernelGGL((k_composite_fwd_tiles<KEEP_, SORT_>), dim3(wgs), dim3(64), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg, out_color, \
-                       final_T, n_contrib, hdr, KEEP_ ? inst_valid : nullptr, wave_prio ? 1 : 0, unsorted_keys)
+#define GSR_FWD_TILES_LAUNCH(KEEP_, SORT_)                                                                                                                        \
+    hipLaunchKernelGGL((k_composite_fwd_tiles<KEEP_, SORT_>), dim3(wgs), dim3(64), gsr_debug_lds_pad(), c.s, c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, \
+                       c.bg, c.out_color, c.final_T, c.n_contrib, c.hdr, KEEP_ ? c.inst_valid : nullptr, wave_prio ? 1 : 0, unsorted_keys)
     if (keep_state) { if (unsorted_keys) GSR_FWD_TILES_LAUNCH(true, true); else GSR_FWD_TILES_LAUNCH(true, false); }
     else { if (unsorted_keys) GSR_FWD_TILES_LAUNCH(false, true); else GSR_FWD_TILES_LAUNCH(false, false); }
 #undef GSR_FWD_TILES_LAUNCH
 }
 
-void gsr_launch_composite_bwd_tiles(int W, int H, int bx, int by, const GsrSplat *splats, GsrBins bins, const uint32_t *wg_order,
-                                    const uint32_t *point_list, const float *bg, const float *dL_dpix, const float *final_T,
-                                    const uint32_t *n_contrib, const uint32_t *goff, const uint32_t *gpart, uint8_t *inst_valid, float *inst_dop,
-                                    GsrGradAcc *inst_grad, const GsrHeader *hdr, bool color_grad, bool wave_prio, hipStream_t s) {
-    const int wgs = bx * by;
+void gsr_launch_composite_bwd_tiles(const GsrCompositeBwd &c, bool color_grad, bool wave_prio) {
+    const int wgs = c.bx * c.by;
     if (wgs <= 0) return;
     // workgroups the chip holds at once (the first generation): occupancy x compute units, asked once per (device, kernel instantiation) and kept in
     // relaxed atomics (a process may drive several GPUs from several host threads; a lost race only asks the runtime twice).  The LDS pad is a
@@ -575,12 +570,11 @@ void gsr_launch_composite_bwd_tiles(int W, int H, int bx, int by, const GsrSplat
         }
     }
     const uint32_t prio_from_wg = wave_prio ? res : 0u;
-    if (color_grad)
-        hipLaunchKernelGGL(k_composite_bwd_tiles<true>, dim3(wgs), dim3(64), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, prio_from_wg);
-    else
-        hipLaunchKernelGGL(k_composite_bwd_tiles<false>, dim3(wgs), dim3(64), gsr_debug_lds_pad(), s, W, H, bx, splats, bins, wg_order, point_list, bg,
-                           dL_dpix, final_T, n_contrib, goff, gpart, inst_valid, inst_dop, inst_grad, hdr, prio_from_wg);
+#define GSR_BWD_TILES_LAUNCH(CG_)                                                                                                                                 \
+    hipLaunchKernelGGL(k_composite_bwd_tiles<CG_>, dim3(wgs), dim3(64), gsr_debug_lds_pad(), c.s, c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, c.bg, c.dL_dpix, \
+                       c.final_T, c.n_contrib, c.goff, c.gpart, c.inst_valid, c.inst_dop, c.inst_grad, c.hdr, prio_from_wg)
+    if (color_grad) GSR_BWD_TILES_LAUNCH(true); else GSR_BWD_TILES_LAUNCH(false);
+#undef GSR_BWD_TILES_LAUNCH
 }
 
 int gsr_set_wg_trace(unsigned long long *rows_device) {
