@@ -7,7 +7,7 @@ LIB_PATH = os.environ.get("GPSGS_LIB") or os.path.join(_HERE, "lib", "libgpsgs_h
 
 # every symbol include/gpsgs.h declares (tests/test_capi_symbols.py cross-checks this list against the header)
 SYMBOLS = (
-    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features", "gsr_workspace_bytes_contrib", "gsr_forward_contrib", "gsr_workspace_bytes_absgrad", "gsr_backward_absgrad", "gsr_copy_header_async", "gsr_read_header",
+    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features", "gsr_workspace_bytes_contrib", "gsr_forward_contrib", "gsr_workspace_bytes_absgrad", "gsr_backward_absgrad", "gsr_forward_distort", "gsr_backward_distort", "gsr_copy_header_async", "gsr_read_header",
     "gsr_export_state", "gsr_mark_visible", "gsr_selftest", "gsr_timing_read", "gsr_debug_count_records", "gsr_pack_scratch_bytes", "gsr_pack_views", "gsr_pack_views_backward", "fl_scratch_bytes",
     "fl_l1_ssim_forward", "fl_l1_ssim_backward", "up_unproject_forward", "up_unproject_backward", "up_unproject_forward_dev", "up_unproject_backward_dev", "up_splat_scratch_bytes", "up_zsplat", "up_flow2render_dev", "cs_forward", "cs_backward",
     "cv_build_forward", "cv_build_backward", "cs_lookup_forward", "cs_lookup_backward", "cu_upsample_forward", "cu_upsample_backward", "cu_upsample_scratch_bytes",
@@ -78,6 +78,17 @@ class GsrAbsGrad(C.Structure):
     _fields_ = [("absgrad", C.c_void_p), ("reserved", C.c_void_p)]
 
 
+class _DistortSlot(C.Union):
+    _fields_ = [("out_distort", C.c_void_p), ("dL_ddistort", C.c_void_p)]
+
+
+class GsrDistort(C.Structure):
+    """Depth-distortion map of one view (include/gpsgs.h): out_distort fp32 [H, W] (forward) sharing its slot with dL_ddistort (backward), NULL = not
+    wanted; totals fp32 [2, H, W], written by the forward and read by the backward; reserved must be NULL."""
+    _anonymous_ = ("_map",)
+    _fields_ = [("_map", _DistortSlot), ("totals", C.c_void_p), ("reserved", C.c_void_p * 2)]
+
+
 _lib = None
 
 
@@ -141,6 +152,10 @@ def lib():
     l.gsr_workspace_bytes_absgrad.argtypes = [i32, i32, i32, i64, u32]
     l.gsr_backward_absgrad.restype = i32
     l.gsr_backward_absgrad.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrAbsGrad)]
+    l.gsr_forward_distort.restype = i32
+    l.gsr_forward_distort.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrDistort)]
+    l.gsr_backward_distort.restype = i32
+    l.gsr_backward_distort.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrDistort)]
     l.gsr_copy_header_async.restype = i32
     l.gsr_copy_header_async.argtypes = [vp, vp, vp]
     l.gsr_read_header.restype = i32

@@ -210,6 +210,7 @@ struct ForwardCall : ViewCall {
     uint32_t notify_seq;
     const GsrFeatures *feat;     // gsr_forward_features
     const GsrContrib *contrib;   // gsr_forward_contrib
+    const GsrDistort *distort;   // gsr_forward_distort
 };
 struct BackwardCall : ViewCall {
     const int *radii;
@@ -218,6 +219,7 @@ struct BackwardCall : ViewCall {
     const GsrCamGrad *cam;    // gsr_backward_camera / _features / _absgrad with a camera gradient asked for
     const GsrFeatures *feat;  // gsr_backward_features
     const GsrAbsGrad *abs;    // gsr_backward_absgrad
+    const GsrDistort *distort;  // gsr_backward_distort
 };
 
 // One stage of a call: announced (GPSGS_TRACE), bracketed by an event pair (GSR_FLAG_TIMING), launched, checked
@@ -283,6 +285,12 @@ inline bool misaligned(const void *a, const void *b = nullptr, const void *c = n
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 3u) != 0;
 }
 
+// depth-distortion map: is a GsrDistort (NULL = none) one the entry points accept?  (map = out_distort | dL_ddistort: the two share their slot)
+inline bool distort_ok(const GsrDistort *d) {
+    if (!d) return true;
+    return !(misaligned(d->out_distort, d->totals) || d->reserved[0] || d->reserved[1] || (d->out_distort && !d->totals));
+}
+
 int forward_impl(const ForwardCall &c) {
     const int P = c.P, width = c.width, height = c.height;
     const int64_t instance_capacity = c.instance_capacity;
@@ -297,8 +305,11 @@ int forward_impl(const ForwardCall &c) {
     if (misaligned(out_depth, out_alpha)) return GPSGS_E_INVALID;
     const bool stats = con.weight_sum || con.weight_max || con.pixel_count;
     if (!gsr_one_tail(F, stats, false)) return GPSGS_E_INVALID;  // (no entry point passes both)
-    // feature maps, statistics, depth / alpha maps: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
-    const unsigned flags = (F > 0 || stats || out_depth || out_alpha) ? c.flags & ~GSR_FLAG_COMPOSITE_TILES : c.flags;
+    // depth-distortion map: the VALU family's EXTRA + DISTORT forward, its totals in the caller's plane (no workspace tail)
+    if (!distort_ok(c.distort)) return GPSGS_E_INVALID;
+    float *out_distort = c.distort ? c.distort->out_distort : nullptr;
+    // feature maps, statistics, depth / alpha maps, the distortion map: made by the VALU compositing kernels only (the tiles flag is ignored for such a view)
+    const unsigned flags = (F > 0 || stats || out_depth || out_alpha || out_distort) ? c.flags & ~GSR_FLAG_COMPOSITE_TILES : c.flags;
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0 || instance_capacity > 0x7fffffffLL) return GPSGS_E_INVALID;
     if (width > 65535 * GSR_TILE || height > 65535 * GSR_TILE) return GPSGS_E_INVALID;
     if (!c.out_color || !c.workspace) return GPSGS_E_INVALID;
@@ -342,6 +353,8 @@ int forward_impl(const ForwardCall &c) {
         if (hipMemsetAsync(c.out_color, 0, 3 * map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (out_depth && hipMemsetAsync(out_depth, 0, map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (out_alpha && hipMemsetAsync(out_alpha, 0, map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
+        if (out_distort && (hipMemsetAsync(out_distort, 0, map_bytes, s) != hipSuccess || hipMemsetAsync(c.distort->totals, 0, 2 * map_bytes, s) != hipSuccess))
+            return GPSGS_E_LAUNCH;
         if (F > 0 && hipMemsetAsync(c.feat->out_features, 0, (size_t)F * map_bytes, s) != hipSuccess) return GPSGS_E_LAUNCH;
         if (hipMemsetAsync(w.bin_offset, 0, (size_t)(L.NB + 1) * 4, s) != hipSuccess) return GPSGS_E_LAUNCH;
         return check(s, flags);
@@ -393,6 +406,7 @@ int forward_impl(const ForwardCall &c) {
     GsrCompositeFwd k = {width, height, L.bx, L.by, w.splats, w.bins, w.wg_order, w.point_list, c.bg, c.out_color, w.final_T, w.n_contrib, w.hdr, w.inst_valid, s, out_depth, out_alpha};
     if (F > 0) { k.features = c.feat->features; k.F = F; k.row_range = row_range; k.out_feat = c.feat->out_features; }
     if (stats) { k.goff = w.goff; k.gpart = w.gprefix; k.inst_contrib = static_cast<float4 *>(w.tail); }
+    if (out_distort) { k.out_distort = out_distort; k.totals = c.distort->totals; }
     rc = stage("composite_fwd", GSR_STAGE_COMPOSITE_FWD, [&] {
         if (flags & GSR_FLAG_COMPOSITE_TILES) return gsr_launch_composite_fwd_tiles(k, training, (flags & GSR_FLAG_WAVE_PRIORITY) != 0, fused_sort ? w.keys : nullptr);
         if (k.inst_contrib) gsr_launch_contrib_clear(k.inst_contrib, instance_capacity, w.hdr, s);
@@ -411,7 +425,7 @@ extern "C" int gsr_forward_ex(int P, int width, int height, const float *means3D
                               const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                               void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                               void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext) {
-    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, nullptr});
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, nullptr, nullptr});
 }
 
 extern "C" int gsr_forward_features(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -419,7 +433,7 @@ extern "C" int gsr_forward_features(int P, int width, int height, const float *m
                                     const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                     void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                     void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrFeatures *feat) {
-    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, feat, nullptr});
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, feat, nullptr, nullptr});
 }
 
 extern "C" int gsr_forward_contrib(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -427,7 +441,15 @@ extern "C" int gsr_forward_contrib(int P, int width, int height, const float *me
                                    const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                    void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                    void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrContrib *contrib) {
-    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, contrib});
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, contrib, nullptr});
+}
+
+extern "C" int gsr_forward_distort(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                   const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                   const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                                   void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                                   void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrDistort *distort) {
+    return forward_impl({GSR_VIEW_CALL(ext), out_color, radii, host_header_out, notify_seq, nullptr, nullptr, distort});
 }
 
 extern "C" int gsr_forward_notify(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -435,14 +457,14 @@ extern "C" int gsr_forward_notify(int P, int width, int height, const float *mea
                                   const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                                   void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
                                   void *host_header_out, uint32_t notify_seq) {
-    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, host_header_out, notify_seq, nullptr, nullptr});
+    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, host_header_out, notify_seq, nullptr, nullptr, nullptr});
 }
 
 extern "C" int gsr_forward(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
                            const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
                            const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
                            void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream) {
-    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, nullptr, 0u, nullptr, nullptr});
+    return forward_impl({GSR_VIEW_CALL(nullptr), out_color, radii, nullptr, 0u, nullptr, nullptr, nullptr});
 }
 
 extern "C" size_t gsr_camera_grad_scratch_bytes(int P) {
@@ -461,7 +483,6 @@ int backward_impl(const BackwardCall &c) {
     const bool antialias = (c.flags & GSR_FLAG_ANTIALIAS) != 0;
     // depth / alpha gradients (either may be NULL = zero): the VALU family's EXTRA kernels, one more float per instance slot in the workspace
     const float *dL_ddepth = ext ? ext->dL_ddepth : nullptr, *dL_dalpha = ext ? ext->dL_dalpha : nullptr;
-    const bool extras = dL_ddepth || dL_dalpha;
     if (misaligned(dL_ddepth, dL_dalpha)) return GPSGS_E_INVALID;
     // feature maps (either gradient pointer may be NULL): the VALU family's feature kernels, cap x F more floats in the workspace's feature tail
     const int F = feature_channels(c.feat, true, P);
@@ -473,6 +494,10 @@ int backward_impl(const BackwardCall &c) {
     if (c.abs && c.abs->reserved) return GPSGS_E_INVALID;
     float2 *absgrad = c.abs ? reinterpret_cast<float2 *>(c.abs->absgrad) : nullptr;
     if (misaligned(absgrad) || !gsr_one_tail(F, false, absgrad != nullptr)) return GPSGS_E_INVALID;  // (no entry point passes both)
+    // depth-distortion map: the VALU family's EXTRA + DISTORT backward; its dL/dz term rides in inst_ddepth (the depth / alpha workspace size)
+    if (!distort_ok(c.distort)) return GPSGS_E_INVALID;
+    const float *dL_ddistort = c.distort ? c.distort->dL_ddistort : nullptr;
+    const bool extras = dL_ddepth || dL_dalpha || dL_ddistort;
     const unsigned flags = (extras || F > 0 || absgrad) ? c.flags & ~GSR_FLAG_COMPOSITE_TILES : c.flags;  // options only the VALU kernels have
     if (P < 0 || width <= 0 || height <= 0 || instance_capacity < 0) return GPSGS_E_INVALID;
     hipStream_t s = (hipStream_t)c.stream;
@@ -506,6 +531,7 @@ int backward_impl(const BackwardCall &c) {
                          w.inst_grad, w.hdr, s, dL_ddepth, dL_dalpha, extras ? w.inst_ddepth : nullptr};
     if (F > 0) { k.features = c.feat->features; k.F = F; k.row_range = row_range; k.dL_dfeat = dL_dfeat; k.inst_dfeat = feat_sums ? static_cast<float *>(w.tail) : nullptr; }
     if (absgrad) k.inst_absgrad = static_cast<float2 *>(w.tail);  // (the contribution tail's place: dead by now)
+    if (dL_ddistort) { k.dL_ddistort = dL_ddistort; k.totals = c.distort->totals; }
 
     const Stages stage = {c, flags, s};
     // must be the same family as the forward that filled the workspace: the two designs round the exponent differently, and the
@@ -559,7 +585,7 @@ extern "C" int gsr_backward_ex(int P, int width, int height, const float *means3
                                const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
                                float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext) {
-    return backward_impl({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr});
+    return backward_impl({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr, nullptr});
 }
 
 extern "C" int gsr_backward_camera(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
@@ -569,7 +595,7 @@ extern "C" int gsr_backward_camera(int P, int width, int height, const float *me
                                    float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                                    int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                    float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes) {
-    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr},
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr, nullptr},
                                 dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
@@ -581,7 +607,19 @@ extern "C" int gsr_backward_absgrad(int P, int width, int height, const float *m
                                     int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                     float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                     const GsrAbsGrad *abs) {
-    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, abs},
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, abs, nullptr},
+                                dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
+}
+
+extern "C" int gsr_backward_distort(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                                    const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                                    const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                                    const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                                    float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                                    int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                                    float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                                    const GsrDistort *distort) {
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr, distort},
                                 dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
@@ -593,7 +631,7 @@ extern "C" int gsr_backward_features(int P, int width, int height, const float *
                                      int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                                      float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                                      const GsrFeatures *feat) {
-    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, feat, nullptr},
+    return backward_with_camera({GSR_VIEW_CALL(ext), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, feat, nullptr, nullptr},
                                 dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, scratch, scratch_bytes);
 }
 
@@ -603,7 +641,7 @@ extern "C" int gsr_backward(int P, int width, int height, const float *means3D, 
                             const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
                             float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
                             int64_t instance_capacity, unsigned flags, void *stream) {
-    return backward_impl({GSR_VIEW_CALL(nullptr), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr});
+    return backward_impl({GSR_VIEW_CALL(nullptr), radii, dL_dpix, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, nullptr, nullptr, nullptr, nullptr});
 }
 #undef GSR_VIEW_CALL
 

@@ -541,6 +541,8 @@ struct GsrCompositeFwd {
     // contribution statistics (GsrContrib), inst_contrib non-NULL: the same outputs plus {sum w, max w, pixels} per blended instance at its slot
     const uint32_t *goff, *gpart;
     float4 *inst_contrib;
+    // depth-distortion map (GsrDistort), out_distort [H, W] non-NULL: the EXTRA + DISTORT instantiation, which also writes the per-pixel totals [2, H, W]
+    float *out_distort, *totals;
 };
 struct GsrCompositeBwd {
     int W, H, bx, by;
@@ -564,6 +566,8 @@ struct GsrCompositeBwd {
     const float *dL_dfeat;
     float *inst_dfeat;
     float2 *inst_absgrad;  // absgrad (GsrAbsGrad), non-NULL: the same records, inst_dop, inst_ddepth and flags bit for bit, plus {sum_p |t_x|, sum_p |t_y|} per slot
+    // depth-distortion map (GsrDistort), dL_ddistort [H, W] non-NULL: the EXTRA + DISTORT instantiation (inst_ddepth must be set); totals: the forward's plane
+    const float *dL_ddistort, *totals;
 };
 // the VALU family (gsr_composite.hip): the instantiation follows from the optional blocks that are set
 void gsr_launch_composite_fwd(const GsrCompositeFwd &c);

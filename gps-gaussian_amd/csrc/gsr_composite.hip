@@ -87,7 +87,12 @@ __device__ __forceinline__ void contrib_fetch(const GsrSplat *__restrict__ splat
 // max go through wave_reduce_scatter8 once per blend group of eight splats and are parked in LDS.  Once per round lane j writes staged splat j's
 // {sum, max, count, 0} to inst_contrib[slot] -- the instance's Gaussian-major slot, as the backward's records -- if the splat was blended anywhere.
 // Slots nobody writes (not walked, nothing blended, bin-rect cells outside the list) were zeroed by k_contrib_clear in front of this launch.
-template <bool EXTRA, bool CONTRIB = false>
+// DISTORT (on top of EXTRA): the opt-in depth-distortion map (GsrDistort), sum_i sum_j w_i w_j |z_i - z_j| = 2 sum_i w_i (z_i A_<i - D_<i) with the prefix
+// sums A_<i = sum_{j<i} w_j, D_<i = sum_{j<i} w_j z_j of the list order (the list is sorted by the same fp32 depth).  The depths are taken relative to
+// the depth of the bin list's first entry (wave-uniform): the sum does not change under a shift of z, and z A - D then has the size of the depth spread
+// instead of cancelling two numbers of the size of z.  One accumulator and one FMA pair per blended pair; the per-pixel totals {sum w, sum w (z - z0)}
+// go to the caller's [2, H, W] plane for the backward, which reads these very numbers (not the public depth / alpha maps).
+template <bool EXTRA, bool CONTRIB = false, bool DISTORT = false>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
@@ -95,7 +100,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                                                        uint32_t *__restrict__ n_contrib, const GsrHeader *__restrict__ hdr, uint8_t *__restrict__ inst_valid,
                                                        float *__restrict__ out_depth, float *__restrict__ out_alpha,
                                                        const uint32_t *__restrict__ goff = nullptr, const uint32_t *__restrict__ gpart = nullptr,
-                                                       float4 *__restrict__ inst_contrib = nullptr) {
+                                                       float4 *__restrict__ inst_contrib = nullptr, float *__restrict__ out_distort = nullptr,
+                                                       float *__restrict__ totals = nullptr) {
+    static_assert(!DISTORT || EXTRA, "DISTORT reads the staged depths of EXTRA");
     __shared__ float4 sA[WAVES][WAVE];
     __shared__ float4 sB[WAVES][WAVE];
     __shared__ float sC[WAVES][WAVE];
@@ -110,6 +117,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
             if (out_depth) out_depth[q] = 0.f;
             if (out_alpha) out_alpha[q] = 0.f;
         }
+        if (DISTORT && g.inside) {  // a zero map (the backward of an overflowed view does nothing: the totals are zeroed only for tidiness)
+            const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
+            out_distort[q] = 0.f;
+            totals[q] = 0.f;
+            totals[npix + q] = 0.f;
+        }
         return;
     }
     clear_record_flags(inst_valid, hdr, (int)threadIdx.x, 64 * WAVES);
@@ -118,6 +131,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
     float *wC = sC[g.wid], *wD = sD[g.wid];
 
     float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, CD = 0.f, CA = 0.f;
+    float DI = 0.f, DS = 0.f;  // DISTORT: sum_i w_i (zs_i A_<i - DS_<i) and DS = sum w zs, zs = z - z0
     uint32_t last = 0;      // 1-based list position of the last splat that contributed (n_contrib), up to the previous round
     uint32_t last_rnd = 0;  // ... 1-based slot of the last contributor inside the current round (0: none): an inline constant per select
     // Per-lane predicates live as wave-uniform 64-bit masks in SGPRs and are combined on the scalar unit: one v_cmp per test, never a
@@ -125,6 +139,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
     typedef unsigned long long lanemask_t;
     lanemask_t active = __ballot(g.inside);  // pixels inside the image that are not yet saturated
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r0), r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r1);
+    float z0 = 0.f;  // DISTORT: the reference depth, the bin list's first entry's (wave-uniform; the backward takes the same)
+    if constexpr (DISTORT) {
+        if (r0 < r1) z0 = reinterpret_cast<const float4 *>(splats + point_list[r0])[2].y;
+    }
 
     float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
     float nC = 0.f, nD = 0.f;
@@ -181,6 +199,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                     C0 += b.z * w;
                     C1 += b.w * w;
                     C2 += c2 * w;
+                    if constexpr (DISTORT) {  // in front of CA's update: the prefix sums exclude the pair itself (w = 0 adds exact zeros: every operand is finite)
+                        const float zs = wD[j] - z0;
+                        DI = __builtin_fmaf(w, __builtin_fmaf(zs, CA, -DS), DI);
+                        DS = __builtin_fmaf(zs, w, DS);
+                    }
                     if (EXTRA) {
                         CD += wD[j] * w;  // the same contraction as a colour channel: fma(z, w, CD)
                         CA += w;          // alpha as the sum of the weights (its gradient then follows the colour recurrence), not 1 - T
@@ -225,6 +248,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
             if (out_depth) out_depth[q] = CD;
             if (out_alpha) out_alpha[q] = CA;
         }
+        if constexpr (DISTORT) {  // (a view without Gaussians gives 0: DI = CA = DS = 0)
+            out_distort[q] = 2.f * DI;
+            totals[q] = CA;
+            totals[npix + q] = DS;
+        }
     }
 }
 
@@ -237,7 +265,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
 // 0-31 then hold the x term, lanes 32-63 the y term; |.| is an input modifier of that add), four DPP adds make the row sums, and the two row sums per
 // component are parked in one more float4 per staged splat.  The flush lane adds them, scales by 0.5 W (2 / log2 e) resp. 0.5 H (2 / log2 e) once and
 // writes one float2 to inst_absgrad[slot], next to the record -- which, with inst_dop, inst_ddepth and the flag, is written exactly as without it.
-template <bool EXTRA, bool ABSGRAD = false>
+// DISTORT (on top of EXTRA): the distortion map's upstream gradient g.  Walking back to front with the suffix sums behind the pair, d dist / d w_i =
+// 2 [zs_i (A_tot - 2 A_>i) - (D_tot - 2 D_>i)] (the pair's own w cancels) enters cd like one more colour channel whose value differs per pixel, so
+// dL/dopacity, dL/dmean2D and dL/dconic follow through the scalar recurrence; g d dist / d z_i = 2 g w_i (A_tot - 2 A_>i - w_i) joins w dL/ddepth in
+// the row-summed dL/dz.  A_tot, D_tot are the forward's own totals (depths relative to the bin list's first entry, as there); the two carried values
+// are U_A = A_tot - 2 A_>i and U_D = D_tot - 2 D_>i.  With g = 0 every term is an exact zero.
+template <bool EXTRA, bool ABSGRAD = false, bool DISTORT = false>
 __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int bx, const GsrSplat *__restrict__ splats,
                                                        GsrBins bins, const uint32_t *__restrict__ wg_order,
                                                        const uint32_t *__restrict__ point_list, const float *__restrict__ bg,
@@ -246,7 +279,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
                                                        const uint32_t *__restrict__ gpart, uint8_t *__restrict__ inst_valid, float *__restrict__ inst_dop,
                                                        GsrGradAcc *__restrict__ inst_grad, const GsrHeader *__restrict__ hdr,
                                                        const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, float *__restrict__ inst_ddepth,
-                                                       float2 *__restrict__ inst_absgrad = nullptr) {
+                                                       float2 *__restrict__ inst_absgrad = nullptr, const float *__restrict__ dL_ddistort = nullptr,
+                                                       const float *__restrict__ totals = nullptr) {
+    static_assert(!DISTORT || EXTRA, "DISTORT reads the staged depths of EXTRA and writes inst_ddepth");
     constexpr int AB = EXTRA ? 4 : 3;              // ABSGRAD: the float4 of the absolute sums
     constexpr int REC = AB + (ABSGRAD ? 1 : 0);    // float4s per staged splat in sAcc
     __shared__ float4 sA[WAVES][WAVE];
@@ -279,6 +314,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
     if (EXTRA && g.inside) {
         if (dL_ddepth) dd = dL_ddepth[q];
         if (dL_dalpha) da = dL_dalpha[q];
+    }
+    float g2 = 0.f, UA = 0.f, UD = 0.f, z0 = 0.f;  // DISTORT: 2 dL/ddistortion of this pixel, U_A, U_D, the reference depth
+    if constexpr (DISTORT) {
+        if (g.inside) {
+            g2 = 2.f * dL_ddistort[q];
+            UA = totals[q];
+            UD = totals[npix + q];
+        }
+        z0 = reinterpret_cast<const float4 *>(splats + point_list[g.r0])[2].y;  // (g.r0 < g.r1 here)
     }
     const float bg_dot = bg[0] * d0 + bg[1] * d1 + bg[2] * d2;
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
@@ -358,6 +402,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
                 cd = cd + (zd + da);
             }
             const float w = ae * T;  // dchannel/dcolour
+            float dzv = 0.f;         // DISTORT: this pixel's g d dist / d z_i
+            if constexpr (DISTORT) {
+                const float zs = wD[j] - z0;
+                cd = cd + __builtin_fmaf(zs, UA, -UD) * g2;
+                dzv = (g2 * w) * (UA - w);
+                UA = __builtin_fmaf(-2.f, w, UA);
+                UD = __builtin_fmaf(-2.f * w, zs, UD);
+            }
             const float dL_dalpha = (cd - A) * T + nTb * rcp;
             A = ae * cd + om * A;
             const float g_r = w * d0;
@@ -382,7 +434,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
             if (slot >= 0) wAccF[4 * REC * j + slot] = out;  // 12 lanes, 12 distinct words of this splat's record
             if (EXTRA) {
-                const float rz = wave_row_sum(w * dd);  // dL/dz share of this pixel: w dL/ddepth
+                float rz = wave_row_sum(w * dd);  // dL/dz share of this pixel: w dL/ddepth
+                // DISTORT: the map's share in a row sum of its own, so that w dL/ddepth's keeps the operations -- and with g = 0 the bits -- it has without it
+                if constexpr (DISTORT) rz += wave_row_sum(dzv);
                 if ((lane & 15) == 7) wAccF[4 * REC * j + 12 + (lane >> 4)] = rz;
             }
             if constexpr (ABSGRAD) {
@@ -964,8 +1018,8 @@ static int feat_chunk(int F) { return F <= 4 ? 4 : F <= 8 ? 8 : 16; }
 #define GSR_FWD_ARGS c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, c.bg, c.out_color, c.final_T, c.n_contrib, c.hdr, c.inst_valid, c.out_depth, c.out_alpha
 #define GSR_BWD_ARGS c.W, c.H, c.bx, c.splats, c.bins, c.wg_order, c.point_list, c.bg, c.dL_dpix, c.final_T, c.n_contrib, c.goff, c.gpart, c.inst_valid, c.inst_dop, \
                      c.inst_grad, c.hdr, extra ? c.dL_ddepth : nullptr, extra ? c.dL_dalpha : nullptr, c.inst_ddepth
-#define GSR_FWD(E, C) hipLaunchKernelGGL((k_composite_fwd<E, C>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.goff, c.gpart, c.inst_contrib)
-#define GSR_BWD(E, A) hipLaunchKernelGGL((k_composite_bwd<E, A>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.inst_absgrad)
+#define GSR_FWD(E, C) hipLaunchKernelGGL((k_composite_fwd<E, C>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.goff, c.gpart, c.inst_contrib, nullptr, nullptr)
+#define GSR_BWD(E, A) hipLaunchKernelGGL((k_composite_bwd<E, A>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.inst_absgrad, nullptr, nullptr)
 #define GSR_FWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_fwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.features, c.F, c.row_range, c.out_feat)
 #define GSR_BWD_FEAT(E, N) hipLaunchKernelGGL((k_composite_bwd_feat<E, N>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.features, c.F, c.row_range, c.dL_dfeat)
 #define GSR_FEATGRAD(N) hipLaunchKernelGGL((k_composite_bwd_featgrad<N>), dim3(grid.x, (c.F + N - 1) / N), block, gsr_debug_lds_pad(), c.s, c.W, c.H, c.bx, c.splats, c.bins, \
@@ -998,15 +1052,23 @@ static void bwd_feat(const GsrCompositeBwd &c, dim3 grid, bool extra) {
 }
 static void fwd_contrib(const GsrCompositeFwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_FWD, true); }
 static void bwd_absgrad(const GsrCompositeBwd &c, dim3 grid, bool extra) { GSR_PICK_EXTRA(GSR_BWD, true); }
+// the distortion map: EXTRA whatever the depth / alpha pointers are (the maps a call did not ask for stay NULL and are not written)
+static void fwd_distort(const GsrCompositeFwd &c, dim3 grid, bool) {
+    hipLaunchKernelGGL((k_composite_fwd<true, false, true>), grid, block, gsr_debug_lds_pad(), c.s, GSR_FWD_ARGS, c.goff, c.gpart, c.inst_contrib, c.out_distort, c.totals);
+}
+static void bwd_distort(const GsrCompositeBwd &c, dim3 grid, bool) {
+    const bool extra = true;
+    hipLaunchKernelGGL((k_composite_bwd<true, false, true>), grid, block, gsr_debug_lds_pad(), c.s, GSR_BWD_ARGS, c.inst_absgrad, c.dL_ddistort, c.totals);
+}
 
 void gsr_launch_composite_fwd(const GsrCompositeFwd &c) {
     const int wgs = (c.bx / WAVES) * c.by;
-    if (wgs > 0) (c.F > 0 ? fwd_feat : c.inst_contrib ? fwd_contrib : fwd_plain)(c, dim3(wgs), c.out_depth || c.out_alpha);
+    if (wgs > 0) (c.F > 0 ? fwd_feat : c.inst_contrib ? fwd_contrib : c.out_distort ? fwd_distort : fwd_plain)(c, dim3(wgs), c.out_depth || c.out_alpha);
 }
 
 void gsr_launch_composite_bwd(const GsrCompositeBwd &c) {
     const int wgs = (c.bx / WAVES) * c.by;
-    if (wgs > 0) (c.dL_dfeat && c.F > 0 ? bwd_feat : c.inst_absgrad ? bwd_absgrad : bwd_plain)(c, dim3(wgs), c.inst_ddepth != nullptr);
+    if (wgs > 0) (c.dL_dfeat && c.F > 0 ? bwd_feat : c.inst_absgrad ? bwd_absgrad : c.dL_ddistort ? bwd_distort : bwd_plain)(c, dim3(wgs), c.inst_ddepth != nullptr);
 }
 
 void gsr_launch_feature_grad_gather(int P, int F, const uint32_t *row_range, const int *radii, const uint32_t *goff, const uint32_t *gpart,

@@ -476,6 +476,7 @@ def _antialias(rs, antialiasing):
 
 
 _ABSGRAD_FEATURES = "gps_gaussian_amd: return_absgrad cannot be combined with features in one call (the feature backward is another kernel family)"
+_DISTORTION_ALONE = "gps_gaussian_amd: return_distortion cannot be combined with %s in one call (the C-ABI's entry points take one option struct each)"
 
 
 # The opt-ins of one view, resolved once from the public keywords (_view_options) and carried as ONE value to the forward, its backward and whoever
@@ -487,24 +488,29 @@ _ABSGRAD_FEATURES = "gps_gaussian_amd: return_absgrad cannot be combined with fe
 #   contrib       also the three per-Gaussian contribution statistics
 #   absgrad       the backward also writes the absolute screen-space gradient ...
 #   absgrad_sink  ... and then calls this with it, on the backward's stream (internal to pts2render); None = nobody to call
-_ViewOptions = namedtuple("_ViewOptions", "depth_alpha antialiasing camera_grad features contrib absgrad absgrad_sink", defaults=(False,) * 6 + (None,))
+#   distortion    also the depth-distortion map (differentiable)
+_ViewOptions = namedtuple("_ViewOptions", "depth_alpha antialiasing camera_grad features contrib absgrad absgrad_sink distortion",
+                          defaults=(False,) * 6 + (None, False))
 _DEFAULT_OPTIONS = _ViewOptions()
 
 
-def _view_options(rs, depth_alpha=False, antialiasing=False, camera_grad=False, features=None, contrib=False, absgrad=False):
+def _view_options(rs, depth_alpha=False, antialiasing=False, camera_grad=False, features=None, contrib=False, absgrad=False, distortion=False):
     """The public keywords (and the settings object, for its `antialiasing` attribute: _antialias) -> _ViewOptions.  absgrad: True, or the sink
-    callable.  Features cannot be combined with the statistics or absgrad: refused here, before anything is launched."""
+    callable.  Features cannot be combined with the statistics or absgrad, the distortion map with none of the three: refused here, before anything
+    is launched."""
+    if distortion and (features is not None or contrib or absgrad):
+        raise RuntimeError(_DISTORTION_ALONE % ("features" if features is not None else "return_contrib" if contrib else "return_absgrad"))
     if absgrad and features is not None:
         raise RuntimeError(_ABSGRAD_FEATURES)
     if contrib and features is not None:
         raise RuntimeError("gps_gaussian_amd: the contribution statistics cannot be combined with features in one call")
     return _ViewOptions(bool(depth_alpha), _antialias(rs, antialiasing), bool(camera_grad), features is not None, bool(contrib), bool(absgrad),
-                        absgrad if callable(absgrad) else None)
+                        absgrad if callable(absgrad) else None, bool(distortion))
 
 
 # What a view returns, in the documented order; None = not part of this call.  The autograd nodes (here and render_api._RenderBatch, whose batch-wide
 # outputs have no radii) return _pack_outputs() of one and decode outputs, or incoming gradients, with _unpack_outputs().
-_Outputs = namedtuple("_Outputs", "color radii depth alpha feat contrib_weight contrib_max contrib_pixels absgrad", defaults=(None,) * 9)
+_Outputs = namedtuple("_Outputs", "color radii depth alpha feat contrib_weight contrib_max contrib_pixels absgrad distortion", defaults=(None,) * 10)
 
 
 def _pack_outputs(o):
@@ -516,7 +522,7 @@ def _unpack_outputs(opts, values, radii=True):
     """The inverse of _pack_outputs for a call made with `opts` (radii=False: a batch, which returns none): a tuple of outputs, or of the gradients
     autograd hands a backward for them (None for the non-differentiable ones) -> _Outputs."""
     # one entry per field of _Outputs, in its order: is the output part of this call?
-    present = (True, radii, opts.depth_alpha, opts.depth_alpha, opts.features, opts.contrib, opts.contrib, opts.contrib, opts.absgrad)
+    present = (True, radii, opts.depth_alpha, opts.depth_alpha, opts.features, opts.contrib, opts.contrib, opts.contrib, opts.absgrad, opts.distortion)
     it = iter(values)
     return _Outputs(*[next(it) if p else None for p in present])
 
@@ -563,7 +569,8 @@ _ViewState = namedtuple("_ViewState", "raster_settings cap bin_cap family extra_
 
 
 # The tensors a view's backward reads (ctx.saved); None where the other form of an input was given, and for `fea` without features.
-_Saved = namedtuple("_Saved", "m3 col opa sca rot view proj bg radii ws sh cov campos fea")
+# `tot`: the distortion map's per-pixel totals [2, H, W] (None without it).
+_Saved = namedtuple("_Saved", "m3 col opa sca rot view proj bg radii ws sh cov campos fea tot", defaults=(None,))
 
 
 def _workspace_bytes(lib, opts, fwd_only, feat_grad, F, dims):
@@ -574,11 +581,21 @@ def _workspace_bytes(lib, opts, fwd_only, feat_grad, F, dims):
         return lib.gsr_workspace_bytes_features(*dims, F, fwd_only)
     if opts.absgrad and not fwd_only:  # the backward's absolute sums need the absgrad tail (with statistics: inside their larger tail)
         return lib.gsr_workspace_bytes_absgrad(*dims)
-    return (lib.gsr_workspace_bytes_depth_alpha if opts.depth_alpha else lib.gsr_workspace_bytes_ex)(*dims, fwd_only)
+    # (the distortion map's dL/dz rides in the depth / alpha slot array: the same size, no tail of its own)
+    return (lib.gsr_workspace_bytes_depth_alpha if opts.depth_alpha or opts.distortion else lib.gsr_workspace_bytes_ex)(*dims, fwd_only)
 
 
-def _forward_entry(cst, feat):
+def _distort_struct(dmap, totals):
+    """The GsrDistort of a forward (dmap: the map to write) or a backward (dmap: the map's gradient) with the view's totals plane."""
+    d = _capi.GsrDistort()
+    d.out_distort, d.totals = dmap.data_ptr(), totals.data_ptr()
+    return d
+
+
+def _forward_entry(cst, feat, dst=None):
     """-> (name of the forward entry point, the option struct it takes behind the common arguments)."""
+    if dst is not None:
+        return "gsr_forward_distort", (C.byref(dst),)
     if cst is not None:
         return "gsr_forward_contrib", (C.byref(cst),)
     if feat is not None:
@@ -586,11 +603,11 @@ def _forward_entry(cst, feat):
     return "gsr_forward_ex", ()
 
 
-def _backward_entry(lib, P, dev, cam_out, feat, agrad):
+def _backward_entry(lib, P, dev, cam_out, feat, agrad, dst=None):
     """-> (name of the backward entry point, the arguments it takes behind the common ones, the camera scratch slab or None: the caller holds it until
     the call is enqueued).  The three entry points with camera outputs accept NULLs for them (and then need no scratch); the slab is one per view in
     flight (the stream-ordered allocator keeps it alive until this stream's kernels are done)."""
-    if cam_out is None and feat is None and agrad is None:
+    if cam_out is None and feat is None and agrad is None and dst is None:
         return "gsr_backward_ex", (), None
     nbytes = lib.gsr_camera_grad_scratch_bytes(P) if cam_out is not None else 0
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if cam_out is not None else None
@@ -601,6 +618,8 @@ def _backward_entry(lib, P, dev, cam_out, feat, agrad):
         ab = _capi.GsrAbsGrad()
         ab.absgrad = agrad.data_ptr()
         return "gsr_backward_absgrad", cam + (C.byref(ab),), scratch
+    if dst is not None:
+        return "gsr_backward_distort", cam + (C.byref(dst),), scratch
     return "gsr_backward_camera", cam, scratch
 
 
@@ -608,6 +627,7 @@ _NO_OUTPUTS = {}
 _BAD_OUTPUT = dict(  # what _forward_impl raises for a preallocated output it cannot use (and for one a row-range view needs but was not given)
     color="gps_gaussian_amd: out_color must be a contiguous fp32 [3, H, W] tensor on the inputs' device",
     maps="gps_gaussian_amd: out_depth / out_alpha must be contiguous fp32 [H, W] tensors on the inputs' device",
+    distortion="gps_gaussian_amd: the distortion output must be a contiguous fp32 [H, W] tensor on the inputs' device",
     feat="gps_gaussian_amd: out_feat must be a contiguous fp32 [F, H, W] tensor on the inputs' device",
     contrib="gps_gaussian_amd: out_contrib must be contiguous [rows] tensors (fp32, fp32, int32) on the inputs' device",
     no_contrib="gps_gaussian_amd: a row-range view needs its batch-wide statistics arrays (out_contrib)",
@@ -633,7 +653,9 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     backward will not form dL/dfeatures (the workspace gets no feature tail).  contrib: also the per-Gaussian contribution statistics
     (include/gpsgs.h GsrContrib), weight_sum, weight_max fp32 [P] and pixel_count int32 [P], with the VALU family; not with features.  absgrad: the
     view's backward will also write the absolute screen-space gradient (include/gpsgs.h GsrAbsGrad) -- the VALU family, a workspace with the absgrad
-    tail, and a zero-filled fp32 [rows, 2] tensor left in ctx.view.absgrad_out; not with features.
+    tail, and a zero-filled fp32 [rows, 2] tensor left in ctx.view.absgrad_out; not with features.  distortion: also the depth-distortion map
+    [1,H,W] = sum_i sum_j w_i w_j |z_i - z_j| (include/gpsgs.h GsrDistort), with the VALU family; its per-pixel totals [2,H,W] go to ctx.saved.tot for
+    the backward; not with features, contrib or absgrad.
     out: optional dict of preallocated contiguous outputs -- color fp32 [3,H,W]; depth, alpha fp32 [H,W] (or [1,H,W]); feat fp32 [F,H,W];
     radii int32 [rows of the arrays]; contrib: the three statistics tensors; absgrad fp32 [rows, 2], ALREADY zeroed.  A row-range view's radii,
     contrib and absgrad are REQUIRED and batch-wide (its rows are written).
@@ -678,7 +700,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
     st = _dev_state(dev)
     mode = _check_mode()
     family = _composite_flag() | (_wave_priority_flag(st, torch._C._cuda_getCurrentRawStream(dev.index), deterministic=(mode == "none")) if rows is None else 0)
-    if opts.depth_alpha or opts.features or opts.contrib or opts.absgrad:
+    if opts.depth_alpha or opts.features or opts.contrib or opts.absgrad or opts.distortion:
         family = 0  # the depth / alpha and feature maps, the statistics and absgrad are made by the VALU kernels (forward and backward must agree on it)
     extra = _extra_flags  # read ONCE per view and carried to its backward in ctx (the backward runs on an autograd thread)
     base_flags = (_capi.GSR_FLAG_DEBUG if rs.debug else 0) | extra | family | (_capi.GSR_FLAG_ANTIALIAS if opts.antialiasing else 0)
@@ -693,7 +715,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
         f32, bad = torch.float32, _BAD_OUTPUT
         batch_wide = rows is not None  # a row-range view writes its rows of the caller's batch-wide radii / statistics / absgrad arrays
         color = _out_tensor(given.get("color"), (3, H, W), f32, dev, bad["color"], exact=True)
-        depth = alpha = fmap = feat = cstats = cst = agrad = None
+        depth = alpha = fmap = feat = cstats = cst = agrad = dist = tot = dst = None
         if opts.depth_alpha:
             depth = _out_tensor(given.get("depth"), (1, H, W), f32, dev, bad["maps"])
             alpha = _out_tensor(given.get("alpha"), (1, H, W), f32, dev, bad["maps"])
@@ -710,6 +732,10 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
         if opts.absgrad:
             missing = bad["no_absgrad"] if batch_wide else None
             agrad = _out_tensor(given.get("absgrad"), (N, 2), f32, dev, bad["absgrad"], exact=True, zero=True, missing=missing)
+        if opts.distortion:  # (the totals are written by every attempt, the repair included, like the map)
+            dist = _out_tensor(given.get("distortion"), (1, H, W), f32, dev, bad["distortion"])
+            tot = torch.empty((2, H, W), dtype=f32, device=dev)
+            dst = _distort_struct(dist, tot)
         # (only a row-range view takes the caller's radii array: it is batch-wide; a view on its own always gets a fresh one)
         radii = _out_tensor(given.get("radii") if batch_wide else None, (N,), torch.int32, dev, bad["radii"], missing=bad["radii"] if batch_wide else None)
         # inference (no input needs a gradient): skip the backward tail of the workspace (37 B per instance slot)
@@ -720,7 +746,7 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
         # compositing are still running (no GPU idle time)
         ring = _ring(dev) if (mode != "none" and P > 0) else None
         box = [None, 0, 0]  # the workspace, capacity and per-bin capacity of the view's latest attempt
-        what, opt_args = _forward_entry(cst, feat)
+        what, opt_args = _forward_entry(cst, feat, dst)
         entry = getattr(lib, what)
         dmaps = (depth, alpha) if opts.depth_alpha else None
 
@@ -774,8 +800,8 @@ def _forward_impl(ctx, means3D, colors_precomp, opacities, scales, rotations, ra
             _repair_loop(st, note, cur_stream, P, rows is not None, cap, bin_cap, relaunch)
         ws, cap, bin_cap = box  # (inside defer_capacity_checks(): still the first attempt's, a repair replaces them in ctx.view.ws_box)
     ctx.view = _ViewState(rs, cap, bin_cap, family, extra, rows, opts, agrad, ws_box)
-    ctx.saved = _Saved(m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos, fea)
-    return _Outputs(color, radii, depth, alpha, fmap, *(cstats or (None, None, None)), agrad)
+    ctx.saved = _Saved(m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos, fea, tot)
+    return _Outputs(color, radii, depth, alpha, fmap, *(cstats or (None, None, None)), agrad, dist)
 
 
 def _map_grad(g):
@@ -791,7 +817,8 @@ def _backward_impl(ctx, saved, grads, arena, color_grad=True, cam_out=None, feat
     rotations) -- for a row-range view (ctx.view.rows) they are REQUIRED and batch-wide, the view's rows of them are written.
     -> (d_m3, d_m2, d_col, d_op, d_sc, d_rot, d_sh, d_cov); d_sh / d_cov are None unless the forward was given SH coefficients / precomputed
     covariances (d_sc, d_rot are then not meaningful).  grads (an _Outputs): the gradients of the image (color), of the depth and alpha maps of a
-    depth_alpha forward ([H,W] or [1,H,W]) and of the feature map ([F,H,W]); None = zero, and all of them may be None.  cam_out: None, or three
+    depth_alpha forward ([H,W] or [1,H,W]), of the feature map ([F,H,W]) and of the distortion map ([H,W] or [1,H,W]: gsr_backward_distort with the
+    forward's totals, saved.tot); None = zero, and all of them may be None.  cam_out: None, or three
     contiguous fp32 device tensors / None -- dL/d(viewmatrix [16], projmatrix [16], campos [3]) are WRITTEN into them (gsr_backward_camera: the
     per-Gaussian gradients keep their bits).  Features (the forward was given some: saved.fea): feat_out None, or a contiguous fp32 [rows, F] device
     tensor that dL/dfeatures is WRITTEN into (a row-range view: batch-wide, its rows written).  A forward with absgrad (ctx.view.absgrad_out): the
@@ -799,7 +826,7 @@ def _backward_impl(ctx, saved, grads, arena, color_grad=True, cam_out=None, feat
     v = ctx.view
     rs = v.raster_settings
     lib = _capi.lib()
-    m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos, fea = saved
+    m3, col, opa, sca, rot, view, proj, bg, radii, ws, sh, cov, campos, fea, tot = saved
     cap, bin_cap, rows = v.cap, v.bin_cap, v.rows
     if v.ws_box is not None:  # forward ran inside defer_capacity_checks(): the workspace may have been replaced by the overflow repair
         ws, cap, bin_cap = v.ws_box
@@ -829,6 +856,12 @@ def _backward_impl(ctx, saved, grads, arena, color_grad=True, cam_out=None, feat
         dmaps = (_map_grad(grads.depth), _map_grad(grads.alpha))
         if any(t is not None and (t.numel() != H * W or t.device != dev) for t in dmaps):
             raise RuntimeError("gps_gaussian_amd: depth / alpha gradients must have H x W elements on the inputs' device")
+    dst = None
+    if grads.distortion is not None and tot is not None:
+        gd = _map_grad(grads.distortion)
+        if gd.numel() != H * W or gd.device != dev:
+            raise RuntimeError("gps_gaussian_amd: the distortion map's gradient must have H x W elements on the inputs' device")
+        dst = _distort_struct(gd, tot)
     with _device_guard(dev):
         st = _dev_state(dev)
         if _check_mode() != "none":
@@ -855,7 +888,7 @@ def _backward_impl(ctx, saved, grads, arena, color_grad=True, cam_out=None, feat
         if P > 0:
             ext = _ext(rows, 0, (sh, int(rs.sh_degree), campos, cov, d_sh, d_cov) if (sh is not None or cov is not None) else None, bin_cap, dmaps)
             # one entry point for every combination of the opt-ins it serves: camera outputs may be NULL
-            what, opt_args, _scratch = _backward_entry(lib, P, dev, cam_out, feat, agrad)
+            what, opt_args, _scratch = _backward_entry(lib, P, dev, cam_out, feat, agrad, dst)
             rc = getattr(lib, what)(P, W, H, _ptr(m3), _ptr(col), _ptr(opa), _ptr(sca), _ptr(rot), float(rs.scale_modifier),
                                     float(rs.tanfovx), float(rs.tanfovy), _ptr(view), _ptr(proj), _ptr(bg), _ptr(radii), _ptr(g),
                                     _ptr(d_m3), _ptr(d_m2), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_rot), _ptr(ws),
@@ -973,7 +1006,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, *grads):
         opts = ctx.view.opts
         g = _unpack_outputs(opts, grads)
-        if g.color is None and g.depth is None and g.alpha is None and g.feat is None:  # no output took part in the loss
+        if g.color is None and g.depth is None and g.alpha is None and g.feat is None and g.distortion is None:  # no output took part in the loss
             return (None,) * len(ctx.needs_input_grad)
         saved = _Saved(*ctx.saved_tensors)
         cam_out = _cam_grads(ctx.needs_input_grad[11:14], ctx.cams, saved.m3.device) if opts.camera_grad else None
@@ -1005,7 +1038,8 @@ def _rasterize(means3D, means2D, sh, colors_precomp, opacities, scales, rotation
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena=None,
-                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False, return_absgrad=False):
+                        return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False, return_absgrad=False,
+                        return_distortion=False):
     """-> (color [3,H,W], radii [P]); with return_depth_alpha=True (color, radii, depth [1,H,W], alpha [1,H,W]): the depth map sum_i z_i alpha_i T_i
     (view-space z, NOT normalised: divide by alpha for the expected depth) and the accumulated opacity sum_i alpha_i T_i, both with background 0
     and differentiable (include/gpsgs.h GsrViewExt.out_depth).  They are rendered by the VALU compositing kernels whatever GPSGS_COMPOSITE says.
@@ -1023,8 +1057,14 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     means2D.grad[:, :2] (AbsGS's homodirectional gradient, gsplat's absgrad; include/gpsgs.h GsrAbsGrad).  The tensor is zero-filled by the forward, not
     differentiable, and every backward through the node OVERWRITES it in place (it does not accumulate): read it after backward().  Zeros for culled
     Gaussians and for a view that overflowed unrepaired; bitwise reproducible; every other output and gradient keeps the bits of the call without it
-    (VALU kernels).  Combines with everything above except features (RuntimeError before anything is launched)."""
-    opts = _view_options(raster_settings, return_depth_alpha, antialiasing, camera_grad, features, return_contrib, return_absgrad)
+    (VALU kernels).  Combines with everything above except features (RuntimeError before anything is launched).
+    return_distortion=True: also returns, LAST, distortion (fp32 [1,H,W]): the depth-distortion map sum_i sum_j w_i w_j |z_i - z_j| over the splats
+    blended into each pixel (w = alpha T; the distortion term of Mip-NeRF 360 / 2DGS, gsplat's distloss; include/gpsgs.h GsrDistort), in RAW
+    view-space depth units, not normalised -- like the depth map -- with background 0.  Differentiable (opacities, means, scales, rotations and, with
+    camera_grad, the camera); from the image's own blend (the VALU kernels), bitwise reproducible; every other output keeps its bits.  The depth and
+    alpha maps are returned only if return_depth_alpha asks for them too.  Combines with return_depth_alpha, antialiasing, camera_grad, shs and
+    cov3D_precomp; not with features, return_contrib or return_absgrad (RuntimeError before anything is launched)."""
+    opts = _view_options(raster_settings, return_depth_alpha, antialiasing, camera_grad, features, return_contrib, return_absgrad, return_distortion)
     return _rasterize(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_arena, opts, features)
 
 
@@ -1038,13 +1078,14 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                 grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False,
-                return_absgrad=False):
+                return_absgrad=False, return_distortion=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        opts = _view_options(self.raster_settings, return_depth_alpha, antialiasing, camera_grad, features, return_contrib, return_absgrad)
+        opts = _view_options(self.raster_settings, return_depth_alpha, antialiasing, camera_grad, features, return_contrib, return_absgrad,
+                             return_distortion)
         if opts == _DEFAULT_OPTIONS and shs is None and cov3D_precomp is None and grad_arena is None:
             # the reference's call shape (gaussian_renderer/__init__.py:54-62): the compiled host path, when it applies
             out = _fast_forward(means3D, means2D, opacities, colors_precomp, scales, rotations, self.raster_settings)
@@ -1056,7 +1097,7 @@ class GaussianRasterizer(nn.Module):
         # return_depth_alpha=True: (color, radii, depth, alpha), see rasterize_gaussians; antialiasing and camera_grad: the Python host path (not
         # the compiled one)
         # features [P, F]: the feature map is appended to the outputs; return_contrib: the three statistics after it; return_absgrad: the absolute
-        # screen-space gradient last of all, filled by the backward (rasterize_gaussians)
+        # screen-space gradient last of all, filled by the backward; return_distortion: the depth-distortion map, last (rasterize_gaussians)
         return _rasterize(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings, grad_arena, opts,
                           features)
 

@@ -115,7 +115,8 @@ class _RenderBatch(torch.autograd.Function):
         # (pack.pack_features), the feature maps [B,F,H,W] are returned last (rasterizer.rasterize_gaussians(features=...)); contrib: then the
         # per-Gaussian statistics weight_sum, weight_max (fp32) and pixel_count (int32), batch-wide [N] like the packed inputs (each view writes its
         # rows); absgrad: last of all the absolute screen-space gradient [N, 2], zeros here, each view's rows overwritten by every backward
-        # (rasterizer.rasterize_gaussians(return_absgrad=True)); opts.absgrad_sink is then called with it at the end of the backward, on its stream
+        # (rasterizer.rasterize_gaussians(return_absgrad=True)); opts.absgrad_sink is then called with it at the end of the backward, on its stream;
+        # distortion: last, the depth-distortion maps [B,1,H,W] (rasterizer.rasterize_gaussians(return_distortion=True)), differentiable
         # -> rasterizer._pack_outputs of the batch-wide rasterizer._Outputs (no radii)
         bs = len(settings)
         dev = xyz.device
@@ -130,7 +131,8 @@ class _RenderBatch(torch.autograd.Function):
         cstats = (torch.empty((N,), dtype=f32, device=dev), torch.empty((N,), dtype=f32, device=dev),
                   torch.empty((N,), dtype=torch.int32, device=dev)) if opts.contrib else (None, None, None)
         agrad = torch.zeros((N, 2), dtype=f32, device=dev) if opts.absgrad else None
-        outs = _RZ._Outputs(out, None, depth, alpha, fmaps, *cstats, agrad)
+        dist = torch.empty((bs, 1, H, W), dtype=f32, device=dev) if opts.distortion else None  # (each view keeps its own totals plane in its holder)
+        outs = _RZ._Outputs(out, None, depth, alpha, fmaps, *cstats, agrad, dist)
         cur = torch.cuda.current_stream(dev)
         # one HIP stream per sample -- except under graph capture (GPSGS_CHECK=none), where everything stays on the capturing stream
         side = _streams(dev, bs) if (bs > 1 and not torch.cuda.is_current_stream_capturing()) else [cur] * bs
@@ -144,7 +146,7 @@ class _RenderBatch(torch.autograd.Function):
                 with torch.cuda.stream(side[i]):
                     _RZ._forward_impl(h, xyz, rgb, opacity, scale, rot, settings[i], needs, opts,
                                       out=dict(color=out[i], radii=radii, depth=_row(depth, i), alpha=_row(alpha, i), feat=_row(fmaps, i),
-                                               contrib=cstats, absgrad=agrad),
+                                               contrib=cstats, absgrad=agrad, distortion=_row(dist, i)),
                                       rows=_RZ._Rows(offsets, i, cap_rows), features=features, feat_grad=feat_grad)
                 views.append(h)
         for i in range(bs):
@@ -174,13 +176,13 @@ class _RenderBatch(torch.autograd.Function):
     def backward(ctx, *grads):
         opts = ctx.opts
         g = _RZ._unpack_outputs(opts, grads, radii=False)  # (None for the statistics and absgrad: not differentiable)
-        if g.color is None and g.depth is None and g.alpha is None and g.feat is None:
+        if g.color is None and g.depth is None and g.alpha is None and g.feat is None and g.distortion is None:
             return (None,) * len(ctx.needs_input_grad)
         views, side = ctx.views, ctx.side
         xyz, rgb, rot, scale, opacity = ctx.saved_tensors
         dev = xyz.device
         f32c = _RZ._map_grad  # fp32, contiguous
-        g = _RZ._Outputs(color=f32c(g.color), depth=f32c(g.depth), alpha=f32c(g.alpha), feat=f32c(g.feat))
+        g = _RZ._Outputs(color=f32c(g.color), depth=f32c(g.depth), alpha=f32c(g.alpha), feat=f32c(g.feat), distortion=f32c(g.distortion))
         d_feat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev) if ctx.feat_shape is not None else None  # batch-wide, each view writes its rows
         # one gradient buffer per packed tensor (+ one for the unused screen-space gradient); every view's backward writes its own
         # rows, rows behind offsets[-1] (the unused tail of the packed capacity) are never read by the pack backward
@@ -197,7 +199,8 @@ class _RenderBatch(torch.autograd.Function):
                 side[i].wait_stream(cur)
             s = h.saved if h.saved.m3 is not None else h.saved._replace(m3=xyz, col=rgb, opa=opacity.reshape(-1), sca=scale, rot=rot)
             with torch.cuda.stream(side[i]):  # (a workspace replaced by the overflow repair is picked up from h.view.ws_box in there)
-                _RZ._backward_impl(h, s, _RZ._Outputs(color=_row(g.color, i), depth=_row(g.depth, i), alpha=_row(g.alpha, i), feat=_row(g.feat, i)),
+                _RZ._backward_impl(h, s, _RZ._Outputs(color=_row(g.color, i), depth=_row(g.depth, i), alpha=_row(g.alpha, i), feat=_row(g.feat, i),
+                                                      distortion=_row(g.distortion, i)),
                                    (d_xyz, d_rgb, d_op, d_scale, d_rot, d_m2), ctx.color_grad,
                                    None if cam_all is None else tuple(_row(c, i) for c in cam_all), d_feat)
         for i in range(len(views)):
@@ -235,12 +238,12 @@ def _render_view(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_col
     out = rasterizer(means3D=pts_xyz, means2D=screenspace_points, shs=None, colors_precomp=pts_rgb, opacities=opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=None, grad_arena=grad_arena, return_depth_alpha=opts.depth_alpha,
                      antialiasing=opts.antialiasing, camera_grad=opts.camera_grad, features=features, return_contrib=opts.contrib,
-                     return_absgrad=opts.absgrad_sink or opts.absgrad)
+                     return_absgrad=opts.absgrad_sink or opts.absgrad, return_distortion=opts.distortion)
     return _RZ._unpack_outputs(opts, out)
 
 
 def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena=None, antialiasing=False, camera_grad=False,
-              features=None, contrib=False, absgrad=False):
+              features=None, contrib=False, absgrad=False, distortion=False):
     """render() plus the depth and alpha maps of the novel view: {'img': [3,H,W], 'depth': [1,H,W], 'alpha': [1,H,W]}, all differentiable.
     depth = sum_i z_i alpha_i T_i with z_i the view-space depth -- NOT normalised: depth / alpha is the expected depth where alpha > 0 --
     and alpha = sum_i alpha_i T_i (the accumulated opacity, 1 - final transmittance); both have background 0, whatever bg_color is.
@@ -252,14 +255,18 @@ def render_ex(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color,
     'contrib_pixels' (int32 [P], pixels blended into), not differentiable (rasterizer.rasterize_gaussians(return_contrib=True)); not with
     features.  absgrad=True: also 'absgrad' (fp32 [P, 2]), the absolute screen-space gradient sum_p |dL_p/dmean2D_i| in the units of the screen-space
     gradient: zeros until a backward through the view has run, then overwritten in place by each one; not differentiable
-    (rasterizer.rasterize_gaussians(return_absgrad=True)); not with features."""
-    opts = _RZ._view_options(None, True, antialiasing, camera_grad, features, contrib, absgrad)
+    (rasterizer.rasterize_gaussians(return_absgrad=True)); not with features.  distortion=True: also 'distortion' [1,H,W], the depth-distortion map
+    sum_i sum_j w_i w_j |z_i - z_j| of the view's blend in raw view-space depth units (not normalised, background 0), differentiable
+    (rasterizer.rasterize_gaussians(return_distortion=True)); not with features, contrib or absgrad."""
+    opts = _RZ._view_options(None, True, antialiasing, camera_grad, features, contrib, absgrad, distortion)
     o = _render_view(data, idx, pts_xyz, pts_rgb, rotations, scales, opacity, bg_color, grad_arena, opts, features)
     r = {'img': o.color, 'depth': o.depth, 'alpha': o.alpha}
     if opts.features:
         r['feat'] = o.feat
     if opts.absgrad:
         r['absgrad'] = o.absgrad
+    if opts.distortion:
+        r['distortion'] = o.distortion
     if opts.contrib:
         r['contrib_weight'], r['contrib_max'], r['contrib_pixels'] = o.contrib_weight, o.contrib_max, o.contrib_pixels
     return r
@@ -327,12 +334,14 @@ def _write_outputs(data, o, row_of_pixel):
         nv['depth_pred'], nv['alpha_pred'] = o.depth, o.alpha
     if o.feat is not None:
         nv['feat_pred'] = o.feat
+    if o.distortion is not None:
+        nv['distortion_pred'] = o.distortion
     if o.contrib_weight is not None:
         _write_contrib_maps(data, (o.contrib_weight, o.contrib_max, o.contrib_pixels), row_of_pixel)
 
 
 def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camera_grad=False, feature_key=None, with_contrib=False,
-               with_absgrad=False):
+               with_absgrad=False, with_distortion=False):
     """Same contract as the reference's pts2render(): writes data['novel_view']['img_pred'] = [B,3,H,W].  with_depth_alpha=True (opt-in)
     also writes 'depth_pred' and 'alpha_pred' [B,1,H,W] (render_ex: unnormalised depth sum_i z_i alpha_i T_i, accumulated opacity, background 0).
     antialiasing=True (opt-in): every sample is rendered with the opacity-compensated 2D filter (render(antialiasing=True)).
@@ -347,6 +356,8 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
     with_absgrad=True (opt-in): data['lmain'] and data['rmain'] get 'absgrad' [B,2,H,W], zeros now; the BACKWARD of the render node writes every
     Gaussian's absolute screen-space gradient (render_ex(absgrad=True)) to the source pixel it came from, 0 where pts_valid is false -- overwritten by
     each backward, with device index ops only.  Not differentiable; not with feature_key (RuntimeError mentioning features, before any launch).
+    with_distortion=True (opt-in): also writes 'distortion_pred' [B,1,H,W], every sample's depth-distortion map (render_ex(distortion=True)),
+    differentiable back to the source views' maps.  Not with feature_key, with_contrib or with_absgrad (RuntimeError before any launch).
 
     The flatten / mask-gather / concat / rgb-affine of lib/GaussianRender.py:15-34 runs as one fused op for the whole batch
     (pack.py: 3 launches, no sync) instead of 10 boolean-index gathers + syncs per sample, and the B + 1 row offsets STAY ON THE
@@ -362,6 +373,9 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
         raise RuntimeError("gps_gaussian_amd: with_contrib cannot be combined with feature_key")
     if with_absgrad and feature_key is not None:
         raise RuntimeError("gps_gaussian_amd: with_absgrad cannot be combined with feature_key (features)")
+    if with_distortion and (feature_key is not None or with_contrib or with_absgrad):
+        raise RuntimeError(_RZ._DISTORTION_ALONE.replace("return_distortion", "with_distortion")
+                           % ("feature_key (features)" if feature_key is not None else "with_contrib" if with_contrib else "with_absgrad"))
     if with_contrib or with_absgrad or feature_key is not None:
         xyz, rgb, rot, scale, opacity, offsets, row_of_pixel = pack_views(data, return_rows=True)
         if feature_key is not None:
@@ -369,7 +383,7 @@ def pts2render(data, bg_color, with_depth_alpha=False, antialiasing=False, camer
             feats = pack_features(data, feature_key, row_of_pixel)
     else:
         xyz, rgb, rot, scale, opacity, offsets = pack_views(data)
-    opts = _RZ._view_options(None, with_depth_alpha, antialiasing, camera_grad, feats, with_contrib, with_absgrad)
+    opts = _RZ._view_options(None, with_depth_alpha, antialiasing, camera_grad, feats, with_contrib, with_absgrad, with_distortion)
     nv = data['novel_view']
     dev = xyz.device
     sizes_hw = {(int(nv['height'][i]), int(nv['width'][i])) for i in range(bs)}
@@ -420,7 +434,7 @@ def _pts2render_loop(data, bg_color, packed, offs, opts=_RZ._DEFAULT_OPTIONS, fe
     side = _streams(dev, bs) if concurrent else [cur] * bs
     amaps = _absgrad_maps(data) if opts.absgrad else None
     # any map or statistic is wanted: every sample is rendered as render_ex renders it, with the depth / alpha maps too; else as render() does
-    full = opts.depth_alpha or opts.features or opts.contrib or opts.absgrad
+    full = opts.depth_alpha or opts.features or opts.contrib or opts.absgrad or opts.distortion
     view_opts = opts._replace(depth_alpha=True) if full else opts
     with _RZ.defer_capacity_checks():
         for i in range(bs):
@@ -449,7 +463,7 @@ def _pts2render_loop(data, bg_color, packed, offs, opts=_RZ._DEFAULT_OPTIONS, fe
 
     stats = {k: packed_rows(k) for k in _CONTRIB_KEYS} if opts.contrib else {}
     whole = _RZ._Outputs(color=batch('color'), depth=batch('depth') if opts.depth_alpha else None, alpha=batch('alpha') if opts.depth_alpha else None,
-                         feat=batch('feat') if opts.features else None, **stats)
+                         feat=batch('feat') if opts.features else None, distortion=batch('distortion') if opts.distortion else None, **stats)
     _write_outputs(data, whole, row_of_pixel)
     return data
 

@@ -54,7 +54,8 @@ extern "C" {
                                still 4 after the feature maps: GsrFeatures, gsr_workspace_bytes_features, gsr_forward_features,
                                   gsr_backward_features (additive)
                                still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive)
-                               still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive) */
+                               still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive)
+                               still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -382,6 +383,48 @@ int gsr_backward_absgrad(int P, int width, int height, const float *means3D, con
                          int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
                          float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
                          const GsrAbsGrad *abs);
+
+/* Depth-distortion map (opt-in; the distortion term of Mip-NeRF 360 / 2DGS, gsplat's distloss).  Per pixel p, over the splats blended into the image at
+ * p in list order (front to back; w_i = alpha_i T_i, z_i the view-space depth of the splat record, background 0):
+ *   distortion[p] = sum_i sum_j w_i w_j |z_i - z_j| = 2 sum_i w_i (z_i A_<i - D_<i),   A_<i = sum_{j<i} w_j,  D_<i = sum_{j<i} w_j z_j
+ * (the two forms agree because the list is ordered by the same fp32 depth).  Depths are RAW view-space units, not normalised -- like the depth map; the
+ * value does not change under a shift of z and is accumulated relative to the depth of the bin list's first entry.  It uses the image's own splats,
+ * sort order and power > 0 / alpha < 1/255 / T < 1e-4 decisions; an overflowed view and a view without Gaussians give zeros.
+ * Backward, with g = dL/ddistortion[p] and A_>i, D_>i the sums behind i:  d dist / d w_i = 2 [z_i (A_<i - A_>i) - D_<i + D_>i] enters the compositing
+ * backward's scalar recurrence like one more colour channel (so dL/dopacity, dL/dmeans2D, the conic and through it scales / rotations / cov3D follow),
+ * and d dist / d z_i = 2 w_i (A_<i - A_>i) joins the depth map's dL/dz, which reaches dL_dmeans3D through viewmatrix[:, 2] and, with them asked for,
+ * the camera gradients.  With an exact depth tie the pairwise form has a kink; the list-order form's one-sided derivative is what is returned.
+ * `totals` [2, H, W] is caller-owned scratch the forward writes (per pixel sum w and sum w (z - z0)) and the matching backward reads: hand the same
+ * plane to both.  Made by the VALU compositing family, like the depth / alpha maps: the tiles flag is ignored for a view that asks for the map, in the
+ * forward and the backward.  No atomics; the same bits on every run; no host synchronisation.
+ * A NULL struct or a NULL map pointer IS gsr_forward_ex resp. gsr_backward_camera, bit for bit.  GPSGS_E_INVALID for a pointer that is not 4-byte
+ * aligned, a non-NULL `reserved` or a map pointer without `totals`; GPSGS_E_WORKSPACE unless the workspace has the depth / alpha size
+ * (gsr_workspace_bytes_depth_alpha with the call's forward_only: the backward needs forward_only = 0) -- there is no new tail and no new size function.
+ * Combines with the depth / alpha maps and their gradients, antialiasing, camera gradients, shs, cov3D_precomp, row ranges, both list forms and
+ * GSR_FLAG_NO_COLOR_GRAD; not with feature maps, statistics or absgrad (there is no entry point taking two option structs). */
+typedef struct GsrDistort {
+    union {
+        float *out_distort;       /* forward: DEVICE [H, W], written; NULL = not wanted */
+        const float *dL_ddistort; /* backward: DEVICE [H, W], read; NULL = not wanted */
+    };
+    float *totals;     /* DEVICE [2, H, W]: written by the forward, read by the backward */
+    void *reserved[2]; /* NULL */
+} GsrDistort;
+/* gsr_forward_ex's argument list, then the GsrDistort */
+int gsr_forward_distort(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                        const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                        const float *viewmatrix, const float *projmatrix, const float *bg, float *out_color, int *radii,
+                        void *workspace, size_t workspace_bytes, int64_t instance_capacity, unsigned flags, void *stream,
+                        void *host_header_out, uint32_t notify_seq, const GsrViewExt *ext, const GsrDistort *distort);
+/* gsr_backward_camera's argument list, then the GsrDistort */
+int gsr_backward_distort(int P, int width, int height, const float *means3D, const float *colors, const float *opacities,
+                         const float *scales, const float *rotations, float scale_modifier, float tanfovx, float tanfovy,
+                         const float *viewmatrix, const float *projmatrix, const float *bg, const int *radii,
+                         const float *dL_dpix, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacity,
+                         float *dL_dscales, float *dL_drotations, void *workspace, size_t workspace_bytes,
+                         int64_t instance_capacity, unsigned flags, void *stream, const GsrViewExt *ext,
+                         float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *scratch, size_t scratch_bytes,
+                         const GsrDistort *distort);
 
 /* Visibility mask (upstream `_C.mark_visible`, reached through GaussianRasterizer.markVisible(positions) of the module the reference imports at
  * gaussian_renderer/__init__.py:14; the reference itself never calls it): present[i] = 1 iff point i passes the near-plane test of the forward
