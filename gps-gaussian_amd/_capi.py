@@ -13,6 +13,9 @@ SYMBOLS = (
     "cv_build_forward", "cv_build_backward", "cs_lookup_forward", "cs_lookup_backward", "cu_upsample_forward", "cu_upsample_backward", "cu_upsample_scratch_bytes",
 )
 
+# GroupNorm (include/gpsgs.h, its last section; tests/test_capi_groupnorm.py cross-checks this list against the header)
+GN_SYMBOLS = ("gn_chunk_elems", "gn_scratch_bytes", "gn_forward", "gn_backward")
+
 GPSGS_OK, GPSGS_E_INVALID, GPSGS_E_WORKSPACE, GPSGS_E_LAUNCH, GPSGS_E_NO_DEVICE, GPSGS_E_INTERNAL = 0, -1, -2, -3, -4, -5
 _ERR = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failed", -4: "no HIP device",
         -5: "internal self-check failed (debug mode: inconsistent bin lists)"}
@@ -216,6 +219,14 @@ def lib():
     l.cu_upsample_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     l.cu_upsample_scratch_bytes.restype = sz
     l.cu_upsample_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    l.gn_chunk_elems.restype = sz
+    l.gn_chunk_elems.argtypes = []
+    l.gn_scratch_bytes.restype = sz
+    l.gn_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    l.gn_forward.restype = i32
+    l.gn_forward.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+    l.gn_backward.restype = i32
+    l.gn_backward.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     if l.gpsgs_abi_version() != 4:
         raise ImportError("gps_gaussian_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = l

@@ -19,6 +19,12 @@ reference's module ran, the finder SERVES a substitute module for `lib.TaichiRen
 reference's file is never executed.  That is what lets train_stage1.py (:16 imports it, after lib.network -> core.corr has imported corr_sampler
 at :11-12, i.e. after this hook is in place) import and run its validation render.
 
+A second opt-in name, `groupnorm` (GPSGS_ACCELERATE=groupnorm or all,groupnorm), replaces no function of the reference: it wraps the constructors
+of the two classes of core/extractor.py that build `nn.GroupNorm` layers (ResidualBlock, UnetExtractor).  Each wrapper runs the reference's own
+`__init__` and then `groupnorm.convert(self)`, which turns those layers into `FusedGroupNorm` (this package's chip-wide GroupNorm kernels; same
+parameters, same state_dict).  The reference's `forward` bodies run as they are.  Instances are built long after import, so the import order of
+core.extractor against the drop-in does not matter.
+
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
 import importlib.abc
@@ -28,7 +34,7 @@ import sys
 import threading
 
 FEATURES = ("pack", "loss", "corr", "upsample", "unproject")
-OPT_IN = ("splat",)      # accepted by name only, never implied by "all"
+OPT_IN = ("splat", "groupnorm")   # accepted by name only, never implied by "all"
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
@@ -37,6 +43,7 @@ calls = {f: 0 for f in FEATURES + OPT_IN}
 # counted, so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
 calls["loss_passthrough"] = 0
 calls["unproject_passthrough"] = 0
+calls["groupnorm_passthrough"] = 0   # FusedGroupNorm forwards handed to nn.GroupNorm.forward (CPU, channels-last, bf16, ...: groupnorm.py)
 _installed = {}          # "module.attr" -> feature
 _originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), and the two pass-through cases below
 _armed = False           # set by install(); cleared once every requested name is rebound (late_apply() is then a flag test)
@@ -116,6 +123,18 @@ def _depth2pc(depth, extrinsic, intrinsic):
     return _originals["lib.utils.depth2pc"][2](depth, extrinsic, intrinsic)
 
 
+def _converting_init(key):
+    """core/extractor.py:7, :64 -- the reference's own constructor (from _originals), then this package's GroupNorm layers in place of nn.GroupNorm."""
+    def __init__(self, *args, **kwargs):
+        _originals[key][2](self, *args, **kwargs)
+        from . import groupnorm
+        groupnorm.convert(self)
+    return __init__
+
+
+_resblock_init = _converting_init("core.extractor.ResidualBlock.__init__")
+_unet_init = _converting_init("core.extractor.UnetExtractor.__init__")
+
 _corr_cls = None
 
 
@@ -147,6 +166,8 @@ def _table(features):
         t["upsample"].append(("core.raft_stereo_human", "FlowUpdateModule.upsample_flow", _upsample_flow))
     if "unproject" in t:
         t["unproject"] += [("lib.utils", "flow2depth", _flow2depth), ("lib.utils", "depth2pc", _depth2pc)]
+    if "groupnorm" in t:
+        t["groupnorm"] += [("core.extractor", "ResidualBlock.__init__", _resblock_init), ("core.extractor", "UnetExtractor.__init__", _unet_init)]
     return t
 
 

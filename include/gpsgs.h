@@ -31,6 +31,9 @@
  *       the z-buffer splat of lib/TaichiRender.py:13-24 and the whole TaichiRenderBatch.flow2render (:26-60), stage-1 validation render.
  *   fl_l1_ssim_forward / fl_l1_ssim_backward
  *       l1_loss + ssim of lib/loss.py:36-83 (and their autograd backward), called at train_stage2.py:70-72.
+ *   gn_forward / gn_backward (+ gn_chunk_elems, gn_scratch_bytes)
+ *       torch.nn.GroupNorm as the reference's feature extractor builds it (core/extractor.py:17-20, :68: groups of 8 channels x the whole plane)
+ *       and its autograd backward: ATen's one-workgroup-per-row moments kernels, the largest single item of a view's GPU time.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -55,7 +58,8 @@ extern "C" {
                                   gsr_backward_features (additive)
                                still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive)
                                still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive)
-                               still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive) */
+                               still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive)
+                               still 4 after GroupNorm: gn_chunk_elems, gn_scratch_bytes, gn_forward, gn_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -569,6 +573,29 @@ int cu_upsample_forward(const float *flow, const float *mask, float *out, int N,
 size_t cu_upsample_scratch_bytes(int N, int C, int H, int W);
 int cu_upsample_backward(const float *flow, const float *mask, const float *grad_out, float *grad_flow, float *grad_mask, void *scratch,
                          int N, int C, int H, int W, int factor, void *stream);
+
+/* ---- GroupNorm, forward and backward, every row split over the chip ------------------------------------------------------------
+ * x[N,C,HW] contiguous (NCHW with HW = H*W), G groups of C/G channels: y = (x - mean) * rstd * gamma[c] + beta[c] with mean / biased variance over
+ * the L = (C/G)*HW elements of a (sample, group) ROW, rstd = 1/sqrt(var + eps)  (torch.nn.functional.group_norm).
+ * dtype (as cs_forward): 0 = x and dx fp32, 1 = x and dx fp16; y, dy, gamma[C], beta[C], mean[N,G], rstd[N,G], dgamma[C], dbeta[C] are always fp32
+ * and every sum is fp32; dx is rounded once, on store.  x, y, dy and dx must be 16-byte aligned (GPSGS_E_INVALID otherwise).
+ * Rows (forward) and (sample, channel) planes (backward) are cut into chunks of gn_chunk_elems() elements, one workgroup each; per-chunk partials
+ * ({mean, M2}, so a mean far larger than the spread is harmless; {sum dy, sum dy (x - mean)} in the backward) go to `scratch` and are combined in a
+ * fixed order: no atomics, the same bits on every run.
+ * scratch: DEVICE, 8-byte aligned, at least gn_scratch_bytes(N, C, G, HW) =
+ *     8 * N * (C + max(ceil(C*HW / chunk) + G, C * ceil(HW / chunk)))   bytes, chunk = gn_chunk_elems()
+ * -- N*C plane sums, then G * ceil(L / chunk) <= ceil(C*HW / chunk) + G partials per sample (forward) or ceil(HW / chunk) per plane (backward);
+ * forward and backward share the formula, the backward does not need the forward's contents.  0 for a negative size or G <= 0.
+ * gn_forward writes y, mean, rstd.  gn_backward reads x, dy, gamma, mean, rstd (never y: the consumer may have overwritten it in place) and WRITES
+ * dx (x's dtype; NULL = not wanted) and dgamma / dbeta (both or neither; NULL = not wanted).
+ * GPSGS_E_INVALID, before any HIP call: a negative size, G <= 0, C % G != 0, an unknown dtype, one of dgamma / dbeta without the other, a row of
+ * 2^31 elements or more, and -- unless N*C*HW == 0, which returns 0 and launches nothing -- a NULL required pointer or a misaligned one. */
+size_t gn_chunk_elems(void);
+size_t gn_scratch_bytes(int N, int C, int G, int HW);
+int gn_forward(const void *x, int dtype, const float *gamma, const float *beta, int N, int C, int G, int HW, float eps, float *y, float *mean,
+               float *rstd, void *scratch, void *stream);
+int gn_backward(const void *x, int dtype, const float *dy, const float *gamma, const float *mean, const float *rstd, int N, int C, int G, int HW,
+                void *dx, float *dgamma, float *dbeta, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }
