@@ -549,11 +549,26 @@ extern "C" int cs_lookup_backward(const float *coords, const void *grad_out, voi
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
 
+// One thread per element in blocks of 256: does the block count of a * b * c * d elements (non-negative ints) fit a grid's x (<= 0x7fffffff)?
+static bool blocks_fit(int a, int b, int c, int d) {
+    const unsigned long long cap = 0x7fffffffULL * 256;
+    unsigned long long n = (unsigned long long)a * (unsigned long long)b;  // < 2^62
+    if (n > cap) return false;
+    n *= (unsigned long long)c;  // < 2^39 * 2^31
+    if (n > cap) return false;
+    return d == 0 || n <= cap / (unsigned long long)d;
+}
+
+// the kernels form H * factor, W * factor and (backward) W + 63 in int
+static bool fine_dims_fit(int H, int W, int factor) {
+    return (long long)H * factor <= 0x7fffffffLL && (long long)W * factor <= 0x7fffffffLL - 63;
+}
+
 extern "C" int cu_upsample_forward(const float *flow, const float *mask, float *out, int N, int C, int H, int W, int factor, void *stream) {
     if (N < 0 || C < 1 || C > 4 || H < 0 || W < 0 || factor < 1 || factor > 16) return GPSGS_E_INVALID;
+    if ((size_t)N * H == 0 || W == 0) return GPSGS_OK;
+    if (!flow || !mask || !out || !fine_dims_fit(H, W, factor) || !blocks_fit(N, H, factor * factor, W)) return GPSGS_E_INVALID;
     const size_t total = (size_t)N * H * factor * W * factor;
-    if (total == 0) return GPSGS_OK;
-    if (!flow || !mask || !out) return GPSGS_E_INVALID;
     hipLaunchKernelGGL(k_up_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flow, mask, out, N, C, H, W, factor);
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
@@ -569,6 +584,7 @@ extern "C" int cu_upsample_backward(const float *flow, const float *mask, const 
     const size_t total = (size_t)N * H * W;
     if (total == 0) return GPSGS_OK;
     if (!flow || !mask || !grad_out || (!grad_flow && !grad_mask) || (grad_flow && !scratch) || H > 65535 || N > 65535) return GPSGS_E_INVALID;
+    if (!fine_dims_fit(H, W, factor) || (grad_flow && !blocks_fit(N, H, C, W))) return GPSGS_E_INVALID;  // k_up_bwd_flow: one thread per flow element
     hipStream_t s = (hipStream_t)stream;
     float *S = grad_flow ? static_cast<float *>(scratch) : nullptr;
     hipLaunchKernelGGL(k_up_bwd_cells, dim3((W + 63) / 64, H, N), dim3(256), 0, s, flow, mask, grad_out, grad_mask, S, C, H, W, factor);

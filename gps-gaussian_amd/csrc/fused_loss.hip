@@ -14,7 +14,7 @@
 //   k_loss_reduce  sums the partials in double -> {mean L1, mean SSIM};
 //   k_loss_bwd   same tiling, but the 42x42 halo of the three derivative maps IS staged in LDS (read from global directly, as the
 //                forward does, the twelve unaligned 16-byte loads per item made it slower: 125 -> 159 us at [4,3,1024,1024]); then
-//                dL/dpred = gL1 * sign(x1 - x2) / N + gSSIM * (F*M1 + 2 x1 F*M2 + x2 F*M3) / N.
+//                dL/dpred = gL1 * (sign(x1 - x2) / N) + gSSIM * ((F*M1 + 2 x1 F*M2 + x2 F*M3) / N).
 // HBM traffic: forward reads 8 B and writes 12 B per element, backward reads 20 B and writes 4 B -- against roughly 30
 // full-tensor passes in the eager version.
 #include "gsr_common.h"
@@ -222,7 +222,9 @@ __global__ __launch_bounds__(256) void k_loss_bwd(const float *__restrict__ x1g,
             const float a = x1g[q], b = x2g[q];
             const float d = a - b;
             const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);  // torch.abs backward: sign(0) = 0
-            dx1[q] = (g_out2[0] * sgn + g_out2[1] * (f1 + 2.f * a * f2 + b * f3)) * inv_count;
+            // each term is scaled by 1 / N BEFORE the weights: the weighted sum then differs from weight x (that output's gradient taken alone)
+            // only by the roundings of the weighted products and of the sum (at most 2 ulp of the larger term)
+            dx1[q] = g_out2[0] * (sgn * inv_count) + g_out2[1] * ((f1 + 2.f * a * f2 + b * f3) * inv_count);
         }
     }
 }
@@ -238,11 +240,18 @@ Win make_window() {  // lib/loss.py:40-42: exp(-(x-5)^2 / (2 * 1.5^2)), normalis
     return w;
 }
 
+// The grid is (column tiles, row tiles, planes): y and z hold at most 65535 each, the tile count is handed to k_loss_reduce as an int, and the
+// tile counts are formed in int (W + TS - 1 must not wrap).
+bool grid_fits(int planes, int H, int W) {
+    const long long tx = ((long long)W + TS - 1) / TS, ty = ((long long)H + TS - 1) / TS;
+    return planes <= 65535 && ty <= 65535 && W <= 0x7fffffff - (TS - 1) && tx * ty <= 0x7fffffffLL / (planes > 0 ? planes : 1);
+}
+
 }  // namespace
 
 extern "C" size_t fl_scratch_bytes(int planes, int H, int W) {
     if (planes < 0 || H < 0 || W < 0) return 0;
-    return (size_t)planes * ((H + TS - 1) / TS) * ((W + TS - 1) / TS) * sizeof(float2) + 16;
+    return (size_t)planes * (((size_t)H + TS - 1) / TS) * (((size_t)W + TS - 1) / TS) * sizeof(float2) + 16;
 }
 
 extern "C" int fl_l1_ssim_forward(const float *pred, const float *gt, int planes, int H, int W, float *m1, float *m2, float *m3,
@@ -251,6 +260,7 @@ extern "C" int fl_l1_ssim_forward(const float *pred, const float *gt, int planes
     if ((size_t)planes * H * W == 0) return GPSGS_E_INVALID;  // a mean over nothing is undefined (torch returns nan)
     if (!pred || !gt || !scratch || !out2) return GPSGS_E_INVALID;
     if ((m1 || m2 || m3) && !(m1 && m2 && m3)) return GPSGS_E_INVALID;
+    if (!grid_fits(planes, H, W)) return GPSGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((W + TS - 1) / TS, (H + TS - 1) / TS, planes);
     hipLaunchKernelGGL(k_loss_fwd, grid, dim3(256), 0, s, pred, gt, H, W, make_window(), m1, m2, m3, (float2 *)scratch);
@@ -264,6 +274,7 @@ extern "C" int fl_l1_ssim_backward(const float *pred, const float *gt, const flo
     if (planes < 0 || H < 0 || W < 0) return GPSGS_E_INVALID;
     if ((size_t)planes * H * W == 0) return GPSGS_OK;
     if (!pred || !gt || !m1 || !m2 || !m3 || !grad_out2 || !d_pred) return GPSGS_E_INVALID;
+    if (!grid_fits(planes, H, W)) return GPSGS_E_INVALID;
     const dim3 grid((W + TS - 1) / TS, (H + TS - 1) / TS, planes);
     hipLaunchKernelGGL(k_loss_bwd, grid, dim3(256), 0, (hipStream_t)stream, pred, gt, m1, m2, m3, H, W, make_window(), grad_out2,
                        (float)(1.0 / ((double)planes * H * W)), d_pred);

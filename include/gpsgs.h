@@ -495,7 +495,10 @@ int gsr_pack_views_backward(int B, int n_views, int S2, const uint32_t *row_of_p
 /* ---- fused L1 + SSIM loss (lib/loss.py:36-83 as used at train_stage2.py:70-72) ------------------------------------------
  * pred, gt: contiguous fp32 [planes = B*C, H, W].  out2 (device) = {mean |pred - gt|, mean SSIM map} (11x11 Gaussian window,
  * sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2).  m1,m2,m3 [planes,H,W]: derivative maps kept for the backward (all three
- * or none).  scratch: fl_scratch_bytes().  Backward: grad_out2 (device) = {dL/d(mean L1), dL/d(mean SSIM)}; writes d_pred. */
+ * or none).  scratch: fl_scratch_bytes().  Backward: grad_out2 (device) = {dL/d(mean L1), dL/d(mean SSIM)}; writes d_pred.
+ * One workgroup per 32x32 tile, grid = (column tiles, row tiles, planes): GPSGS_E_INVALID for planes > 65535, more than 65535 row tiles,
+ * W > INT_MAX - 31, or a tile count planes x row tiles x column tiles above INT_MAX -- as for a negative size, a NULL pointer, m1 / m2 / m3 given in part and
+ * (forward only: a mean over nothing) an empty tensor; the backward of an empty tensor returns GPSGS_OK and launches nothing. */
 size_t fl_scratch_bytes(int planes, int H, int W);
 int fl_l1_ssim_forward(const float *pred, const float *gt, int planes, int H, int W, float *m1, float *m2, float *m3, void *scratch,
                        float *out2, void *stream);
@@ -568,7 +571,10 @@ int cs_lookup_backward(const float *coords, const void *grad_out, void *const *g
                        int radius, int dtype, void *stream);
 /* flow[N,C,H,W] (C <= 4 forward, <= 2 backward: the reference upsamples a 2-channel flow), mask[N,9*f*f,H,W] logits,
  * out[N,C,f*H,f*W]; fp32.  The backward needs cu_upsample_scratch_bytes() of device scratch when grad_flow is requested
- * (per coarse cell and tap: the sums of softmax weight x upstream gradient); grad_flow / grad_mask may each be NULL. */
+ * (per coarse cell and tap: the sums of softmax weight x upstream gradient); grad_flow / grad_mask may each be NULL, not both.
+ * factor in 1..16.  Empty tensors return GPSGS_OK and launch nothing.  GPSGS_E_INVALID where a launch could not hold the work: the forward runs
+ * one thread per output pixel N*f*H*f*W and the flow gradient one per flow element N*C*H*W, in blocks of 256, and a block count above 0x7fffffff
+ * is refused, as are f*H > INT_MAX and f*W > INT_MAX - 63; the backward also needs N <= 65535 and H <= 65535 (grid z and y). */
 int cu_upsample_forward(const float *flow, const float *mask, float *out, int N, int C, int H, int W, int factor, void *stream);
 size_t cu_upsample_scratch_bytes(int N, int C, int H, int W);
 int cu_upsample_backward(const float *flow, const float *mask, const float *grad_out, float *grad_flow, float *grad_mask, void *scratch,
