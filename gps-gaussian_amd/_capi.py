@@ -15,6 +15,8 @@ SYMBOLS = (
 
 # GroupNorm (include/gpsgs.h, its last section; tests/test_capi_groupnorm.py cross-checks this list against the header)
 GN_SYMBOLS = ("gn_chunk_elems", "gn_scratch_bytes", "gn_forward", "gn_backward")
+# GroupNorm with the ReLU / residual add + ReLU epilogue fused in (the same section; tests/test_capi_groupnorm_epilogue.py)
+GNE_SYMBOLS = ("gne_forward", "gne_backward")
 
 GPSGS_OK, GPSGS_E_INVALID, GPSGS_E_WORKSPACE, GPSGS_E_LAUNCH, GPSGS_E_NO_DEVICE, GPSGS_E_INTERNAL = 0, -1, -2, -3, -4, -5
 _ERR = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failed", -4: "no HIP device",
@@ -227,6 +229,10 @@ def lib():
     l.gn_forward.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     l.gn_backward.restype = i32
     l.gn_backward.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    l.gne_forward.restype = i32
+    l.gne_forward.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+    l.gne_backward.restype = i32
+    l.gne_backward.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     if l.gpsgs_abi_version() != 4:
         raise ImportError("gps_gaussian_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = l

@@ -25,6 +25,12 @@ of the two classes of core/extractor.py that build `nn.GroupNorm` layers (Residu
 parameters, same state_dict).  The reference's `forward` bodies run as they are.  Instances are built long after import, so the import order of
 core.extractor against the drop-in does not matter.
 
+A third, `resblock` (GPSGS_ACCELERATE=resblock; its own tuple OPT_IN_FUSED, never implied by "all" either), goes one step further than `groupnorm`,
+which it implies: besides the conversion it rebinds `core.extractor.ResidualBlock.forward` to `groupnorm.residual_block_forward` -- the same block
+with each `relu_(norm(conv(.)))` and the closing `relu(x + y)` inside the GroupNorm kernels -- and the wrapped `UnetExtractor.__init__` runs
+`groupnorm.fuse_sequential_relu(self)`, which folds the stem's Conv -> GroupNorm -> ReLU the same way.  One wrapper per constructor serves both
+names (`_originals` is keyed by attribute); with `groupnorm` alone exactly the two constructors are wrapped and every forward body is the reference's.
+
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
 import importlib.abc
@@ -35,15 +41,18 @@ import threading
 
 FEATURES = ("pack", "loss", "corr", "upsample", "unproject")
 OPT_IN = ("splat", "groupnorm")   # accepted by name only, never implied by "all"
+OPT_IN_FUSED = ("resblock",)      # likewise by name only; implies the groupnorm conversion and replaces ResidualBlock.forward (see above)
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
-calls = {f: 0 for f in FEATURES + OPT_IN}
+calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED}
 # calls that went THROUGH a replacement but were handed on to the reference's own function (a configuration the fused kernel does not implement):
 # counted, so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
 calls["loss_passthrough"] = 0
 calls["unproject_passthrough"] = 0
 calls["groupnorm_passthrough"] = 0   # FusedGroupNorm forwards handed to nn.GroupNorm.forward (CPU, channels-last, bf16, ...: groupnorm.py)
+calls["resblock_passthrough"] = 0    # residual blocks without GroupNorm layers (norm_fn batch / instance / none): the reference's own forward
+_fuse_relu = False       # set while `resblock` is requested: the constructor wrappers then also run groupnorm.fuse_sequential_relu
 _installed = {}          # "module.attr" -> feature
 _originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), and the two pass-through cases below
 _armed = False           # set by install(); cleared once every requested name is rebound (late_apply() is then a flag test)
@@ -62,10 +71,11 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    bad = [x for x in names if x not in FEATURES + OPT_IN + ("1", "all", "on", "true")]
+    known = FEATURES + OPT_IN + OPT_IN_FUSED
+    bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
-        raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(FEATURES + OPT_IN)))
-    return tuple(f for f in FEATURES + OPT_IN if f in names)
+        raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
+    return tuple(f for f in known if f in names)
 
 
 def installed():
@@ -129,11 +139,21 @@ def _converting_init(key):
         _originals[key][2](self, *args, **kwargs)
         from . import groupnorm
         groupnorm.convert(self)
+        if _fuse_relu:
+            groupnorm.fuse_sequential_relu(self)
     return __init__
 
 
 _resblock_init = _converting_init("core.extractor.ResidualBlock.__init__")
 _unet_init = _converting_init("core.extractor.UnetExtractor.__init__")
+
+
+
+def _resblock_forward(self, x):
+    """core/extractor.py:48 -- the block on the fused norm + ReLU (+ add + ReLU) ops; blocks without GroupNorm run the reference's forward."""
+    from . import groupnorm
+    return groupnorm.residual_block_forward(self, x)
+
 
 _corr_cls = None
 
@@ -166,8 +186,11 @@ def _table(features):
         t["upsample"].append(("core.raft_stereo_human", "FlowUpdateModule.upsample_flow", _upsample_flow))
     if "unproject" in t:
         t["unproject"] += [("lib.utils", "flow2depth", _flow2depth), ("lib.utils", "depth2pc", _depth2pc)]
-    if "groupnorm" in t:
-        t["groupnorm"] += [("core.extractor", "ResidualBlock.__init__", _resblock_init), ("core.extractor", "UnetExtractor.__init__", _unet_init)]
+    if "groupnorm" in t or "resblock" in t:   # one wrapper per constructor, whichever of the two names asks (both: filed under groupnorm)
+        t["groupnorm" if "groupnorm" in t else "resblock"] += [("core.extractor", "ResidualBlock.__init__", _resblock_init),
+                                                                ("core.extractor", "UnetExtractor.__init__", _unet_init)]
+    if "resblock" in t:
+        t["resblock"].append(("core.extractor", "ResidualBlock.forward", _resblock_forward))
     return t
 
 
@@ -185,11 +208,13 @@ def _loaded(name):
 def apply(features=None):
     """Rebind whatever can be rebound NOW (idempotent; called after every reference module finishes loading).  Returns the number of new
     bindings made."""
+    global _fuse_relu
     feats = requested() if features is None else tuple(features)
     if not feats:
         return 0
     made = 0
     with _lock:
+        _fuse_relu = _fuse_relu or "resblock" in feats
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -226,6 +251,7 @@ def apply(features=None):
 
 def restore():
     """Undo every rebinding (tests)."""
+    global _fuse_relu
     with _lock:
         for key, (holder, name, orig) in list(_originals.items()):
             repl = holder.__dict__.get(name) if isinstance(holder, type) else getattr(holder, name, None)
@@ -237,6 +263,7 @@ def restore():
                         d[name] = orig
         _originals.clear()
         _installed.clear()
+        _fuse_relu = False
         for k in calls:
             calls[k] = 0
 

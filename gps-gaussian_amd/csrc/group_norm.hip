@@ -16,6 +16,16 @@
 // No atomics; every sum has a fixed order (per-thread strided, xor tree over the wave, waves in index order): the same bits on every run.
 // Loads and stores are 16 bytes per lane wherever an element index is a multiple of the vector width (all tensor pointers are 16-byte aligned);
 // the ragged head and tail of a chunk (a row that starts off a 16-byte boundary, a length that is no multiple of 4 / 8) go element by element.
+//
+// EPILOGUES (template parameter EP of k_gn_apply / k_gn_bwd_sums / k_gn_bwd_apply; gne_forward / gne_backward): what the reference's extractor runs
+// after every one of these layers, folded into the same passes --
+//   EP_NONE           out = y                               the kernels above, bit for bit
+//   EP_RELU           out = relu(y)                         relu_(norm(conv(x)))
+//   EP_RELU_ADD_RELU  out = relu(res + relu(y))             relu(x + relu_(norm2(...))), res fp32 of x's shape
+// Backward: g = dout masked by the OUTER sign, read from the saved out (the next convolution keeps it alive anyway); dres = g; dy = g masked by the
+// INNER sign, recomputed from x, mean, rstd, gamma, beta with the forward's own expression GN_Y (same bits as the forward stored, so no normalised
+// activation is kept); the GroupNorm backward then runs on dy inside the same two kernels.  The masks are ATen's threshold_backward (v <= 0 -> +0.0f),
+// the sums keep their order: the result is bit for bit what relu_ / add / relu around the EP_NONE kernels give.
 #include <hip/hip_fp16.h>
 
 #include "gsr_common.h"
@@ -74,6 +84,28 @@ template <int V> __device__ __forceinline__ void store_f32(float *p, const float
 #pragma unroll
     for (int q = 0; q < V / 4; q++) reinterpret_cast<float4 *>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
+
+enum { EP_NONE = 0, EP_RELU = 1, EP_RELU_ADD_RELU = 2 };
+
+// The arithmetic every instantiation shares: the forward's y (which the backward evaluates again for the inner sign), the two backward sums and dx.
+// The EP_NONE instantiations keep the expressions as plain text (macros, not functions: they must compile to the instructions they always were, and
+// even a helper inlined in another order changes their schedule); the compiler contracts them to
+//     y  = fma((x - mu) * rs, g, bt)      dx = fma(kd, dy, c1 * d) + c2      s2 = s2 + dy * d  (NOT fused)
+// The epilogue instantiations spell exactly that out, because left alone the compiler picks another contraction for the same text once a select
+// feeds it (dx became fma(c1, d, kd * dy) + c2): their bits must be those of relu_ / add / relu around the EP_NONE kernels.
+__device__ __forceinline__ float gn_y_fused(float x, float mu, float rs, float g, float bt) { return __fmaf_rn((x - mu) * rs, g, bt); }
+__device__ __forceinline__ float gn_dx_fused(float kd, float dy, float c1, float d, float c2) { return __fmaf_rn(kd, dy, c1 * d) + c2; }
+__device__ __forceinline__ void gn_acc_fused(float &s1, float &s2, float dy, float d) {
+#pragma clang fp contract(off)
+    s1 += dy;
+    s2 += dy * d;
+}
+#define GN_Y(x, mu, rs, g, bt) (EP == EP_NONE ? (((x) - (mu)) * (rs) * (g) + (bt)) : gn_y_fused((x), (mu), (rs), (g), (bt)))
+#define GN_DX(kd, dy, c1, d, c2) (EP == EP_NONE ? ((kd) * (dy) + (c1) * (d) + (c2)) : gn_dx_fused((kd), (dy), (c1), (d), (c2)))
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }                  // NaN goes through, as ATen's clamp_min
+__device__ __forceinline__ float mask_f(float sign, float g) { return sign <= 0.f ? 0.f : g; }   // threshold_backward(g, sign, 0): +0.0f where masked
+template <int EP> __device__ __forceinline__ float gn_epilogue(float y, float r) { return EP == EP_RELU ? relu_f(y) : relu_f(r + relu_f(y)); }
+#define GN_OUT(y, r) (EP == EP_NONE ? (y) : gn_epilogue<EP>((y), (r)))
 
 // Elements [b, e) of the tensor (e - b <= GN_CHUNK) as: head [b, b + nh), nvec vectors of V from v0 (a multiple of V), tail [e - nt, e); nh, nt < V.
 // Vector j * 256 + tid belongs to thread tid; head element k to thread k, tail element k to thread 64 + k (another wave).
@@ -145,12 +177,14 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_moments(const typename XT<DT>
     if (tid == 0) partial[blockIdx.x] = make_float2(mean, m2);
 }
 
-template <int DT>
+// res: the residual of EP_RELU_ADD_RELU (not read otherwise)
+template <int DT, int EP>
 __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ gamma,
                                                          const float *__restrict__ beta, const float2 *__restrict__ partial, int L, int chunks, int HW,
                                                          int cpg, int G, float eps, float *__restrict__ y, float *__restrict__ mean_out,
-                                                         float *__restrict__ rstd_out) {
+                                                         float *__restrict__ rstd_out, const float *__restrict__ res) {
     constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
     const unsigned row = blockIdx.x / (unsigned)chunks, ck = blockIdx.x - row * (unsigned)chunks;
@@ -163,6 +197,13 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::
     size_t ei;
     const bool edge = edge_index(s, tid, ei);
     if (edge) ev = XT<DT>::load1(x + ei);
+    float rv[RES ? NV : 1][V], er = 0.f;  // the residual's loads are in flight with x's, over the combine below
+    if constexpr (RES) {
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (j * GN_THREADS + tid < s.nvec) load_f32<V>(res + s.v0 + (size_t)(j * GN_THREADS + tid) * V, rv[j]);
+        if (edge) er = res[ei];
+    }
 
     // the row's moments from its chunks' {mean_i, M2_i} (Chan): mean = m0 + sum n_i (mean_i - m0) / L, M2 = sum M2_i + n_i (mean_i - mean)^2
     const float2 *pr = partial + (size_t)row * chunks;
@@ -197,12 +238,12 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::
             if (left >= (unsigned)V) {
                 const float g = gamma[c0 + cc], bt = beta[c0 + cc];
 #pragma unroll
-                for (int k = 0; k < V; k++) out[k] = (v[j][k] - mu) * rs * g + bt;
+                for (int k = 0; k < V; k++) out[k] = GN_OUT(GN_Y(v[j][k], mu, rs, g, bt), rv[RES ? j : 0][k]);
             } else {
 #pragma unroll
                 for (int k = 0; k < V; k++) {
                     const unsigned c = c0 + (o + k) / (unsigned)HW;
-                    out[k] = (v[j][k] - mu) * rs * gamma[c] + beta[c];
+                    out[k] = GN_OUT(GN_Y(v[j][k], mu, rs, gamma[c], beta[c]), rv[RES ? j : 0][k]);
                 }
             }
             store_f32<V>(y + i, out);
@@ -210,29 +251,42 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::
     }
     if (edge) {
         const unsigned c = c0 + (unsigned)(ei - r0) / (unsigned)HW;
-        y[ei] = (ev - mu) * rs * gamma[c] + beta[c];
+        y[ei] = GN_OUT(GN_Y(ev, mu, rs, gamma[c], beta[c]), er);
     }
 }
 
-template <int DT>
+// EP != EP_NONE: `dy` is the gradient of the epilogue's output; it is masked here, element by element, to the gradient of y (see the top of the file).
+// out: the forward's output, read by EP_RELU_ADD_RELU only.
+template <int DT, int EP>
 __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ dy,
                                                             const float *__restrict__ mean, int HW, int chunks, int C, int cpg, int G,
-                                                            float2 *__restrict__ partial) {
+                                                            float2 *__restrict__ partial, const float *__restrict__ gamma,
+                                                            const float *__restrict__ beta, const float *__restrict__ rstd,
+                                                            const float *__restrict__ out) {
     constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
     const unsigned plane = blockIdx.x / (unsigned)chunks, ck = blockIdx.x - plane * (unsigned)chunks;
     const unsigned n = plane / (unsigned)C, c = plane - n * (unsigned)C;
     const float mu = mean[(size_t)n * G + c / (unsigned)cpg];
+    float rs = 0.f, gm = 0.f, bt = 0.f;
+    if constexpr (EP != EP_NONE) {
+        rs = rstd[(size_t)n * G + c / (unsigned)cpg];
+        gm = gamma[c];
+        bt = beta[c];
+    }
     const size_t p0 = (size_t)plane * HW, b = p0 + (size_t)ck * GN_CHUNK, e = min(b + (size_t)GN_CHUNK, p0 + (size_t)HW);
     const Span s = make_span<V>(b, e);
     float xv[NV][V], gv[NV][V];  // every load of the chunk is issued before the first sum waits for one
+    float ov[RES ? NV : 1][V];
 #pragma unroll
     for (int j = 0; j < NV; j++) {
         const int vi = j * GN_THREADS + tid;
         if (vi < s.nvec) {
             XT<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
             load_f32<V>(dy + s.v0 + (size_t)vi * V, gv[j]);
+            if constexpr (RES) load_f32<V>(out + s.v0 + (size_t)vi * V, ov[j]);
         }
     }
     float s1 = 0.f, s2 = 0.f;
@@ -241,28 +295,43 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT
         if (j * GN_THREADS + tid < s.nvec) {
 #pragma unroll
             for (int k = 0; k < V; k++) {
-                s1 += gv[j][k];
-                s2 += gv[j][k] * (xv[j][k] - mu);
+                if constexpr (RES) gv[j][k] = mask_f(ov[RES ? j : 0][k], gv[j][k]);
+                if constexpr (EP != EP_NONE) gv[j][k] = mask_f(GN_Y(xv[j][k], mu, rs, gm, bt), gv[j][k]);
+                if constexpr (EP == EP_NONE) {
+                    s1 += gv[j][k];
+                    s2 += gv[j][k] * (xv[j][k] - mu);
+                } else {
+                    gn_acc_fused(s1, s2, gv[j][k], xv[j][k] - mu);
+                }
             }
         }
     size_t ei;
     if (edge_index(s, tid, ei)) {
-        const float g = dy[ei];
-        s1 += g;
-        s2 += g * (XT<DT>::load1(x + ei) - mu);
+        float g = dy[ei];
+        if constexpr (RES) g = mask_f(out[ei], g);
+        if constexpr (EP != EP_NONE) g = mask_f(GN_Y(XT<DT>::load1(x + ei), mu, rs, gm, bt), g);
+        if constexpr (EP == EP_NONE) {
+            s1 += g;
+            s2 += g * (XT<DT>::load1(x + ei) - mu);
+        } else {
+            gn_acc_fused(s1, s2, g, XT<DT>::load1(x + ei) - mu);
+        }
     }
     const float2 t = block_sum2(s1, s2, red);
     if (tid == 0) partial[blockIdx.x] = t;
 }
 
-// gchunks = chunks (one workgroup per chunk, dx written) or 1 (dx not wanted: one workgroup per plane, which only stores the plane's sums)
-template <int DT>
+// gchunks = chunks (one workgroup per chunk, dx and / or dres written) or 1 (neither wanted: one workgroup per plane, which only stores the plane's
+// sums).  dres (EP_RELU_ADD_RELU only; NULL = not wanted) receives the outer-masked gradient.
+template <int DT, int EP>
 __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ dy,
                                                              const float *__restrict__ gamma, const float *__restrict__ mean,
                                                              const float *__restrict__ rstd, const float2 *__restrict__ partial, int HW, int chunks,
                                                              int gchunks, int C, int cpg, int G, typename XT<DT>::T *__restrict__ dx,
-                                                             float2 *__restrict__ sums) {
+                                                             float2 *__restrict__ sums, const float *__restrict__ beta,
+                                                             const float *__restrict__ out, float *__restrict__ dres) {
     constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
     const unsigned plane = blockIdx.x / (unsigned)gchunks, ck = blockIdx.x - plane * (unsigned)gchunks;
@@ -276,17 +345,19 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
         const float2 t = block_sum2(a, bb, red);
         if (tid == 0) sums[plane] = t;
     }
-    if (dx == nullptr) return;
+    if (dx == nullptr && (!RES || dres == nullptr)) return;
     const unsigned n = plane / (unsigned)C, c = plane - n * (unsigned)C, g = c / (unsigned)cpg;
     const size_t p0 = (size_t)plane * HW, b = p0 + (size_t)ck * GN_CHUNK, e = min(b + (size_t)GN_CHUNK, p0 + (size_t)HW);
     const Span s = make_span<V>(b, e);
     float xv[NV][V], gv[NV][V], ex = 0.f, eg = 0.f;
+    float ov[RES ? NV : 1][V], eo = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; j++) {
         const int vi = j * GN_THREADS + tid;
         if (vi < s.nvec) {
             XT<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
             load_f32<V>(dy + s.v0 + (size_t)vi * V, gv[j]);
+            if constexpr (RES) load_f32<V>(out + s.v0 + (size_t)vi * V, ov[j]);
         }
     }
     size_t ei;
@@ -294,6 +365,21 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
     if (edge) {
         ex = XT<DT>::load1(x + ei);
         eg = dy[ei];
+        if constexpr (RES) eo = out[ei];
+    }
+    if constexpr (RES) {  // the outer mask; what is left is the residual's gradient
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (j * GN_THREADS + tid < s.nvec) {
+#pragma unroll
+                for (int k = 0; k < V; k++) gv[j][k] = mask_f(ov[j][k], gv[j][k]);
+                if (dres != nullptr) store_f32<V>(dres + s.v0 + (size_t)(j * GN_THREADS + tid) * V, gv[j]);
+            }
+        if (edge) {
+            eg = mask_f(eo, eg);
+            if (dres != nullptr) dres[ei] = eg;
+        }
+        if (dx == nullptr) return;
     }
     // the group's sums: sum_c gamma[c] sum dy, sum_c gamma[c] sum dy (x - mean) over the group's cpg planes x chunks partials, in a fixed order
     const float2 *pg = partial + ((size_t)n * C + (size_t)g * cpg) * chunks;
@@ -310,17 +396,28 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
     const size_t row = (size_t)n * G + g;
     const float mu = mean[row], rs = rstd[row], m = (float)cpg * (float)HW;
     const float kd = rs * gamma[c], c1 = -(rs * rs * rs) * t.y / m, c2 = -rs * t.x / m;
+    float gm = 0.f, bt = 0.f;
+    if constexpr (EP != EP_NONE) {
+        gm = gamma[c];
+        bt = beta[c];
+    }
 #pragma unroll
     for (int j = 0; j < NV; j++) {
         const int vi = j * GN_THREADS + tid;
         if (vi < s.nvec) {
-            float out[V];
+            float o[V];
 #pragma unroll
-            for (int k = 0; k < V; k++) out[k] = kd * gv[j][k] + c1 * (xv[j][k] - mu) + c2;
-            XT<DT>::store(dx + s.v0 + (size_t)vi * V, out);
+            for (int k = 0; k < V; k++) {
+                if constexpr (EP != EP_NONE) gv[j][k] = mask_f(GN_Y(xv[j][k], mu, rs, gm, bt), gv[j][k]);
+                o[k] = GN_DX(kd, gv[j][k], c1, xv[j][k] - mu, c2);
+            }
+            XT<DT>::store(dx + s.v0 + (size_t)vi * V, o);
         }
     }
-    if (edge) XT<DT>::store1(dx + ei, kd * eg + c1 * (ex - mu) + c2);
+    if (edge) {
+        if constexpr (EP != EP_NONE) eg = mask_f(GN_Y(ex, mu, rs, gm, bt), eg);
+        XT<DT>::store1(dx + ei, GN_DX(kd, eg, c1, ex - mu, c2));
+    }
 }
 
 __global__ __launch_bounds__(GN_THREADS) void k_gn_param_grad(const float2 *__restrict__ sums, const float *__restrict__ rstd, int N, int C, int cpg,
@@ -360,23 +457,49 @@ extern "C" size_t gn_scratch_bytes(int N, int C, int G, int HW) {
     return 8 * (size_t)N * ((size_t)C + (rows > planes ? rows : planes));
 }
 
+namespace {
+
+template <int DT, int EP>
+void launch_forward(const void *x, const float *gamma, const float *beta, const float *res, int N, int C, int G, int HW, float eps, float *out,
+                    float *mean, float *rstd, void *scratch, hipStream_t s) {
+    typedef const typename XT<DT>::T *XP;
+    const int cpg = C / G, L = cpg * HW, chunks = (int)cdiv(L, GN_CHUNK);
+    const dim3 grid((unsigned)((size_t)N * G * chunks)), block(GN_THREADS);
+    float2 *partial = (float2 *)scratch + (size_t)N * C;
+    hipLaunchKernelGGL((k_gn_moments<DT>), grid, block, 0, s, (XP)x, L, chunks, partial);
+    hipLaunchKernelGGL((k_gn_apply<DT, EP>), grid, block, 0, s, (XP)x, gamma, beta, (const float2 *)partial, L, chunks, HW, cpg, G, eps, out, mean, rstd,
+                       res);
+}
+
+template <int DT, int EP>
+void launch_backward(const void *x, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                     int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch, hipStream_t s) {
+    typedef typename XT<DT>::T X;
+    const int cpg = C / G, chunks = (int)cdiv(HW, GN_CHUNK), gchunks = dx || dres ? chunks : 1;
+    const dim3 block(GN_THREADS);
+    float2 *sums = (float2 *)scratch, *partial = sums + (size_t)N * C;
+    const unsigned planes = (unsigned)N * (unsigned)C;
+    hipLaunchKernelGGL((k_gn_bwd_sums<DT, EP>), dim3(planes * chunks), block, 0, s, (const X *)x, dout, mean, HW, chunks, C, cpg, G, partial, gamma, beta,
+                       rstd, out);
+    hipLaunchKernelGGL((k_gn_bwd_apply<DT, EP>), dim3(planes * gchunks), block, 0, s, (const X *)x, dout, gamma, mean, rstd, (const float2 *)partial, HW,
+                       chunks, gchunks, C, cpg, G, (X *)dx, sums, beta, out, dres);
+    if (dgamma)
+        hipLaunchKernelGGL(k_gn_param_grad, dim3((unsigned)cdiv(C, GN_THREADS)), block, 0, s, (const float2 *)sums, rstd, N, C, cpg, G, dgamma, dbeta);
+}
+
+}  // namespace
+
 extern "C" int gn_forward(const void *x, int dtype, const float *gamma, const float *beta, int N, int C, int G, int HW, float eps, float *y,
                           float *mean, float *rstd, void *scratch, void *stream) {
     const int rc = gn_check(dtype, N, C, G, HW);
     if (rc != 0) return rc < 0 ? rc : GPSGS_OK;
     if (!x || !gamma || !beta || !y || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
     if (!aligned16(x) || !aligned16(y) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
-    const int cpg = C / G, L = cpg * HW, chunks = (int)cdiv(L, GN_CHUNK);
-    const dim3 grid((unsigned)((size_t)N * G * chunks)), block(GN_THREADS);
-    float2 *partial = (float2 *)scratch + (size_t)N * C;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0) {
-        hipLaunchKernelGGL(k_gn_moments<0>, grid, block, 0, s, (const float *)x, L, chunks, partial);
-        hipLaunchKernelGGL(k_gn_apply<0>, grid, block, 0, s, (const float *)x, gamma, beta, (const float2 *)partial, L, chunks, HW, cpg, G, eps, y, mean, rstd);
-    } else {
-        hipLaunchKernelGGL(k_gn_moments<1>, grid, block, 0, s, (const __half *)x, L, chunks, partial);
-        hipLaunchKernelGGL(k_gn_apply<1>, grid, block, 0, s, (const __half *)x, gamma, beta, (const float2 *)partial, L, chunks, HW, cpg, G, eps, y, mean, rstd);
-    }
+    if (dtype == 0)
+        launch_forward<0, EP_NONE>(x, gamma, beta, nullptr, N, C, G, HW, eps, y, mean, rstd, scratch, s);
+    else
+        launch_forward<1, EP_NONE>(x, gamma, beta, nullptr, N, C, G, HW, eps, y, mean, rstd, scratch, s);
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
 
@@ -389,21 +512,59 @@ extern "C" int gn_backward(const void *x, int dtype, const float *dy, const floa
     if (!x || !dy || !gamma || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
     if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
     if (!dx && !dgamma) return GPSGS_OK;
-    const int cpg = C / G, chunks = (int)cdiv(HW, GN_CHUNK), gchunks = dx ? chunks : 1;
-    const dim3 block(GN_THREADS);
-    float2 *sums = (float2 *)scratch, *partial = sums + (size_t)N * C;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned planes = (unsigned)N * (unsigned)C;
+    if (dtype == 0)
+        launch_backward<0, EP_NONE>(x, dy, nullptr, gamma, nullptr, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
+    else
+        launch_backward<1, EP_NONE>(x, dy, nullptr, gamma, nullptr, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
+    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+}
+
+// ---- the same with the epilogue fused (see the top of the file): residual == NULL / out == NULL select EP_RELU, otherwise EP_RELU_ADD_RELU ----
+extern "C" int gne_forward(const void *x, int dtype, const float *gamma, const float *beta, const float *residual, int N, int C, int G, int HW,
+                           float eps, float *out, float *mean, float *rstd, void *scratch, void *stream) {
+    const int rc = gn_check(dtype, N, C, G, HW);
+    if (rc != 0) return rc < 0 ? rc : GPSGS_OK;
+    if (!x || !gamma || !beta || !out || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
+    if (!aligned16(x) || !aligned16(out) || !aligned16(residual) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
     if (dtype == 0) {
-        hipLaunchKernelGGL(k_gn_bwd_sums<0>, dim3(planes * chunks), block, 0, s, (const float *)x, dy, mean, HW, chunks, C, cpg, G, partial);
-        hipLaunchKernelGGL(k_gn_bwd_apply<0>, dim3(planes * gchunks), block, 0, s, (const float *)x, dy, gamma, mean, rstd, (const float2 *)partial, HW,
-                           chunks, gchunks, C, cpg, G, (float *)dx, sums);
+        if (residual)
+            launch_forward<0, EP_RELU_ADD_RELU>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, s);
+        else
+            launch_forward<0, EP_RELU>(x, gamma, beta, nullptr, N, C, G, HW, eps, out, mean, rstd, scratch, s);
     } else {
-        hipLaunchKernelGGL(k_gn_bwd_sums<1>, dim3(planes * chunks), block, 0, s, (const __half *)x, dy, mean, HW, chunks, C, cpg, G, partial);
-        hipLaunchKernelGGL(k_gn_bwd_apply<1>, dim3(planes * gchunks), block, 0, s, (const __half *)x, dy, gamma, mean, rstd, (const float2 *)partial, HW,
-                           chunks, gchunks, C, cpg, G, (__half *)dx, sums);
+        if (residual)
+            launch_forward<1, EP_RELU_ADD_RELU>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, s);
+        else
+            launch_forward<1, EP_RELU>(x, gamma, beta, nullptr, N, C, G, HW, eps, out, mean, rstd, scratch, s);
     }
-    if (dgamma)
-        hipLaunchKernelGGL(k_gn_param_grad, dim3((unsigned)cdiv(C, GN_THREADS)), block, 0, s, (const float2 *)sums, rstd, N, C, cpg, G, dgamma, dbeta);
+    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+}
+
+extern "C" int gne_backward(const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
+                            const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch,
+                            void *stream) {
+    const int rc = gn_check(dtype, N, C, G, HW);
+    if (rc < 0) return rc;
+    if ((dgamma != nullptr) != (dbeta != nullptr)) return GPSGS_E_INVALID;
+    if (dres && !out) return GPSGS_E_INVALID;  // only the residual form has a residual to differentiate
+    if (rc != 0) return GPSGS_OK;
+    if (!x || !dout || !gamma || !beta || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
+    if (!aligned16(x) || !aligned16(dout) || !aligned16(out) || !aligned16(dx) || !aligned16(dres) || ((uintptr_t)scratch & 7) != 0)
+        return GPSGS_E_INVALID;
+    if (!dx && !dres && !dgamma) return GPSGS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == 0) {
+        if (out)
+            launch_backward<0, EP_RELU_ADD_RELU>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch, s);
+        else
+            launch_backward<0, EP_RELU>(x, dout, nullptr, gamma, beta, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
+    } else {
+        if (out)
+            launch_backward<1, EP_RELU_ADD_RELU>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch, s);
+        else
+            launch_backward<1, EP_RELU>(x, dout, nullptr, gamma, beta, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
+    }
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }

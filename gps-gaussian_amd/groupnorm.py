@@ -5,10 +5,16 @@ to two million elements, so most of the chip idles while a handful of CUs stream
 `_capi.lib().gn_chunk_elems()` elements, one workgroup each (DESIGN.md "GroupNorm").
 
   group_norm(x, num_groups, weight, bias, eps)   the op (autograd); GPU tensors only, like every other op of this package
+      relu=True                                  ... with the ReLU that follows it in the same kernels (gne_forward / gne_backward)
+      relu=True, residual=r                      ... and relu(r + .) on top: the tail of a residual block, one autograd node
   FusedGroupNorm                                 nn.GroupNorm with `forward` on that op; whatever the op does not take goes to nn.GroupNorm.forward
+      .forward_relu(input, residual=None)        the two fused forms; otherwise relu_(nn.GroupNorm.forward(input)) and relu(residual + .)
   convert(module)                                turn every nn.GroupNorm of a module tree into a FusedGroupNorm, in place
+  residual_block_forward(block, x)               the forward of a conv1 / norm1 / conv2 / norm2 / downsample block on forward_relu
+  fuse_sequential_relu(module)                   GroupNorm directly followed by nn.ReLU in an nn.Sequential -> one FusedGroupNormReLU + nn.Identity
 
-`GPSGS_ACCELERATE=groupnorm` makes the reference's extractor classes call convert() on themselves (accelerate.py)."""
+`GPSGS_ACCELERATE=groupnorm` makes the reference's extractor classes call convert() on themselves, `GPSGS_ACCELERATE=resblock` also rebinds the
+residual block's forward and fuses the stem's ReLU (accelerate.py)."""
 import ctypes as C
 
 import torch
@@ -83,11 +89,86 @@ class _GroupNorm(torch.autograd.Function):
         return (dx.view(shape) if need_x else None, None, dgamma.to(wdt) if need_w else None, dbeta.to(bdt) if need_b else None, None)
 
 
-def group_norm(x, num_groups, weight, bias, eps=1e-5):
+class _GroupNormEpilogue(torch.autograd.Function):
+    """relu(group_norm(x)) or, with a residual, relu(residual + relu(group_norm(x))): one node.  Saved for the backward: x, mean, rstd, weight, bias
+    (the sign of the normalised value is recomputed from them) and, in the residual form only, the output (its sign masks the incoming gradient; the
+    layer that consumes the output keeps it alive anyway)."""
+
+    @staticmethod
+    def forward(ctx, x, num_groups, weight, bias, eps, residual):
+        lib = _capi.lib()
+        if not x.is_cuda:
+            raise RuntimeError("gps_gaussian_amd: group_norm input must live on a GPU (no CPU fallback)")
+        if x.dtype not in _DTYPES:
+            raise RuntimeError("gps_gaussian_amd: group_norm takes fp32 or fp16 input, not %s" % x.dtype)
+        if x.dim() < 2 or weight is None or bias is None:
+            raise RuntimeError("gps_gaussian_amd: group_norm needs an [N, C, ...] input, a weight and a bias")
+        N, Cn, G = x.shape[0], x.shape[1], int(num_groups)
+        if G <= 0 or Cn % G != 0 or weight.numel() != Cn or bias.numel() != Cn:
+            raise RuntimeError("gps_gaussian_amd: group_norm: %d channels, %d groups, %d weights, %d biases" % (Cn, G, weight.numel(), bias.numel()))
+        dev = x.device
+        if residual is not None and not (torch.is_tensor(residual) and residual.is_cuda and residual.device == dev
+                                         and residual.dtype == torch.float32 and residual.shape == x.shape):
+            raise RuntimeError("gps_gaussian_amd: group_norm: residual must be an fp32 GPU tensor of the input's shape %s" % (tuple(x.shape),))
+        xc = _aligned(x.detach())
+        rc_ = _aligned(residual.detach()) if residual is not None else None
+        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+        HW = xc.numel() // (N * Cn) if N * Cn else 0
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        mean = torch.empty((N, G), dtype=torch.float32, device=dev)
+        rstd = torch.empty((N, G), dtype=torch.float32, device=dev)
+        scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.gne_forward(_ptr(xc), _DTYPES[x.dtype], _ptr(w), _ptr(b), _ptr(rc_), N, Cn, G, HW, float(eps), _ptr(out), _ptr(mean), _ptr(rstd),
+                                 _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _capi.check(rc, "gne_forward")
+        if any(ctx.needs_input_grad):
+            if residual is None:
+                ctx.save_for_backward(xc, mean, rstd, w, b)      # never the output: its sign is the sign of y, recomputed
+            else:
+                ctx.save_for_backward(xc, mean, rstd, w, b, out)
+            ctx.dims = (N, Cn, G, HW, x.shape, weight.dtype, bias.dtype)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _capi.lib()
+        xc, mean, rstd, w, b = ctx.saved_tensors[:5]
+        out = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        N, Cn, G, HW, shape, wdt, bdt = ctx.dims
+        dev = xc.device
+        need_x, _, need_w, need_b, _, need_r = ctx.needs_input_grad
+        need_r = need_r and out is not None
+        dc = _aligned(dout.to(torch.float32))
+        dx = torch.empty_like(xc) if need_x else None
+        dres = torch.empty(shape, dtype=torch.float32, device=dev) if need_r else None
+        dgamma = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
+        dbeta = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
+        scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.gne_backward(_ptr(xc), _DTYPES[xc.dtype], _ptr(dc), _ptr(out), _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), N, Cn, G, HW, _ptr(dx),
+                                  _ptr(dres), _ptr(dgamma), _ptr(dbeta), _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _capi.check(rc, "gne_backward")
+        if N * Cn * HW == 0 and dgamma is not None:
+            dgamma.zero_(), dbeta.zero_()
+        return (dx.view(shape) if need_x else None, None, dgamma.to(wdt) if need_w else None, dbeta.to(bdt) if need_b else None, None, dres)
+
+
+def group_norm(x, num_groups, weight, bias, eps=1e-5, *, relu=False, residual=None):
     """torch.nn.functional.group_norm(x, num_groups, weight, bias, eps) for a GPU tensor x [N, C, *] in fp32 or fp16; the result is fp32 (what
     autocast's fp32 policy for group_norm gives for an fp16 input), x.grad comes back in x's dtype.  The backward reads x, not the output, so the
-    output may be modified in place."""
-    return _GroupNorm.apply(x, num_groups, weight, bias, eps)
+    output may be modified in place.
+
+    relu=True returns relu(y) instead, and relu=True with residual=r (an fp32 GPU tensor of x's shape) returns relu(r + relu(y)), each from the same
+    two kernels and as ONE autograd node, with the bits of `relu_` / `+` / `relu` applied to the plain result; gradients flow to x, weight, bias
+    and r.  A residual without relu=True, or one of another device, dtype or shape, is a RuntimeError."""
+    if residual is not None and not relu:
+        raise RuntimeError("gps_gaussian_amd: group_norm: residual= needs relu=True (the fused form is relu(residual + relu(y)))")
+    if not relu:
+        return _GroupNorm.apply(x, num_groups, weight, bias, eps)
+    return _GroupNormEpilogue.apply(x, num_groups, weight, bias, eps, residual)
 
 
 def _autocast_dtype():
@@ -124,6 +205,27 @@ class FusedGroupNorm(nn.GroupNorm):
         accelerate.calls["groupnorm"] += 1
         return _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps)
 
+    def forward_relu(self, input, residual=None):
+        """relu_(self(input)), and with a residual relu(residual + that): in the fused kernels where forward() would use them, otherwise with
+        exactly those ops on nn.GroupNorm.forward (the reference's own: same bits), counted as a pass-through."""
+        if not _fusable(self, input):
+            accelerate.calls["groupnorm_passthrough"] += 1
+            y = torch.relu_(nn.GroupNorm.forward(self, input))
+            return y if residual is None else torch.relu(residual + y)
+        accelerate.calls["groupnorm"] += 1
+        if residual is None:
+            return _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, None)
+        if not (residual.is_cuda and residual.device == input.device and residual.dtype == torch.float32 and residual.shape == input.shape):
+            return torch.relu(residual + _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, None))   # broadcast, fp64, ...
+        return _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, residual)
+
+
+class FusedGroupNormReLU(FusedGroupNorm):
+    """A FusedGroupNorm that applies the ReLU which followed it in its nn.Sequential (fuse_sequential_relu put an nn.Identity there)."""
+
+    def forward(self, input):
+        return self.forward_relu(input)
+
 
 def convert(module):
     """Make every nn.GroupNorm in `module`'s tree (the module itself included) a FusedGroupNorm, in place: the instance keeps its parameters, buffers,
@@ -135,3 +237,54 @@ def convert(module):
             m.__class__ = FusedGroupNorm
             n += 1
     return n
+
+
+def fuse_sequential_relu(module):
+    """In every nn.Sequential of `module`'s tree (the module itself included): a GroupNorm (plain or FusedGroupNorm) DIRECTLY followed by an nn.ReLU
+    becomes a FusedGroupNormReLU and the ReLU's slot an nn.Identity -- same indices, same state_dict keys, same parameters.  A norm that sits in more
+    than one place of the tree is left alone (its other users do not want the ReLU).  Idempotent; returns the number fused."""
+    uses = {}
+    for m in module.modules():
+        for c in m.children():
+            uses[id(c)] = uses.get(id(c), 0) + 1
+    n = 0
+    for seq in module.modules():
+        if not isinstance(seq, nn.Sequential):
+            continue
+        for i in range(len(seq) - 1):
+            if type(seq[i]) in (nn.GroupNorm, FusedGroupNorm) and type(seq[i + 1]) is nn.ReLU and uses.get(id(seq[i]), 0) == 1:
+                seq[i].__class__ = FusedGroupNormReLU
+                seq[i + 1] = nn.Identity()
+                n += 1
+    return n
+
+
+def _own_forward(block):
+    """The forward the block's class defines -- the reference's own where accelerate has rebound it to residual_block_forward."""
+    for holder, name, orig in list(accelerate._originals.values()):
+        if name == "forward" and isinstance(holder, type) and isinstance(block, holder):
+            return orig
+    return type(block).forward
+
+
+def _norm_relu(norm, y, residual=None):
+    if isinstance(norm, FusedGroupNorm):
+        return norm.forward_relu(y, residual)
+    y = torch.relu_(norm(y))
+    return y if residual is None else torch.relu(residual + y)
+
+
+def residual_block_forward(block, x):
+    """The forward of a residual block with the members conv1, norm1, conv2, norm2, downsample (None or a module):
+        y = relu_(norm1(conv1(x)));  y = relu_(norm2(conv2(y)));  relu(downsample(x) + y)
+    with each norm + ReLU, and the add + ReLU behind the second, in one fused op (FusedGroupNorm.forward_relu).  Blocks whose norm1 / norm2 are not
+    GroupNorm layers (batch, instance, none) run their class's own forward.  Counted in accelerate.calls["resblock"] / ["resblock_passthrough"]."""
+    n1, n2 = getattr(block, "norm1", None), getattr(block, "norm2", None)
+    if not (isinstance(n1, nn.GroupNorm) and isinstance(n2, nn.GroupNorm)):
+        accelerate.calls["resblock_passthrough"] += 1
+        return _own_forward(block)(block, x)
+    accelerate.calls["resblock"] += 1
+    y = _norm_relu(n1, block.conv1(x))
+    y = block.conv2(y)
+    r = x if block.downsample is None else block.downsample(x)
+    return _norm_relu(n2, y, r)

@@ -34,6 +34,9 @@
  *   gn_forward / gn_backward (+ gn_chunk_elems, gn_scratch_bytes)
  *       torch.nn.GroupNorm as the reference's feature extractor builds it (core/extractor.py:17-20, :68: groups of 8 channels x the whole plane)
  *       and its autograd backward: ATen's one-workgroup-per-row moments kernels, the largest single item of a view's GPU time.
+ *   gne_forward / gne_backward
+ *       the same layers with what the reference runs right after them folded in: `relu_(norm(conv(x)))` (core/extractor.py:51-52, :54-55, the
+ *       Conv -> GroupNorm -> ReLU stem at :66-70) and the block's `relu(x + y)` (:60) -- ATen's clamp, add and copy kernels on the largest activations.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -59,7 +62,8 @@ extern "C" {
                                still 4 after the contribution statistics: GsrContrib, gsr_workspace_bytes_contrib, gsr_forward_contrib (additive)
                                still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive)
                                still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive)
-                               still 4 after GroupNorm: gn_chunk_elems, gn_scratch_bytes, gn_forward, gn_backward (additive) */
+                               still 4 after GroupNorm: gn_chunk_elems, gn_scratch_bytes, gn_forward, gn_backward (additive)
+                               still 4 after the GroupNorm epilogues: gne_forward, gne_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -602,6 +606,19 @@ int gn_forward(const void *x, int dtype, const float *gamma, const float *beta, 
                float *rstd, void *scratch, void *stream);
 int gn_backward(const void *x, int dtype, const float *dy, const float *gamma, const float *mean, const float *rstd, int N, int C, int G, int HW,
                 void *dx, float *dgamma, float *dbeta, void *scratch, void *stream);
+/* The same two passes with an epilogue fused in (no further kernel, no further pass over y):
+ *     residual == NULL:  out = relu(y)                    residual != NULL:  out = relu(residual + relu(y)),  residual fp32 [N,C,HW]
+ * out is bit for bit what relu_ / add / relu applied to gn_forward's y give.  gne_backward takes dout, the gradient of out:
+ *     g = dout where out > 0, else +0 (residual form only; `out` non-NULL selects it and must be gne_forward's output)      dres = g
+ *     dy = g where y > 0, else +0 -- the sign of y is recomputed from x, mean, rstd, gamma, beta with the forward's arithmetic, so no normalised
+ *     activation has to be kept; the plain form needs x, mean, rstd only
+ * and then does what gn_backward does with dy, in the same two kernels: dx, dgamma, dbeta are bit for bit gn_backward's on that dy.  dres (fp32
+ * [N,C,HW]; NULL = not wanted) needs `out`.  Scratch, alignment (also of residual, out, dout, dres), the empty-tensor rule and the refusals are
+ * gn_forward's / gn_backward's; in addition GPSGS_E_INVALID for dres without out, and beta is a required pointer of the backward too. */
+int gne_forward(const void *x, int dtype, const float *gamma, const float *beta, const float *residual, int N, int C, int G, int HW, float eps,
+                float *out, float *mean, float *rstd, void *scratch, void *stream);
+int gne_backward(const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
+                 const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }
