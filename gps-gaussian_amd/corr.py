@@ -34,6 +34,13 @@ def _args(volume, coords):
     return N, H1, W1, W2, c
 
 
+def _radius(radius):
+    r = int(radius)
+    if r != radius or r < 0:
+        raise RuntimeError("radius must be a non-negative integer, got %r" % (radius,))
+    return r
+
+
 _lib = None
 
 
@@ -57,10 +64,11 @@ def forward(volume, coords, radius):
         if acc is not None and acc._armed:
             acc.late_apply()
     N, H1, W1, W2, c = _args(volume, coords)
+    radius = _radius(radius)
     v = volume if volume.is_contiguous() else volume.contiguous()
     out = torch.empty((N, 2 * radius + 1, H1, W1), dtype=v.dtype, device=v.device)
     # plain integers: ctypes converts them to the void* / int arguments declared in _capi (boxing them in c_void_p costs ~1 us each)
-    _call(lib.cs_forward, "cs_forward", v.device, v.data_ptr(), c.data_ptr(), out.data_ptr(), N, H1, W1, W2, int(radius), _DT[v.dtype])
+    _call(lib.cs_forward, "cs_forward", v.device, v.data_ptr(), c.data_ptr(), out.data_ptr(), N, H1, W1, W2, radius, _DT[v.dtype])
     return (out,)
 
 
@@ -69,13 +77,14 @@ def backward(volume, coords, grad_output, radius):
     lib = _lib or _capi.lib()
     _lib = lib
     N, H1, W1, W2, c = _args(volume, coords)
+    radius = _radius(radius)
     g = grad_output
+    if tuple(g.shape) != (N, 2 * radius + 1, H1, W1) or g.device != volume.device:
+        raise RuntimeError("grad_output must be [N,2r+1,H1,W1] on the volume's device, got %s" % (tuple(g.shape),))
     if g.dtype is not volume.dtype or not g.is_contiguous():
         g = g.to(dtype=volume.dtype).contiguous()
-    if tuple(g.shape) != (N, 2 * radius + 1, H1, W1):
-        raise RuntimeError("grad_output must be [N,2r+1,H1,W1]")
     gv = torch.empty((N, H1, W1, W2), dtype=volume.dtype, device=volume.device)
-    _call(lib.cs_backward, "cs_backward", volume.device, c.data_ptr(), g.data_ptr(), gv.data_ptr(), N, H1, W1, W2, int(radius), _DT[volume.dtype])
+    _call(lib.cs_backward, "cs_backward", volume.device, c.data_ptr(), g.data_ptr(), gv.data_ptr(), N, H1, W1, W2, radius, _DT[volume.dtype])
     return (gv,)
 
 
@@ -85,6 +94,8 @@ def _stream(dev):
 
 
 def _ptr_array(tensors):
+    if len(tensors) > 4:
+        raise RuntimeError("at most 4 pyramid levels, got %d" % len(tensors))
     return (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) if t is not None else None for t in list(tensors) + [None] * (4 - len(tensors))])
 
 
@@ -141,6 +152,9 @@ class _LookupPyramid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, coords, radius, *pyr):
         lib = _capi.lib()
+        if not 1 <= len(pyr) <= 4:
+            raise RuntimeError("1..4 pyramid levels, got %d" % len(pyr))
+        radius = _radius(radius)
         v0 = pyr[0]
         N, H1, W1, W2, c = _args(v0, coords)
         for l, v in enumerate(pyr):
@@ -149,10 +163,10 @@ class _LookupPyramid(torch.autograd.Function):
         out = torch.empty((N, len(pyr) * (2 * radius + 1), H1, W1), dtype=v0.dtype, device=v0.device)
         with torch.cuda.device(v0.device):
             rc = lib.cs_lookup_forward(_ptr_array(pyr), C.c_void_p(c.data_ptr()), C.c_void_p(out.data_ptr()), N, H1, W1, W2, len(pyr),
-                                       int(radius), _DT[v0.dtype], _stream(v0.device))
+                                       radius, _DT[v0.dtype], _stream(v0.device))
         _capi.check(rc, "cs_lookup_forward")
         ctx.save_for_backward(c)
-        ctx.meta = (N, H1, W1, W2, len(pyr), int(radius), v0.dtype)
+        ctx.meta = (N, H1, W1, W2, len(pyr), radius, v0.dtype)
         return out
 
     @staticmethod

@@ -509,12 +509,24 @@ extern "C" int cv_build_backward(const void *fmap1, const void *fmap2, const voi
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
 
+// N * H1 * W1 (non-negative ints) where an int holds it -- the lookup kernels index the (n, y, x) rows in int -- else -1; no intermediate product overflows
+static long long lookup_rows(int N, int H1, int W1) {
+    const long long a = (long long)N * H1;  // < 2^62
+    if (a == 0 || W1 == 0) return 0;
+    if (a > 0x7fffffffLL) return -1;
+    const long long t = a * W1;  // < 2^62
+    return t > 0x7fffffffLL ? -1 : t;
+}
+
+// 2 * radius + 1 must fit an int
+static bool lookup_radius_ok(int radius) { return radius >= 0 && radius <= 0x3fffffff; }
+
 extern "C" int cs_lookup_forward(const void *const *pyramid, const float *coords, void *out, int N, int H1, int W1, int W2, int levels, int radius,
                                  int dtype, void *stream) {
-    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || radius < 0 || !pyramid) return GPSGS_E_INVALID;
-    const long long total = (long long)N * H1 * W1;
+    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || !lookup_radius_ok(radius) || !pyramid) return GPSGS_E_INVALID;
+    const long long total = lookup_rows(N, H1, W1);
     if (total == 0) return GPSGS_OK;
-    if (!coords || !out || total > 0x7fffffffLL) return GPSGS_E_INVALID;
+    if (!coords || !out || total < 0) return GPSGS_E_INVALID;
     PyrConstPtrs pp;
     for (int l = 0; l < 4; l++) {
         pp.p[l] = l < levels ? pyramid[l] : nullptr;
@@ -531,17 +543,20 @@ extern "C" int cs_lookup_forward(const void *const *pyramid, const float *coords
 
 extern "C" int cs_lookup_backward(const float *coords, const void *grad_out, void *const *grad_pyramid, int N, int H1, int W1, int W2, int levels,
                                   int radius, int dtype, void *stream) {
-    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || radius < 0 || !grad_pyramid) return GPSGS_E_INVALID;
-    const size_t total = (size_t)N * H1 * W1 * W2;
-    if (total == 0) return GPSGS_OK;
-    if (!coords || !grad_out) return GPSGS_E_INVALID;
+    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || !lookup_radius_ok(radius) || !grad_pyramid) return GPSGS_E_INVALID;
+    const long long rows = lookup_rows(N, H1, W1);
+    if (rows == 0 || W2 == 0) return GPSGS_OK;
+    if (!coords || !grad_out || rows < 0) return GPSGS_E_INVALID;
+    const size_t total = (size_t)rows * W2;  // < 2^62
+    const size_t blocks = (total + 255) / 256;  // one thread per level-0 element in blocks of 256
+    if (blocks > 0x7fffffffULL) return GPSGS_E_INVALID;  // more than a grid's x holds: refused, not truncated
     PyrPtrs pp;
     for (int l = 0; l < 4; l++) {
         pp.p[l] = l < levels ? grad_pyramid[l] : nullptr;
         if (l < levels && !pp.p[l] && (W2 >> l) > 0) return GPSGS_E_INVALID;
     }
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((total + 255) / 256));
+    const dim3 grid((unsigned)blocks);
     if (dtype == 0)
         hipLaunchKernelGGL(k_lookup_bwd<float>, grid, dim3(256), 0, s, coords, (const float *)grad_out, pp, total, H1, W1, W2, levels, radius);
     else

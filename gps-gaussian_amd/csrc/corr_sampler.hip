@@ -118,12 +118,24 @@ __global__ __launch_bounds__(256) void k_cs_bwd4(const float *__restrict__ coord
 
 }  // namespace
 
+// N * H1 * W1 (non-negative ints) where an int holds it -- the kernels index the (n, y, x) rows in int -- else -1; no intermediate product overflows
+static long long cs_rows(int N, int H1, int W1) {
+    const long long a = (long long)N * H1;  // < 2^62
+    if (a == 0 || W1 == 0) return 0;
+    if (a > 0x7fffffffLL) return -1;
+    const long long t = a * W1;  // < 2^62
+    return t > 0x7fffffffLL ? -1 : t;
+}
+
+// 2 * radius + 1 must fit an int
+static bool cs_radius_ok(int radius) { return radius >= 0 && radius <= 0x3fffffff; }
+
 extern "C" int cs_forward(const void *volume, const float *coords, void *out, int N, int H1, int W1, int W2, int radius, int dtype,
                           void *stream) {
-    if (N < 0 || H1 < 0 || W1 < 0 || W2 < 0 || radius < 0 || (dtype != 0 && dtype != 1)) return GPSGS_E_INVALID;
-    const long long total = (long long)N * H1 * W1;
+    if (N < 0 || H1 < 0 || W1 < 0 || W2 < 0 || !cs_radius_ok(radius) || (dtype != 0 && dtype != 1)) return GPSGS_E_INVALID;
+    const long long total = cs_rows(N, H1, W1);
     if (total == 0) return GPSGS_OK;
-    if (!volume || !coords || !out || total > 0x7fffffffLL) return GPSGS_E_INVALID;
+    if (!volume || !coords || !out || total < 0) return GPSGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == 0)
@@ -135,21 +147,26 @@ extern "C" int cs_forward(const void *volume, const float *coords, void *out, in
 
 extern "C" int cs_backward(const float *coords, const void *grad_out, void *grad_volume, int N, int H1, int W1, int W2, int radius,
                            int dtype, void *stream) {
-    if (N < 0 || H1 < 0 || W1 < 0 || W2 < 0 || radius < 0 || (dtype != 0 && dtype != 1)) return GPSGS_E_INVALID;
-    const size_t total = (size_t)N * H1 * W1 * W2;
-    if (total == 0) return GPSGS_OK;
-    if (!coords || !grad_out || !grad_volume) return GPSGS_E_INVALID;
+    if (N < 0 || H1 < 0 || W1 < 0 || W2 < 0 || !cs_radius_ok(radius) || (dtype != 0 && dtype != 1)) return GPSGS_E_INVALID;
+    const long long rows = cs_rows(N, H1, W1);
+    if (rows == 0 || W2 == 0) return GPSGS_OK;
+    if (!coords || !grad_out || !grad_volume || rows < 0) return GPSGS_E_INVALID;
+    const size_t total = (size_t)rows * W2;  // < 2^62
     hipStream_t s = (hipStream_t)stream;
-    if ((W2 & 3) == 0 && ((uintptr_t)grad_volume & 15) == 0) {
-        const size_t total4 = total / 4;
-        const dim3 grid4((unsigned)((total4 + 255) / 256));
+    // one thread per quad (k_cs_bwd4) or per element (k_cs_bwd) in blocks of 256: a block count a grid's x cannot hold is refused, not truncated
+    const bool quads = (W2 & 3) == 0 && ((uintptr_t)grad_volume & 15) == 0;
+    const size_t threads = quads ? total / 4 : total;
+    const size_t blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffULL) return GPSGS_E_INVALID;
+    if (quads) {
+        const dim3 grid4((unsigned)blocks);
         if (dtype == 0)
-            hipLaunchKernelGGL(k_cs_bwd4<float>, grid4, dim3(256), 0, s, coords, (const float *)grad_out, (float *)grad_volume, total4, H1, W1, W2, radius);
+            hipLaunchKernelGGL(k_cs_bwd4<float>, grid4, dim3(256), 0, s, coords, (const float *)grad_out, (float *)grad_volume, threads, H1, W1, W2, radius);
         else
-            hipLaunchKernelGGL(k_cs_bwd4<__half>, grid4, dim3(256), 0, s, coords, (const __half *)grad_out, (__half *)grad_volume, total4, H1, W1, W2, radius);
+            hipLaunchKernelGGL(k_cs_bwd4<__half>, grid4, dim3(256), 0, s, coords, (const __half *)grad_out, (__half *)grad_volume, threads, H1, W1, W2, radius);
         return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
     }
-    const dim3 grid((unsigned)((total + 255) / 256));
+    const dim3 grid((unsigned)blocks);
     if (dtype == 0)
         hipLaunchKernelGGL(k_cs_bwd<float>, grid, dim3(256), 0, s, coords, (const float *)grad_out, (float *)grad_volume, total, H1, W1, W2, radius);
     else

@@ -550,7 +550,17 @@ int up_flow2render_dev(int B, int S, int res, const float *flow_l, const float *
 
 /* ---- 1-D correlation sampler ----------------------------------------------------------------------------------
  * volume[N,H1,W1,W2], coords[N,H1,W1] fp32 (channel 0 of the reference's [N,1,H1,W1]), out[N,2r+1,H1,W1].
- * dtype: 0 = fp32, 1 = fp16 (volume / out / grads; coords always fp32). */
+ * dtype: 0 = fp32, 1 = fp16 (volume / out / grads; coords always fp32).
+ * out[n,k,y,x] = sum_j volume[n,y,x,j] * max(0, 1 - |coords[n,y,x] - radius + k - j|): linear interpolation, zero outside the row; any radius >= 0,
+ * the window may be wider than the row.  The backward writes every element of grad_volume (zero fill fused; no gradient to coords).
+ * Coordinate range: finite, |c| + radius + 1 < 2^31.  Outside it (NaN, infinities, farther away) no access leaves the tensors, but the values
+ * written are unspecified.
+ * Empty tensors (N*H1*W1 == 0, for the backward also W2 == 0) return GPSGS_OK, launch nothing and may come with NULL pointers.  GPSGS_E_INVALID:
+ * a negative size, a dtype other than 0 / 1, a NULL pointer of a non-empty tensor, radius < 0 or 2*radius + 1 > INT_MAX, N*H1*W1 > INT_MAX
+ * (forward and backward: the kernels index the rows in int), and a backward whose block count exceeds 0x7fffffff -- one thread per four elements
+ * of grad_volume where W2 % 4 == 0 and grad_volume is 16-byte aligned, else one per element, in blocks of 256.  cs_lookup_forward /
+ * cs_lookup_backward below refuse the same (their backward runs one thread per level-0 element), levels outside 1..4, and a NULL level pointer
+ * except where W2 >> l == 0. */
 int cs_forward(const void *volume, const float *coords, void *out, int N, int H1, int W1, int W2, int radius,
                int dtype, void *stream);
 int cs_backward(const float *coords, const void *grad_out, void *grad_volume, int N, int H1, int W1, int W2,
