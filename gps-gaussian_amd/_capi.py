@@ -17,6 +17,8 @@ SYMBOLS = (
 GN_SYMBOLS = ("gn_chunk_elems", "gn_scratch_bytes", "gn_forward", "gn_backward")
 # GroupNorm with the ReLU / residual add + ReLU epilogue fused in (the same section; tests/test_capi_groupnorm_epilogue.py)
 GNE_SYMBOLS = ("gne_forward", "gne_backward")
+# Stem convolution (the header's last section; tests/test_capi_stemconv.py)
+SC_SYMBOLS = ("sc_supported", "sc_tile", "sc_scratch_bytes", "sc_forward", "sc_backward")
 
 GPSGS_OK, GPSGS_E_INVALID, GPSGS_E_WORKSPACE, GPSGS_E_LAUNCH, GPSGS_E_NO_DEVICE, GPSGS_E_INTERNAL = 0, -1, -2, -3, -4, -5
 _ERR = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failed", -4: "no HIP device",
@@ -233,6 +235,16 @@ def lib():
     l.gne_forward.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     l.gne_backward.restype = i32
     l.gne_backward.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    l.sc_supported.restype = i32
+    l.sc_supported.argtypes = [i32, i32, i32, i32, i32]
+    l.sc_tile.restype = i32
+    l.sc_tile.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+    l.sc_scratch_bytes.restype = sz
+    l.sc_scratch_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32]
+    l.sc_forward.restype = i32
+    l.sc_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
+    l.sc_backward.restype = i32
+    l.sc_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     if l.gpsgs_abi_version() != 4:
         raise ImportError("gps_gaussian_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = l

@@ -31,6 +31,12 @@ with each `relu_(norm(conv(.)))` and the closing `relu(x + y)` inside the GroupN
 `groupnorm.fuse_sequential_relu(self)`, which folds the stem's Conv -> GroupNorm -> ReLU the same way.  One wrapper per constructor serves both
 names (`_originals` is keyed by attribute); with `groupnorm` alone exactly the two constructors are wrapped and every forward body is the reference's.
 
+A fourth, `stemconv` (GPSGS_ACCELERATE=stemconv; its own tuple OPT_IN_CONV, never implied by "all" or by the names above), makes the wrapped
+`UnetExtractor.__init__` run `stemconv.convert(self)`: the full-resolution `Conv2d(3 | 1, 32, 5, stride 2, padding 2)` that opens each encoder
+(`in_ds[0]`, core/extractor.py:66-70) becomes a `FusedStemConv2d` on the direct-convolution kernels of csrc/stem_conv.hip.  The wrapper is the one
+`groupnorm` / `resblock` use and does only what was asked: `stemconv` alone leaves every norm an `nn.GroupNorm` (and ResidualBlock, which has no such
+layer, unwrapped); `groupnorm` or `resblock` alone leave `in_ds[0]` a plain `nn.Conv2d`.
+
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
 import importlib.abc
@@ -42,16 +48,20 @@ import threading
 FEATURES = ("pack", "loss", "corr", "upsample", "unproject")
 OPT_IN = ("splat", "groupnorm")   # accepted by name only, never implied by "all"
 OPT_IN_FUSED = ("resblock",)      # likewise by name only; implies the groupnorm conversion and replaces ResidualBlock.forward (see above)
+OPT_IN_CONV = ("stemconv",)       # likewise by name only: the encoders' stem convolutions (see above)
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
-calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED}
+calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV}
 # calls that went THROUGH a replacement but were handed on to the reference's own function (a configuration the fused kernel does not implement):
 # counted, so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
 calls["loss_passthrough"] = 0
 calls["unproject_passthrough"] = 0
 calls["groupnorm_passthrough"] = 0   # FusedGroupNorm forwards handed to nn.GroupNorm.forward (CPU, channels-last, bf16, ...: groupnorm.py)
 calls["resblock_passthrough"] = 0    # residual blocks without GroupNorm layers (norm_fn batch / instance / none): the reference's own forward
+calls["stemconv_passthrough"] = 0    # FusedStemConv2d forwards handed to nn.Conv2d.forward (CPU, channels-last, bf16 autocast, ...: stemconv.py)
+_convert_norms = False   # set while `groupnorm` or `resblock` is requested: the constructor wrappers then run groupnorm.convert
+_convert_convs = False   # set while `stemconv` is requested: the UnetExtractor wrapper then runs stemconv.convert
 _fuse_relu = False       # set while `resblock` is requested: the constructor wrappers then also run groupnorm.fuse_sequential_relu
 _installed = {}          # "module.attr" -> feature
 _originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), and the two pass-through cases below
@@ -71,7 +81,7 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN + OPT_IN_FUSED
+    known = FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
@@ -134,13 +144,18 @@ def _depth2pc(depth, extrinsic, intrinsic):
 
 
 def _converting_init(key):
-    """core/extractor.py:7, :64 -- the reference's own constructor (from _originals), then this package's GroupNorm layers in place of nn.GroupNorm."""
+    """core/extractor.py:7, :64 -- the reference's own constructor (from _originals), then whatever was asked for: this package's GroupNorm layers in
+    place of nn.GroupNorm (`groupnorm`, `resblock`), the stem's ReLU folded into its norm (`resblock`), the stem convolution (`stemconv`)."""
     def __init__(self, *args, **kwargs):
         _originals[key][2](self, *args, **kwargs)
-        from . import groupnorm
-        groupnorm.convert(self)
-        if _fuse_relu:
-            groupnorm.fuse_sequential_relu(self)
+        if _convert_norms:
+            from . import groupnorm
+            groupnorm.convert(self)
+            if _fuse_relu:
+                groupnorm.fuse_sequential_relu(self)
+        if _convert_convs:
+            from . import stemconv
+            stemconv.convert(self)
     return __init__
 
 
@@ -189,6 +204,8 @@ def _table(features):
     if "groupnorm" in t or "resblock" in t:   # one wrapper per constructor, whichever of the two names asks (both: filed under groupnorm)
         t["groupnorm" if "groupnorm" in t else "resblock"] += [("core.extractor", "ResidualBlock.__init__", _resblock_init),
                                                                 ("core.extractor", "UnetExtractor.__init__", _unet_init)]
+    elif "stemconv" in t:                     # the stem convolution alone: only the class that has one
+        t["stemconv"].append(("core.extractor", "UnetExtractor.__init__", _unet_init))
     if "resblock" in t:
         t["resblock"].append(("core.extractor", "ResidualBlock.forward", _resblock_forward))
     return t
@@ -208,13 +225,15 @@ def _loaded(name):
 def apply(features=None):
     """Rebind whatever can be rebound NOW (idempotent; called after every reference module finishes loading).  Returns the number of new
     bindings made."""
-    global _fuse_relu
+    global _fuse_relu, _convert_norms, _convert_convs
     feats = requested() if features is None else tuple(features)
     if not feats:
         return 0
     made = 0
     with _lock:
         _fuse_relu = _fuse_relu or "resblock" in feats
+        _convert_norms = _convert_norms or "groupnorm" in feats or "resblock" in feats
+        _convert_convs = _convert_convs or "stemconv" in feats
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -251,7 +270,7 @@ def apply(features=None):
 
 def restore():
     """Undo every rebinding (tests)."""
-    global _fuse_relu
+    global _fuse_relu, _convert_norms, _convert_convs
     with _lock:
         for key, (holder, name, orig) in list(_originals.items()):
             repl = holder.__dict__.get(name) if isinstance(holder, type) else getattr(holder, name, None)
@@ -263,7 +282,7 @@ def restore():
                         d[name] = orig
         _originals.clear()
         _installed.clear()
-        _fuse_relu = False
+        _fuse_relu = _convert_norms = _convert_convs = False
         for k in calls:
             calls[k] = 0
 

@@ -37,6 +37,10 @@
  *   gne_forward / gne_backward
  *       the same layers with what the reference runs right after them folded in: `relu_(norm(conv(x)))` (core/extractor.py:51-52, :54-55, the
  *       Conv -> GroupNorm -> ReLU stem at :66-70) and the block's `relu(x + y)` (:60) -- ATen's clamp, add and copy kernels on the largest activations.
+ *   sc_forward / sc_backward (+ sc_supported, sc_tile, sc_scratch_bytes)
+ *       the two full-resolution stem convolutions, torch.nn.Conv2d(3 | 1, 32, 5, stride 2, padding 2) of core/extractor.py:66-70 (the depth
+ *       encoder's through lib/gs_parm_network.py:14) and their autograd backward: the library's implicit-GEMM kernels with a K step of 4 and the
+ *       NCHW <-> NHWC transposes around them.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -63,7 +67,8 @@ extern "C" {
                                still 4 after the absolute screen-space gradient: GsrAbsGrad, gsr_workspace_bytes_absgrad, gsr_backward_absgrad (additive)
                                still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive)
                                still 4 after GroupNorm: gn_chunk_elems, gn_scratch_bytes, gn_forward, gn_backward (additive)
-                               still 4 after the GroupNorm epilogues: gne_forward, gne_backward (additive) */
+                               still 4 after the GroupNorm epilogues: gne_forward, gne_backward (additive)
+                               still 4 after the stem convolution: sc_supported, sc_tile, sc_scratch_bytes, sc_forward, sc_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -629,6 +634,30 @@ int gne_forward(const void *x, int dtype, const float *gamma, const float *beta,
                 float *out, float *mean, float *rstd, void *scratch, void *stream);
 int gne_backward(const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
                  const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch, void *stream);
+
+/* ---- Stem convolution: direct 2-D convolution for layers with almost no input channels, forward and backward ----------------------
+ * y[N,C_out,Ho,Wo] = conv2d(x[N,C_in,H,W], w[C_out,C_in,K,K], bias[C_out], stride, padding = pad), zero padding, dilation 1, groups 1, contiguous
+ * NCHW, Ho = (H + 2 pad - K) / stride + 1 (floored), Wo likewise  (torch.nn.functional.conv2d).
+ * sc_supported: 1 for (C_in, K, stride, pad) in {(1, 5, 2, 2), (3, 5, 2, 2)} with C_out a multiple of 8, 8 <= C_out <= 64; otherwise 0.
+ * sc_tile: the output tile (rows, columns) one workgroup of the forward and of the weight gradient computes.
+ * x, w, bias, dx, dw, dbias are fp32.  y_dtype / dy_dtype: 0 = fp32, 1 = fp16 (what fp16 autocast makes of this layer's output and its gradient);
+ * every sum is fp32, y is rounded once, on store: acc = bias, then fmaf over (ci, ky, kx) in index order.  x, y, dy, dx and scratch must be
+ * 16-byte aligned; rows of any width, also ones that start off a 16-byte boundary, are fine.  H, W, Ho, Wo may be anything >= 1.
+ * sc_backward WRITES dx (NULL = not wanted: that kernel is not launched) and dw / dbias (both or neither; NULL = not wanted).  dw and dbias are
+ * two-stage sums: per tile, then over the tiles in index order (in groups of 64, then the groups) -- no atomics, the same bits on every run.
+ * scratch (needed for dw / dbias only): DEVICE, at least sc_scratch_bytes(...) =
+ *     4 * C_out * (C_in * K * K + 1) * (tiles + ceil(tiles / 64))   bytes,  tiles = N * ceil(Ho / tile_h) * ceil(Wo / tile_w)
+ * and 0 for arguments sc_forward would refuse.
+ * GPSGS_E_INVALID, before any HIP call: a configuration sc_supported refuses, a non-positive N, H or W, a dtype outside {0, 1}, 2^31 elements or
+ * more in x or in y, one of dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, and scratch where dw is wanted) or a
+ * misaligned one. */
+int sc_supported(int C_in, int C_out, int K, int stride, int pad);
+int sc_tile(int *tile_h, int *tile_w);
+size_t sc_scratch_bytes(int N, int C_in, int C_out, int H, int W, int K, int stride, int pad);
+int sc_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int K, int stride, int pad, void *y,
+               int y_dtype, void *stream);
+int sc_backward(const float *x, const float *w, const void *dy, int dy_dtype, int N, int C_in, int C_out, int H, int W, int K, int stride, int pad,
+                float *dx, float *dw, float *dbias, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }
