@@ -5,21 +5,6 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPSGS_LIB") or os.path.join(_HERE, "lib", "libgpsgs_hip.so")  # GPSGS_LIB: development (another build of the same library)
 
-# every symbol include/gpsgs.h declares (tests/test_capi_symbols.py cross-checks this list against the header)
-SYMBOLS = (
-    "gpsgs_abi_version", "gsr_supported_flags", "gpsgs_build_info", "gpsgs_measure_sclk", "gsr_debug_set_wg_trace", "gsr_workspace_bytes", "gsr_workspace_bytes_forward_only", "gsr_workspace_bytes_ex", "gsr_workspace_bytes_depth_alpha", "gsr_direct_lists_ok", "gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_backward", "gsr_backward_ex", "gsr_camera_grad_scratch_bytes", "gsr_backward_camera", "gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features", "gsr_workspace_bytes_contrib", "gsr_forward_contrib", "gsr_workspace_bytes_absgrad", "gsr_backward_absgrad", "gsr_forward_distort", "gsr_backward_distort", "gsr_copy_header_async", "gsr_read_header",
-    "gsr_export_state", "gsr_mark_visible", "gsr_selftest", "gsr_timing_read", "gsr_debug_count_records", "gsr_pack_scratch_bytes", "gsr_pack_views", "gsr_pack_views_backward", "fl_scratch_bytes",
-    "fl_l1_ssim_forward", "fl_l1_ssim_backward", "up_unproject_forward", "up_unproject_backward", "up_unproject_forward_dev", "up_unproject_backward_dev", "up_splat_scratch_bytes", "up_zsplat", "up_flow2render_dev", "cs_forward", "cs_backward",
-    "cv_build_forward", "cv_build_backward", "cs_lookup_forward", "cs_lookup_backward", "cu_upsample_forward", "cu_upsample_backward", "cu_upsample_scratch_bytes",
-)
-
-# GroupNorm (include/gpsgs.h, its last section; tests/test_capi_groupnorm.py cross-checks this list against the header)
-GN_SYMBOLS = ("gn_chunk_elems", "gn_scratch_bytes", "gn_forward", "gn_backward")
-# GroupNorm with the ReLU / residual add + ReLU epilogue fused in (the same section; tests/test_capi_groupnorm_epilogue.py)
-GNE_SYMBOLS = ("gne_forward", "gne_backward")
-# Stem convolution (the header's last section; tests/test_capi_stemconv.py)
-SC_SYMBOLS = ("sc_supported", "sc_tile", "sc_scratch_bytes", "sc_forward", "sc_backward")
-
 GPSGS_OK, GPSGS_E_INVALID, GPSGS_E_WORKSPACE, GPSGS_E_LAUNCH, GPSGS_E_NO_DEVICE, GPSGS_E_INTERNAL = 0, -1, -2, -3, -4, -5
 _ERR = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failed", -4: "no HIP device",
         -5: "internal self-check failed (debug mode: inconsistent bin lists)"}
@@ -96,6 +81,99 @@ class GsrDistort(C.Structure):
     _fields_ = [("_map", _DistortSlot), ("totals", C.c_void_p), ("reserved", C.c_void_p * 2)]
 
 
+vp, i32, i64, f32, sz, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint
+sp, pp = C.POINTER(GsrStrided), C.POINTER(C.c_void_p)
+_WS = [i32, i32, i32, i64]   # P, W, H, instance capacity
+_FWD = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, sz, i64, u32, vp]
+_FWD_NOTIFY = _FWD + [vp, u32]
+_FWD_EX = _FWD_NOTIFY + [C.POINTER(GsrViewExt)]
+_BWD = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, u32, vp]
+_BWD_EX = _BWD + [C.POINTER(GsrViewExt)]
+_BWD_CAMERA = _BWD_EX + [vp, vp, vp, vp, sz]
+
+# name -> (restype, argtypes) of every symbol include/gpsgs.h declares, in the header's four sections.  lib() sets the prototypes from this table, so
+# a symbol cannot be listed without one (ctypes' default `int` conversion would truncate a 64-bit device pointer silently); tests/test_capi.py
+# cross-checks the first section's names against the header and that every name has its prototype set.
+_GSR = {
+    "gpsgs_abi_version": (i32, []),
+    "gsr_supported_flags": (i32, []),
+    "gpsgs_build_info": (C.c_char_p, []),
+    "gpsgs_measure_sclk": (i32, [vp, C.POINTER(C.c_double), vp]),
+    "gsr_debug_set_wg_trace": (i32, [vp]),
+    "gsr_workspace_bytes": (sz, _WS),
+    "gsr_workspace_bytes_forward_only": (sz, _WS),
+    "gsr_workspace_bytes_ex": (sz, _WS + [u32, i32]),
+    "gsr_workspace_bytes_depth_alpha": (sz, _WS + [u32, i32]),
+    "gsr_direct_lists_ok": (i32, [i32, i32, u32]),
+    "gsr_forward": (i32, _FWD),
+    "gsr_forward_notify": (i32, _FWD_NOTIFY),
+    "gsr_forward_ex": (i32, _FWD_EX),
+    "gsr_backward": (i32, _BWD),
+    "gsr_backward_ex": (i32, _BWD_EX),
+    "gsr_camera_grad_scratch_bytes": (sz, [i32]),
+    "gsr_backward_camera": (i32, _BWD_CAMERA),
+    "gsr_workspace_bytes_features": (sz, _WS + [u32, i32, i32]),
+    "gsr_forward_features": (i32, _FWD_EX + [C.POINTER(GsrFeatures)]),
+    "gsr_backward_features": (i32, _BWD_CAMERA + [C.POINTER(GsrFeatures)]),
+    "gsr_workspace_bytes_contrib": (sz, _WS + [u32, i32]),
+    "gsr_forward_contrib": (i32, _FWD_EX + [C.POINTER(GsrContrib)]),
+    "gsr_workspace_bytes_absgrad": (sz, _WS + [u32]),
+    "gsr_backward_absgrad": (i32, _BWD_CAMERA + [C.POINTER(GsrAbsGrad)]),
+    "gsr_forward_distort": (i32, _FWD_EX + [C.POINTER(GsrDistort)]),
+    "gsr_backward_distort": (i32, _BWD_CAMERA + [C.POINTER(GsrDistort)]),
+    "gsr_copy_header_async": (i32, [vp, vp, vp]),
+    "gsr_read_header": (i32, [vp, C.POINTER(GsrHeader), vp]),
+    "gsr_export_state": (i32, [vp, i32, i32, i32, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gsr_mark_visible": (i32, [i32, vp, vp, vp, vp, vp]),
+    "gsr_selftest": (i32, [vp, vp]),
+    "gsr_timing_read": (i32, [C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "gsr_debug_count_records": (i32, [vp, sz, i32, i32, i32, i64, u32, vp, vp]),
+    "gsr_pack_scratch_bytes": (sz, [i32, i32, i32]),
+    "gsr_pack_views": (i32, [i32, i32, i32, sp, sp, sp, sp, sp, sp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gsr_pack_views_backward": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, pp, pp, pp, pp, pp, vp]),
+    "fl_scratch_bytes": (sz, [i32, i32, i32]),
+    "fl_l1_ssim_forward": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "fl_l1_ssim_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "up_unproject_forward": (i32, [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "up_unproject_backward": (i32, [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
+    "up_unproject_forward_dev": (i32, [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp]),
+    "up_unproject_backward_dev": (i32, [i32, i32, vp, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp]),
+    "up_splat_scratch_bytes": (sz, [i32, i32]),
+    "up_zsplat": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "up_flow2render_dev": (i32, [i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+    "cs_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cs_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cv_build_forward": (i32, [vp, vp, pp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cv_build_backward": (i32, [vp, vp, pp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cs_lookup_forward": (i32, [pp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cs_lookup_backward": (i32, [vp, vp, pp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cu_upsample_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cu_upsample_backward": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cu_upsample_scratch_bytes": (sz, [i32, i32, i32, i32]),
+}
+# GroupNorm (tests/test_capi_groupnorm.py cross-checks these names against the header)
+_GN = {
+    "gn_chunk_elems": (sz, []),
+    "gn_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "gn_forward": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "gn_backward": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+}
+# GroupNorm with the ReLU / residual add + ReLU epilogue fused in (the same section; tests/test_capi_groupnorm_epilogue.py)
+_GNE = {
+    "gne_forward": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "gne_backward": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+}
+# Stem convolution (the header's last section; tests/test_capi_stemconv.py)
+_SC = {
+    "sc_supported": (i32, [i32, i32, i32, i32, i32]),
+    "sc_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "sc_scratch_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "sc_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "sc_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+}
+PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC}
+SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC)
+
 _lib = None
 
 
@@ -109,142 +187,9 @@ def lib():
             "gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gps-gaussian_amd/csrc`). There is no CPU fallback for this path." % LIB_PATH)
     l = C.CDLL(LIB_PATH)
-    vp, i32, i64, f32, sz, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint
-    l.gpsgs_abi_version.restype = i32
-    l.gpsgs_abi_version.argtypes = []
-    l.gsr_supported_flags.restype = i32
-    l.gsr_supported_flags.argtypes = []
-    l.gpsgs_build_info.restype = C.c_char_p
-    l.gpsgs_build_info.argtypes = []
-    l.gsr_debug_set_wg_trace.restype = i32
-    l.gsr_debug_set_wg_trace.argtypes = [vp]
-    l.gpsgs_measure_sclk.restype = i32
-    l.gpsgs_measure_sclk.argtypes = [vp, C.POINTER(C.c_double), vp]
-    l.gsr_workspace_bytes.restype = sz
-    l.gsr_workspace_bytes.argtypes = [i32, i32, i32, i64]
-    l.gsr_workspace_bytes_forward_only.restype = sz
-    l.gsr_workspace_bytes_forward_only.argtypes = [i32, i32, i32, i64]
-    l.gsr_workspace_bytes_ex.restype = sz
-    l.gsr_workspace_bytes_ex.argtypes = [i32, i32, i32, i64, u32, i32]
-    l.gsr_workspace_bytes_depth_alpha.restype = sz
-    l.gsr_workspace_bytes_depth_alpha.argtypes = [i32, i32, i32, i64, u32, i32]
-    l.gsr_direct_lists_ok.restype = i32
-    l.gsr_direct_lists_ok.argtypes = [i32, i32, u32]
-    l.gsr_forward.restype = i32
-    l.gsr_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, sz, i64, u32, vp]
-    l.gsr_forward_notify.restype = i32
-    l.gsr_forward_notify.argtypes = l.gsr_forward.argtypes + [vp, u32]
-    l.gsr_forward_ex.restype = i32
-    l.gsr_forward_ex.argtypes = l.gsr_forward_notify.argtypes + [C.POINTER(GsrViewExt)]
-    l.gsr_backward.restype = i32
-    l.gsr_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                               vp, vp, sz, i64, u32, vp]
-    l.gsr_backward_ex.restype = i32
-    l.gsr_backward_ex.argtypes = l.gsr_backward.argtypes + [C.POINTER(GsrViewExt)]
-    l.gsr_camera_grad_scratch_bytes.restype = sz
-    l.gsr_camera_grad_scratch_bytes.argtypes = [i32]
-    l.gsr_backward_camera.restype = i32
-    l.gsr_backward_camera.argtypes = l.gsr_backward_ex.argtypes + [vp, vp, vp, vp, sz]
-    l.gsr_workspace_bytes_features.restype = sz
-    l.gsr_workspace_bytes_features.argtypes = [i32, i32, i32, i64, u32, i32, i32]
-    l.gsr_forward_features.restype = i32
-    l.gsr_forward_features.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrFeatures)]
-    l.gsr_backward_features.restype = i32
-    l.gsr_backward_features.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrFeatures)]
-    l.gsr_workspace_bytes_contrib.restype = sz
-    l.gsr_workspace_bytes_contrib.argtypes = [i32, i32, i32, i64, u32, i32]
-    l.gsr_forward_contrib.restype = i32
-    l.gsr_forward_contrib.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrContrib)]
-    l.gsr_workspace_bytes_absgrad.restype = sz
-    l.gsr_workspace_bytes_absgrad.argtypes = [i32, i32, i32, i64, u32]
-    l.gsr_backward_absgrad.restype = i32
-    l.gsr_backward_absgrad.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrAbsGrad)]
-    l.gsr_forward_distort.restype = i32
-    l.gsr_forward_distort.argtypes = l.gsr_forward_ex.argtypes + [C.POINTER(GsrDistort)]
-    l.gsr_backward_distort.restype = i32
-    l.gsr_backward_distort.argtypes = l.gsr_backward_camera.argtypes + [C.POINTER(GsrDistort)]
-    l.gsr_copy_header_async.restype = i32
-    l.gsr_copy_header_async.argtypes = [vp, vp, vp]
-    l.gsr_read_header.restype = i32
-    l.gsr_read_header.argtypes = [vp, C.POINTER(GsrHeader), vp]
-    l.gsr_export_state.restype = i32
-    l.gsr_export_state.argtypes = [vp, i32, i32, i32, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    l.gsr_debug_count_records.restype = i32
-    l.gsr_debug_count_records.argtypes = [vp, sz, i32, i32, i32, i64, u32, vp, vp]
-    l.gsr_mark_visible.restype = i32
-    l.gsr_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
-    l.gsr_selftest.restype = i32
-    l.gsr_selftest.argtypes = [vp, vp]
-    l.gsr_timing_read.restype = i32
-    l.gsr_timing_read.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    l.gsr_pack_scratch_bytes.restype = sz
-    l.gsr_pack_scratch_bytes.argtypes = [i32, i32, i32]
-    sp = C.POINTER(GsrStrided)
-    l.gsr_pack_views.restype = i32
-    l.gsr_pack_views.argtypes = [i32, i32, i32, sp, sp, sp, sp, sp, sp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    pp = C.POINTER(C.c_void_p)
-    l.gsr_pack_views_backward.restype = i32
-    l.gsr_pack_views_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, pp, pp, pp, pp, pp, vp]
-    l.fl_scratch_bytes.restype = sz
-    l.fl_scratch_bytes.argtypes = [i32, i32, i32]
-    l.fl_l1_ssim_forward.restype = i32
-    l.fl_l1_ssim_forward.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    l.fl_l1_ssim_backward.restype = i32
-    l.fl_l1_ssim_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    l.up_unproject_forward.restype = i32
-    l.up_unproject_forward.argtypes = [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    l.up_unproject_backward.restype = i32
-    l.up_unproject_backward.argtypes = [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]
-    l.up_unproject_forward_dev.restype = i32
-    l.up_unproject_forward_dev.argtypes = [i32, i32, vp, vp, i64, vp, vp, vp, vp, vp]
-    l.up_unproject_backward_dev.restype = i32
-    l.up_unproject_backward_dev.argtypes = [i32, i32, vp, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp]
-    l.up_splat_scratch_bytes.restype = sz
-    l.up_splat_scratch_bytes.argtypes = [i32, i32]
-    l.up_zsplat.restype = i32
-    l.up_zsplat.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
-    l.up_flow2render_dev.restype = i32
-    l.up_flow2render_dev.argtypes = [i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp, vp, vp]
-    l.cs_forward.restype = i32
-    l.cs_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    l.cs_backward.restype = i32
-    l.cs_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    l.cv_build_forward.restype = i32
-    l.cv_build_forward.argtypes = [vp, vp, pp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.cv_build_backward.restype = i32
-    l.cv_build_backward.argtypes = [vp, vp, pp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.cs_lookup_forward.restype = i32
-    l.cs_lookup_forward.argtypes = [pp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.cs_lookup_backward.restype = i32
-    l.cs_lookup_backward.argtypes = [vp, vp, pp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.cu_upsample_forward.restype = i32
-    l.cu_upsample_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.cu_upsample_backward.restype = i32
-    l.cu_upsample_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.cu_upsample_scratch_bytes.restype = sz
-    l.cu_upsample_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    l.gn_chunk_elems.restype = sz
-    l.gn_chunk_elems.argtypes = []
-    l.gn_scratch_bytes.restype = sz
-    l.gn_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    l.gn_forward.restype = i32
-    l.gn_forward.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
-    l.gn_backward.restype = i32
-    l.gn_backward.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    l.gne_forward.restype = i32
-    l.gne_forward.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]
-    l.gne_backward.restype = i32
-    l.gne_backward.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    l.sc_supported.restype = i32
-    l.sc_supported.argtypes = [i32, i32, i32, i32, i32]
-    l.sc_tile.restype = i32
-    l.sc_tile.argtypes = [C.POINTER(i32), C.POINTER(i32)]
-    l.sc_scratch_bytes.restype = sz
-    l.sc_scratch_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32]
-    l.sc_forward.restype = i32
-    l.sc_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
-    l.sc_backward.restype = i32
-    l.sc_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(l, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if l.gpsgs_abi_version() != 4:
         raise ImportError("gps_gaussian_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = l

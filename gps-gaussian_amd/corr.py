@@ -11,8 +11,7 @@ import sys
 import torch
 
 from . import _capi
-
-_DT = {torch.float32: 0, torch.float16: 1}
+from ._ops import DTYPE_CODE as _DT, call, ptr
 
 
 def _args(volume, coords):
@@ -41,25 +40,14 @@ def _radius(radius):
     return r
 
 
-_lib = None
-
-
-def _call(fn, what, dev, *args):
-    """One C-ABI call on the current stream of `dev`; the device guard (~10 us) is taken only when `dev` is not the current device."""
-    if torch.cuda.current_device() == dev.index:
-        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
-    else:
-        with torch.cuda.device(dev):
-            rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
-    if rc:
-        _capi.check(rc, what)
+_first_call = True
 
 
 def forward(volume, coords, radius):
-    global _lib
-    lib = _lib
-    if lib is None:
-        lib = _lib = _capi.lib()
+    global _first_call
+    if _first_call:
+        _capi.lib()
+        _first_call = False
         acc = sys.modules.get("gps_gaussian_amd.accelerate")  # first sampler call of the process: the opt-in hook's safety net (accelerate.py)
         if acc is not None and acc._armed:
             acc.late_apply()
@@ -67,15 +55,11 @@ def forward(volume, coords, radius):
     radius = _radius(radius)
     v = volume if volume.is_contiguous() else volume.contiguous()
     out = torch.empty((N, 2 * radius + 1, H1, W1), dtype=v.dtype, device=v.device)
-    # plain integers: ctypes converts them to the void* / int arguments declared in _capi (boxing them in c_void_p costs ~1 us each)
-    _call(lib.cs_forward, "cs_forward", v.device, v.data_ptr(), c.data_ptr(), out.data_ptr(), N, H1, W1, W2, radius, _DT[v.dtype])
+    call("cs_forward", v.device, v.data_ptr(), c.data_ptr(), out.data_ptr(), N, H1, W1, W2, radius, _DT[v.dtype])
     return (out,)
 
 
 def backward(volume, coords, grad_output, radius):
-    global _lib
-    lib = _lib or _capi.lib()
-    _lib = lib
     N, H1, W1, W2, c = _args(volume, coords)
     radius = _radius(radius)
     g = grad_output
@@ -84,19 +68,15 @@ def backward(volume, coords, grad_output, radius):
     if g.dtype is not volume.dtype or not g.is_contiguous():
         g = g.to(dtype=volume.dtype).contiguous()
     gv = torch.empty((N, H1, W1, W2), dtype=volume.dtype, device=volume.device)
-    _call(lib.cs_backward, "cs_backward", volume.device, c.data_ptr(), g.data_ptr(), gv.data_ptr(), N, H1, W1, W2, radius, _DT[volume.dtype])
+    call("cs_backward", volume.device, c.data_ptr(), g.data_ptr(), gv.data_ptr(), N, H1, W1, W2, radius, _DT[volume.dtype])
     return (gv,)
 
 
 # ---- the sampler's neighbours inside RAFT-Stereo -------------------------------------------------
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _ptr_array(tensors):
     if len(tensors) > 4:
         raise RuntimeError("at most 4 pyramid levels, got %d" % len(tensors))
-    return (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) if t is not None else None for t in list(tensors) + [None] * (4 - len(tensors))])
+    return (C.c_void_p * 4)(*[ptr(t) for t in list(tensors) + [None] * (4 - len(tensors))])
 
 
 class _BuildPyramid(torch.autograd.Function):
@@ -104,7 +84,6 @@ class _BuildPyramid(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fmap1, fmap2, levels):
-        lib = _capi.lib()
         if not fmap1.is_cuda:
             raise RuntimeError("gps_gaussian_amd: correlation volume inputs must live on a GPU (no CPU fallback)")
         if fmap1.dim() != 4 or fmap2.dim() != 4 or fmap1.shape[:3] != fmap2.shape[:3]:
@@ -117,10 +96,7 @@ class _BuildPyramid(torch.autograd.Function):
         N, D, H, W1 = f1.shape
         W2 = f2.shape[3]
         pyr = [torch.empty((N, H, W1, W2 >> l), dtype=f1.dtype, device=f1.device) for l in range(levels)]
-        with torch.cuda.device(f1.device):
-            rc = lib.cv_build_forward(C.c_void_p(f1.data_ptr()), C.c_void_p(f2.data_ptr()), _ptr_array(pyr), N, D, H, W1, W2, levels,
-                                      _DT[f1.dtype], _stream(f1.device))
-        _capi.check(rc, "cv_build_forward")
+        call("cv_build_forward", f1.device, ptr(f1), ptr(f2), _ptr_array(pyr), N, D, H, W1, W2, levels, _DT[f1.dtype])
         ctx.save_for_backward(f1, f2)
         ctx.levels = levels
         ctx.set_materialize_grads(False)
@@ -128,7 +104,6 @@ class _BuildPyramid(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _capi.lib()
         f1, f2 = ctx.saved_tensors
         N, D, H, W1 = f1.shape
         W2 = f2.shape[3]
@@ -138,11 +113,7 @@ class _BuildPyramid(torch.autograd.Function):
             return None, None, None
         g1 = torch.empty_like(f1) if need1 else None
         g2 = torch.empty_like(f2) if need2 else None
-        with torch.cuda.device(f1.device):
-            rc = lib.cv_build_backward(C.c_void_p(f1.data_ptr()), C.c_void_p(f2.data_ptr()), _ptr_array(gs),
-                                       C.c_void_p(g1.data_ptr()) if need1 else None, C.c_void_p(g2.data_ptr()) if need2 else None, N, D, H, W1,
-                                       W2, ctx.levels, _DT[f1.dtype], _stream(f1.device))
-        _capi.check(rc, "cv_build_backward")
+        call("cv_build_backward", f1.device, ptr(f1), ptr(f2), _ptr_array(gs), ptr(g1), ptr(g2), N, D, H, W1, W2, ctx.levels, _DT[f1.dtype])
         return g1, g2, None
 
 
@@ -151,7 +122,6 @@ class _LookupPyramid(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, coords, radius, *pyr):
-        lib = _capi.lib()
         if not 1 <= len(pyr) <= 4:
             raise RuntimeError("1..4 pyramid levels, got %d" % len(pyr))
         radius = _radius(radius)
@@ -161,25 +131,18 @@ class _LookupPyramid(torch.autograd.Function):
             if tuple(v.shape) != (N, H1, W1, W2 >> l) or v.dtype != v0.dtype or not v.is_contiguous():
                 raise RuntimeError("pyramid level %d must be a contiguous [N,H1,W1,W2>>%d] tensor of the level-0 dtype" % (l, l))
         out = torch.empty((N, len(pyr) * (2 * radius + 1), H1, W1), dtype=v0.dtype, device=v0.device)
-        with torch.cuda.device(v0.device):
-            rc = lib.cs_lookup_forward(_ptr_array(pyr), C.c_void_p(c.data_ptr()), C.c_void_p(out.data_ptr()), N, H1, W1, W2, len(pyr),
-                                       radius, _DT[v0.dtype], _stream(v0.device))
-        _capi.check(rc, "cs_lookup_forward")
+        call("cs_lookup_forward", v0.device, _ptr_array(pyr), ptr(c), ptr(out), N, H1, W1, W2, len(pyr), radius, _DT[v0.dtype])
         ctx.save_for_backward(c)
         ctx.meta = (N, H1, W1, W2, len(pyr), radius, v0.dtype)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _capi.lib()
         c, = ctx.saved_tensors
         N, H1, W1, W2, levels, radius, dt = ctx.meta
         g = grad_out.to(dtype=dt).contiguous()
         gp = [torch.empty((N, H1, W1, W2 >> l), dtype=dt, device=g.device) for l in range(levels)]
-        with torch.cuda.device(g.device):
-            rc = lib.cs_lookup_backward(C.c_void_p(c.data_ptr()), C.c_void_p(g.data_ptr()), _ptr_array(gp), N, H1, W1, W2, levels, radius,
-                                        _DT[dt], _stream(g.device))
-        _capi.check(rc, "cs_lookup_backward")
+        call("cs_lookup_backward", g.device, ptr(c), ptr(g), _ptr_array(gp), N, H1, W1, W2, levels, radius, _DT[dt])
         return (None, None) + tuple(gp)
 
 
@@ -208,7 +171,6 @@ class CorrBlockFast1D:
 class _ConvexUpsample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, mask, factor):
-        lib = _capi.lib()
         if not flow.is_cuda:
             raise RuntimeError("gps_gaussian_amd: upsample_flow inputs must live on a GPU (no CPU fallback)")
         N, Cc, H, W = flow.shape
@@ -217,10 +179,7 @@ class _ConvexUpsample(torch.autograd.Function):
         fl = flow.detach().to(torch.float32).contiguous()
         mk = mask.detach().to(torch.float32).contiguous()  # AMP hands over an fp16 mask; the softmax is evaluated in fp32
         out = torch.empty((N, Cc, H * factor, W * factor), dtype=torch.float32, device=flow.device)
-        with torch.cuda.device(flow.device):
-            rc = lib.cu_upsample_forward(C.c_void_p(fl.data_ptr()), C.c_void_p(mk.data_ptr()), C.c_void_p(out.data_ptr()), N, Cc, H, W, int(factor),
-                                         _stream(flow.device))
-        _capi.check(rc, "cu_upsample_forward")
+        call("cu_upsample_forward", flow.device, ptr(fl), ptr(mk), ptr(out), N, Cc, H, W, int(factor))
         ctx.save_for_backward(fl, mk)
         ctx.factor = int(factor)
         ctx.dtypes = (flow.dtype, mask.dtype)
@@ -237,13 +196,7 @@ class _ConvexUpsample(torch.autograd.Function):
         if gf is None and gm is None:
             return None, None, None
         scratch = torch.empty((lib.cu_upsample_scratch_bytes(N, Cc, H, W),), dtype=torch.uint8, device=fl.device) if gf is not None else None
-        with torch.cuda.device(fl.device):
-            rc = lib.cu_upsample_backward(C.c_void_p(fl.data_ptr()), C.c_void_p(mk.data_ptr()), C.c_void_p(g.data_ptr()),
-                                          C.c_void_p(gf.data_ptr()) if gf is not None else None,
-                                          C.c_void_p(gm.data_ptr()) if gm is not None else None,
-                                          C.c_void_p(scratch.data_ptr()) if scratch is not None else None, N, Cc, H, W, ctx.factor,
-                                          _stream(fl.device))
-        _capi.check(rc, "cu_upsample_backward")
+        call("cu_upsample_backward", fl.device, ptr(fl), ptr(mk), ptr(g), ptr(gf), ptr(gm), ptr(scratch), N, Cc, H, W, ctx.factor)
         return (gf.to(ctx.dtypes[0]) if gf is not None else None, gm.to(ctx.dtypes[1]) if gm is not None else None, None)
 
 

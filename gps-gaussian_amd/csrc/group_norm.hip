@@ -28,6 +28,8 @@
 // the sums keep their order: the result is bit for bit what relu_ / add / relu around the EP_NONE kernels give.
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "gsr_common.h"
 
 namespace {
@@ -487,84 +489,76 @@ void launch_backward(const void *x, const float *dout, const float *out, const f
         hipLaunchKernelGGL(k_gn_param_grad, dim3((unsigned)cdiv(C, GN_THREADS)), block, 0, s, (const float2 *)sums, rstd, N, C, cpg, G, dgamma, dbeta);
 }
 
-}  // namespace
-
-extern "C" int gn_forward(const void *x, int dtype, const float *gamma, const float *beta, int N, int C, int G, int HW, float eps, float *y,
-                          float *mean, float *rstd, void *scratch, void *stream) {
-    const int rc = gn_check(dtype, N, C, G, HW);
-    if (rc != 0) return rc < 0 ? rc : GPSGS_OK;
-    if (!x || !gamma || !beta || !y || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
-    if (!aligned16(x) || !aligned16(y) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
+// f(dt, ep) with the run-time dtype and epilogue as compile-time constants: the six <DT, EP> instantiations of whatever f launches
+template <class F> void dispatch(int dtype, int ep, F f) {
+    auto with_dt = [&](auto dt) {
+        if (ep == EP_NONE)
+            f(dt, std::integral_constant<int, EP_NONE>());
+        else if (ep == EP_RELU)
+            f(dt, std::integral_constant<int, EP_RELU>());
+        else
+            f(dt, std::integral_constant<int, EP_RELU_ADD_RELU>());
+    };
     if (dtype == 0)
-        launch_forward<0, EP_NONE>(x, gamma, beta, nullptr, N, C, G, HW, eps, y, mean, rstd, scratch, s);
+        with_dt(std::integral_constant<int, 0>());
     else
-        launch_forward<1, EP_NONE>(x, gamma, beta, nullptr, N, C, G, HW, eps, y, mean, rstd, scratch, s);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+        with_dt(std::integral_constant<int, 1>());
 }
 
-extern "C" int gn_backward(const void *x, int dtype, const float *dy, const float *gamma, const float *mean, const float *rstd, int N, int C, int G,
-                           int HW, void *dx, float *dgamma, float *dbeta, void *scratch, void *stream) {
-    const int rc = gn_check(dtype, N, C, G, HW);
-    if (rc < 0) return rc;
-    if ((dgamma != nullptr) != (dbeta != nullptr)) return GPSGS_E_INVALID;
-    if (rc != 0) return GPSGS_OK;
-    if (!x || !dy || !gamma || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
-    if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
-    if (!dx && !dgamma) return GPSGS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        launch_backward<0, EP_NONE>(x, dy, nullptr, gamma, nullptr, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
-    else
-        launch_backward<1, EP_NONE>(x, dy, nullptr, gamma, nullptr, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
-}
-
-// ---- the same with the epilogue fused (see the top of the file): residual == NULL / out == NULL select EP_RELU, otherwise EP_RELU_ADD_RELU ----
-extern "C" int gne_forward(const void *x, int dtype, const float *gamma, const float *beta, const float *residual, int N, int C, int G, int HW,
-                           float eps, float *out, float *mean, float *rstd, void *scratch, void *stream) {
+// gn_forward (EP_NONE, no residual) and gne_forward (EP_RELU, or EP_RELU_ADD_RELU with a residual)
+int forward(int ep, const void *x, int dtype, const float *gamma, const float *beta, const float *residual, int N, int C, int G, int HW, float eps,
+            float *out, float *mean, float *rstd, void *scratch, void *stream) {
     const int rc = gn_check(dtype, N, C, G, HW);
     if (rc != 0) return rc < 0 ? rc : GPSGS_OK;
     if (!x || !gamma || !beta || !out || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
     if (!aligned16(x) || !aligned16(out) || !aligned16(residual) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0) {
-        if (residual)
-            launch_forward<0, EP_RELU_ADD_RELU>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, s);
-        else
-            launch_forward<0, EP_RELU>(x, gamma, beta, nullptr, N, C, G, HW, eps, out, mean, rstd, scratch, s);
-    } else {
-        if (residual)
-            launch_forward<1, EP_RELU_ADD_RELU>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, s);
-        else
-            launch_forward<1, EP_RELU>(x, gamma, beta, nullptr, N, C, G, HW, eps, out, mean, rstd, scratch, s);
-    }
+    dispatch(dtype, ep, [&](auto dt, auto e) {
+        launch_forward<decltype(dt)::value, decltype(e)::value>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, (hipStream_t)stream);
+    });
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
 }
 
-extern "C" int gne_backward(const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
-                            const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch,
-                            void *stream) {
+// gn_backward (EP_NONE: no beta, out or dres) and gne_backward (EP_RELU, or EP_RELU_ADD_RELU with the forward's out).  An invalid argument is
+// reported even where there is nothing to do.
+int backward(int ep, const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
+             const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch, void *stream) {
     const int rc = gn_check(dtype, N, C, G, HW);
     if (rc < 0) return rc;
     if ((dgamma != nullptr) != (dbeta != nullptr)) return GPSGS_E_INVALID;
     if (dres && !out) return GPSGS_E_INVALID;  // only the residual form has a residual to differentiate
     if (rc != 0) return GPSGS_OK;
-    if (!x || !dout || !gamma || !beta || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
+    if (!x || !dout || !gamma || (ep != EP_NONE && !beta) || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
     if (!aligned16(x) || !aligned16(dout) || !aligned16(out) || !aligned16(dx) || !aligned16(dres) || ((uintptr_t)scratch & 7) != 0)
         return GPSGS_E_INVALID;
     if (!dx && !dres && !dgamma) return GPSGS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0) {
-        if (out)
-            launch_backward<0, EP_RELU_ADD_RELU>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch, s);
-        else
-            launch_backward<0, EP_RELU>(x, dout, nullptr, gamma, beta, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
-    } else {
-        if (out)
-            launch_backward<1, EP_RELU_ADD_RELU>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch, s);
-        else
-            launch_backward<1, EP_RELU>(x, dout, nullptr, gamma, beta, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, s);
-    }
+    dispatch(dtype, ep, [&](auto dt, auto e) {
+        launch_backward<decltype(dt)::value, decltype(e)::value>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch,
+                                                                 (hipStream_t)stream);
+    });
     return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int gn_forward(const void *x, int dtype, const float *gamma, const float *beta, int N, int C, int G, int HW, float eps, float *y,
+                          float *mean, float *rstd, void *scratch, void *stream) {
+    return forward(EP_NONE, x, dtype, gamma, beta, nullptr, N, C, G, HW, eps, y, mean, rstd, scratch, stream);
+}
+
+extern "C" int gn_backward(const void *x, int dtype, const float *dy, const float *gamma, const float *mean, const float *rstd, int N, int C, int G,
+                           int HW, void *dx, float *dgamma, float *dbeta, void *scratch, void *stream) {
+    return backward(EP_NONE, x, dtype, dy, nullptr, gamma, nullptr, mean, rstd, N, C, G, HW, dx, nullptr, dgamma, dbeta, scratch, stream);
+}
+
+// ---- the same with the epilogue fused (see the top of the file): residual == NULL / out == NULL select EP_RELU, otherwise EP_RELU_ADD_RELU ----
+extern "C" int gne_forward(const void *x, int dtype, const float *gamma, const float *beta, const float *residual, int N, int C, int G, int HW,
+                           float eps, float *out, float *mean, float *rstd, void *scratch, void *stream) {
+    return forward(residual ? EP_RELU_ADD_RELU : EP_RELU, x, dtype, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, stream);
+}
+
+extern "C" int gne_backward(const void *x, int dtype, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean,
+                            const float *rstd, int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch,
+                            void *stream) {
+    return backward(out ? EP_RELU_ADD_RELU : EP_RELU, x, dtype, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch,
+                    stream);
 }

@@ -15,91 +15,26 @@ to two million elements, so most of the chip idles while a handful of CUs stream
 
 `GPSGS_ACCELERATE=groupnorm` makes the reference's extractor classes call convert() on themselves, `GPSGS_ACCELERATE=resblock` also rebinds the
 residual block's forward and fuses the stem's ReLU (accelerate.py)."""
-import ctypes as C
-
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-
-_DTYPES = {torch.float32: 0, torch.float16: 1}
-
-
-def _aligned(t):
-    """Contiguous and 16-byte aligned (a fresh allocation always is; a view into a larger tensor may start anywhere)."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, ptr
 
 
 class _GroupNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, num_groups, weight, bias, eps):
-        lib = _capi.lib()
-        if not x.is_cuda:
-            raise RuntimeError("gps_gaussian_amd: group_norm input must live on a GPU (no CPU fallback)")
-        if x.dtype not in _DTYPES:
-            raise RuntimeError("gps_gaussian_amd: group_norm takes fp32 or fp16 input, not %s" % x.dtype)
-        if x.dim() < 2 or weight is None or bias is None:
-            raise RuntimeError("gps_gaussian_amd: group_norm needs an [N, C, ...] input, a weight and a bias")
-        N, Cn, G = x.shape[0], x.shape[1], int(num_groups)
-        if G <= 0 or Cn % G != 0 or weight.numel() != Cn or bias.numel() != Cn:
-            raise RuntimeError("gps_gaussian_amd: group_norm: %d channels, %d groups, %d weights, %d biases" % (Cn, G, weight.numel(), bias.numel()))
-        dev = x.device
-        xc = _aligned(x.detach())
-        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
-        HW = xc.numel() // (N * Cn) if N * Cn else 0
-        y = torch.empty(x.shape, dtype=torch.float32, device=dev)
-        mean = torch.empty((N, G), dtype=torch.float32, device=dev)
-        rstd = torch.empty((N, G), dtype=torch.float32, device=dev)
-        scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gn_forward(_ptr(xc), _DTYPES[x.dtype], _ptr(w), _ptr(b), N, Cn, G, HW, float(eps), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(scratch),
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gn_forward")
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(xc, mean, rstd, w)   # never y: the reference applies an in-place ReLU to it
-            ctx.dims = (N, Cn, G, HW, x.shape, weight.dtype, bias.dtype)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        lib = _capi.lib()
-        xc, mean, rstd, w = ctx.saved_tensors
-        N, Cn, G, HW, shape, wdt, bdt = ctx.dims
-        dev = xc.device
-        need_x, _, need_w, need_b, _ = ctx.needs_input_grad
-        dyc = _aligned(dy.to(torch.float32))
-        dx = torch.empty_like(xc) if need_x else None
-        dgamma = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
-        dbeta = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
-        scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gn_backward(_ptr(xc), _DTYPES[xc.dtype], _ptr(dyc), _ptr(w), _ptr(mean), _ptr(rstd), N, Cn, G, HW, _ptr(dx), _ptr(dgamma), _ptr(dbeta),
-                                 _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gn_backward")
-        if dgamma is not None and N * Cn * HW == 0:
-            dgamma.zero_(), dbeta.zero_()
-        return (dx.view(shape) if need_x else None, None, dgamma.to(wdt) if need_w else None, dbeta.to(bdt) if need_b else None, None)
-
-
-class _GroupNormEpilogue(torch.autograd.Function):
-    """relu(group_norm(x)) or, with a residual, relu(residual + relu(group_norm(x))): one node.  Saved for the backward: x, mean, rstd, weight, bias
-    (the sign of the normalised value is recomputed from them) and, in the residual form only, the output (its sign masks the incoming gradient; the
+    """group_norm(x); with relu, relu(group_norm(x)) or, with a residual too, relu(residual + relu(group_norm(x))): one node each.  Saved for the
+    backward: x, mean, rstd, weight -- never y: the reference applies an in-place ReLU to it; with relu also the bias (the sign of the normalised
+    value is recomputed from them, not read from the output) and, in the residual form only, the output (its sign masks the incoming gradient; the
     layer that consumes the output keeps it alive anyway)."""
 
     @staticmethod
-    def forward(ctx, x, num_groups, weight, bias, eps, residual):
+    def forward(ctx, x, num_groups, weight, bias, eps, relu, residual):
         lib = _capi.lib()
         if not x.is_cuda:
             raise RuntimeError("gps_gaussian_amd: group_norm input must live on a GPU (no CPU fallback)")
-        if x.dtype not in _DTYPES:
+        if x.dtype not in DTYPE_CODE:
             raise RuntimeError("gps_gaussian_amd: group_norm takes fp32 or fp16 input, not %s" % x.dtype)
         if x.dim() < 2 or weight is None or bias is None:
             raise RuntimeError("gps_gaussian_amd: group_norm needs an [N, C, ...] input, a weight and a bias")
@@ -110,8 +45,8 @@ class _GroupNormEpilogue(torch.autograd.Function):
         if residual is not None and not (torch.is_tensor(residual) and residual.is_cuda and residual.device == dev
                                          and residual.dtype == torch.float32 and residual.shape == x.shape):
             raise RuntimeError("gps_gaussian_amd: group_norm: residual must be an fp32 GPU tensor of the input's shape %s" % (tuple(x.shape),))
-        xc = _aligned(x.detach())
-        rc_ = _aligned(residual.detach()) if residual is not None else None
+        xc = aligned16(x.detach())
+        res = aligned16(residual.detach()) if residual is not None else None
         w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
         b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
         HW = xc.numel() // (N * Cn) if N * Cn else 0
@@ -119,41 +54,44 @@ class _GroupNormEpilogue(torch.autograd.Function):
         mean = torch.empty((N, G), dtype=torch.float32, device=dev)
         rstd = torch.empty((N, G), dtype=torch.float32, device=dev)
         scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gne_forward(_ptr(xc), _DTYPES[x.dtype], _ptr(w), _ptr(b), _ptr(rc_), N, Cn, G, HW, float(eps), _ptr(out), _ptr(mean), _ptr(rstd),
-                                 _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gne_forward")
+        head = (ptr(xc), DTYPE_CODE[x.dtype], ptr(w), ptr(b))
+        tail = (N, Cn, G, HW, float(eps), ptr(out), ptr(mean), ptr(rstd), ptr(scratch))
+        if relu:
+            call("gne_forward", dev, *head, ptr(res), *tail)
+        else:
+            call("gn_forward", dev, *head, *tail)   # the plain op keeps its own entry point and kernels
         if any(ctx.needs_input_grad):
-            if residual is None:
-                ctx.save_for_backward(xc, mean, rstd, w, b)      # never the output: its sign is the sign of y, recomputed
-            else:
-                ctx.save_for_backward(xc, mean, rstd, w, b, out)
-            ctx.dims = (N, Cn, G, HW, x.shape, weight.dtype, bias.dtype)
+            ctx.save_for_backward(xc, mean, rstd, w, *((b,) if relu else ()), *((out,) if residual is not None else ()))
+            ctx.dims = (N, Cn, G, HW, x.shape, weight.dtype, bias.dtype, relu)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         lib = _capi.lib()
-        xc, mean, rstd, w, b = ctx.saved_tensors[:5]
-        out = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
-        N, Cn, G, HW, shape, wdt, bdt = ctx.dims
+        N, Cn, G, HW, shape, wdt, bdt, relu = ctx.dims
+        saved = ctx.saved_tensors
+        xc, mean, rstd, w = saved[:4]
+        out = saved[5] if len(saved) > 5 else None
         dev = xc.device
-        need_x, _, need_w, need_b, _, need_r = ctx.needs_input_grad
+        need_x, _, need_w, need_b, _, _, need_r = ctx.needs_input_grad
         need_r = need_r and out is not None
-        dc = _aligned(dout.to(torch.float32))
+        dc = aligned16(dout.to(torch.float32))
         dx = torch.empty_like(xc) if need_x else None
         dres = torch.empty(shape, dtype=torch.float32, device=dev) if need_r else None
         dgamma = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
         dbeta = torch.empty((Cn,), dtype=torch.float32, device=dev) if need_w or need_b else None
         scratch = torch.empty((lib.gn_scratch_bytes(N, Cn, G, HW) // 4 + 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.gne_backward(_ptr(xc), _DTYPES[xc.dtype], _ptr(dc), _ptr(out), _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), N, Cn, G, HW, _ptr(dx),
-                                  _ptr(dres), _ptr(dgamma), _ptr(dbeta), _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gne_backward")
-        if N * Cn * HW == 0 and dgamma is not None:
+        head = (ptr(xc), DTYPE_CODE[xc.dtype], ptr(dc))
+        stats = (ptr(mean), ptr(rstd), N, Cn, G, HW, ptr(dx))
+        tail = (ptr(dgamma), ptr(dbeta), ptr(scratch))
+        if relu:
+            call("gne_backward", dev, *head, ptr(out), ptr(w), ptr(saved[4]), *stats, ptr(dres), *tail)
+        else:
+            call("gn_backward", dev, *head, ptr(w), *stats, *tail)
+        if dgamma is not None and N * Cn * HW == 0:
             dgamma.zero_(), dbeta.zero_()
-        return (dx.view(shape) if need_x else None, None, dgamma.to(wdt) if need_w else None, dbeta.to(bdt) if need_b else None, None, dres)
+        return (dx.view(shape) if need_x else None, None, dgamma.to(wdt) if need_w else None, dbeta.to(bdt) if need_b else None, None, None, dres)
 
 
 def group_norm(x, num_groups, weight, bias, eps=1e-5, *, relu=False, residual=None):
@@ -166,14 +104,7 @@ def group_norm(x, num_groups, weight, bias, eps=1e-5, *, relu=False, residual=No
     and r.  A residual without relu=True, or one of another device, dtype or shape, is a RuntimeError."""
     if residual is not None and not relu:
         raise RuntimeError("gps_gaussian_amd: group_norm: residual= needs relu=True (the fused form is relu(residual + relu(y)))")
-    if not relu:
-        return _GroupNorm.apply(x, num_groups, weight, bias, eps)
-    return _GroupNormEpilogue.apply(x, num_groups, weight, bias, eps, residual)
-
-
-def _autocast_dtype():
-    get = getattr(torch, "get_autocast_dtype", None)      # newer torch; the older accessor warns there
-    return get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
+    return _GroupNorm.apply(x, num_groups, weight, bias, eps, bool(relu), residual)
 
 
 def _fusable(m, x):
@@ -182,7 +113,7 @@ def _fusable(m, x):
     if m.weight.dtype != torch.float32 or m.bias.dtype != torch.float32 or not m.weight.is_cuda:
         return False
     if x.dtype == torch.float16:
-        if not (torch.is_autocast_enabled() and _autocast_dtype() == torch.float16):
+        if not (torch.is_autocast_enabled() and autocast_dtype() == torch.float16):
             return False   # ATen would return fp16 here
     elif x.dtype != torch.float32:
         return False
@@ -203,7 +134,7 @@ class FusedGroupNorm(nn.GroupNorm):
             accelerate.calls["groupnorm_passthrough"] += 1
             return nn.GroupNorm.forward(self, input)
         accelerate.calls["groupnorm"] += 1
-        return _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps)
+        return _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps, False, None)
 
     def forward_relu(self, input, residual=None):
         """relu_(self(input)), and with a residual relu(residual + that): in the fused kernels where forward() would use them, otherwise with
@@ -214,10 +145,10 @@ class FusedGroupNorm(nn.GroupNorm):
             return y if residual is None else torch.relu(residual + y)
         accelerate.calls["groupnorm"] += 1
         if residual is None:
-            return _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, None)
+            return _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps, True, None)
         if not (residual.is_cuda and residual.device == input.device and residual.dtype == torch.float32 and residual.shape == input.shape):
-            return torch.relu(residual + _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, None))   # broadcast, fp64, ...
-        return _GroupNormEpilogue.apply(input, self.num_groups, self.weight, self.bias, self.eps, residual)
+            return torch.relu(residual + _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps, True, None))   # broadcast, fp64, ...
+        return _GroupNorm.apply(input, self.num_groups, self.weight, self.bias, self.eps, True, residual)
 
 
 class FusedGroupNormReLU(FusedGroupNorm):

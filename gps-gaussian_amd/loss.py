@@ -4,13 +4,12 @@ Same definitions as /root/reference/lib/loss.py:36-37 (`l1_loss`) and :40-83 (`s
 padding, mean over batch/channels/pixels); train_stage2.py:70-72 combines them as 0.8 * L1 + 0.2 * (1 - SSIM).
 One forward launch pair and one backward launch replace ~30 eager kernels each way.  Gradient flows to `pred` only (the
 ground-truth image has no gradient in the reference either).  No CPU fallback."""
-import ctypes as C
-
 import threading
 
 import torch
 
 from . import _capi
+from ._ops import call, ptr
 
 
 class _L1SSIM(torch.autograd.Function):
@@ -30,11 +29,7 @@ class _L1SSIM(torch.autograd.Function):
         maps = [torch.empty_like(p) for _ in range(3)] if need else [None, None, None]
         scratch = torch.empty((lib.fl_scratch_bytes(planes, H, W) // 4 + 1,), dtype=torch.float32, device=dev)
         out2 = torch.empty((2,), dtype=torch.float32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            rc = lib.fl_l1_ssim_forward(ptr(p), ptr(g), planes, H, W, ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(scratch), ptr(out2),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "fl_l1_ssim_forward")
+        call("fl_l1_ssim_forward", dev, ptr(p), ptr(g), planes, H, W, ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(scratch), ptr(out2))
         if need:
             ctx.save_for_backward(p, g, *maps)
         ctx.dims = (planes, H, W, pred.shape, pred.dtype)
@@ -42,18 +37,13 @@ class _L1SSIM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
-        lib = _capi.lib()
         p, g, m1, m2, m3 = ctx.saved_tensors
         planes, H, W, shape, dtype = ctx.dims
         dev = p.device
         zero = torch.zeros((), dtype=torch.float32, device=dev)
         gout = torch.stack([(g_l1 if g_l1 is not None else zero).float().reshape(()), (g_ssim if g_ssim is not None else zero).float().reshape(())])
         d = torch.empty_like(p)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.fl_l1_ssim_backward(ptr(p), ptr(g), ptr(m1), ptr(m2), ptr(m3), planes, H, W, ptr(gout), ptr(d),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "fl_l1_ssim_backward")
+        call("fl_l1_ssim_backward", dev, ptr(p), ptr(g), ptr(m1), ptr(m2), ptr(m3), planes, H, W, ptr(gout), ptr(d))
         return d.view(shape).to(dtype), None
 
 

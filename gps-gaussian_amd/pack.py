@@ -9,6 +9,7 @@ import ctypes as C
 import torch
 
 from . import _capi
+from ._ops import call, ptr
 
 VIEWS = ("lmain", "rmain")
 
@@ -68,12 +69,8 @@ class _PackViews(torch.autograd.Function):
         row_of_pixel = torch.empty((B, n_views, S2), dtype=torch.int32, device=dev)
         offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
         scratch = torch.empty((lib.gsr_pack_scratch_bytes(B, n_views, S2) // 4 + 1,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.gsr_pack_views(B, n_views, S2, arrs["valid"], arrs["xyz"], arrs["img"], arrs["rot"], arrs["scale"], arrs["opacity"],
-                                    p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(out[4]), p(row_of_pixel), p(offsets), p(scratch),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gsr_pack_views")
+        call("gsr_pack_views", dev, B, n_views, S2, arrs["valid"], arrs["xyz"], arrs["img"], arrs["rot"], arrs["scale"], arrs["opacity"],
+             ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(row_of_pixel), ptr(offsets), ptr(scratch))
         ctx.save_for_backward(row_of_pixel)
         ctx.meta = (n_views, B, S2, [tuple(t.shape) for t in tensors])
         # the packed colours are differentiable only if some image is (in stage 2 none is: the rasteriser backward then skips dL/dcolour)
@@ -87,7 +84,6 @@ class _PackViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_rgb, g_rot, g_scale, g_op, _g_offsets, _g_rows):
-        lib = _capi.lib()
         (row_of_pixel,) = ctx.saved_tensors
         n_views, B, S2, shapes = ctx.meta
         dev = row_of_pixel.device
@@ -106,12 +102,8 @@ class _PackViews(torch.autograd.Function):
                     ptrs[name][v] = None
         cg = lambda t: None if t is None else t.contiguous()
         g_xyz, g_rgb, g_rot, g_scale, g_op = map(cg, (g_xyz, g_rgb, g_rot, g_scale, g_op))
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            rc = lib.gsr_pack_views_backward(B, n_views, S2, p(row_of_pixel), p(g_xyz), p(g_rgb), p(g_rot), p(g_scale), p(g_op),
-                                             ptrs["xyz"], ptrs["img"], ptrs["rot"], ptrs["scale"], ptrs["op"],
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "gsr_pack_views_backward")
+        call("gsr_pack_views_backward", dev, B, n_views, S2, ptr(row_of_pixel), ptr(g_xyz), ptr(g_rgb), ptr(g_rot), ptr(g_scale), ptr(g_op),
+             ptrs["xyz"], ptrs["img"], ptrs["rot"], ptrs["scale"], ptrs["op"])
         return (None, *grads)
 
 

@@ -42,6 +42,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
+from ._ops import device_guard as _device_guard, ptr as _ptr
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -274,10 +275,6 @@ def _drain_pending(st, block=False):
             st["pending"] = keep + st["pending"]
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None  # ctypes converts a Python int to the void* argument
-
-
 class _HeaderRing:
     """Pinned 32-byte header slots the scan kernel writes directly (gsr_forward_notify), allocated in chunks (allocating pinned memory per call
     costs tens of us).  `acquire_notify()` / `release()` hand them out with IN-FLIGHT ACCOUNTING: a slot goes back to the free list only after the
@@ -412,22 +409,6 @@ def _cam(t, n, device):
     if t.numel() != n:
         raise RuntimeError("camera tensor must have %d elements" % n)
     return t
-
-
-class _NoGuard:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NOGUARD = _NoGuard()
-
-
-def _device_guard(dev):
-    # switching the current device costs ~10 us; skip it when the tensors already live on the current device
-    return _NOGUARD if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
 class _Rows:

@@ -9,11 +9,10 @@ Per target pixel the result is the SEQUENTIAL one -- lmain's points in index ord
 `if z >= depth[px]: depth[px] = z; colour[px] = rgb` -- deterministically; the reference's Taichi kernel writes the colour after a separate
 atomic_max and can keep the colour of the farther of two points landing together.  No gradients (the reference's path has none) and no CPU fallback.
 """
-import ctypes as C
-
 import torch
 
 from . import _capi
+from ._ops import call, ptr
 from .unproject import _cams
 
 
@@ -21,14 +20,6 @@ def _gpu(t, what):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("gps_gaussian_amd.splat: %s must be a tensor on a GPU (no CPU fallback)" % what)
     return t
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def zsplat(pts, mask, depth, color):
@@ -56,9 +47,7 @@ def zsplat(pts, mask, depth, color):
         m = mask.detach().to(device=dev, dtype=torch.float32).reshape(V, B, N).contiguous()
         lib = _capi.lib()
         scratch = torch.empty((max(1, lib.up_splat_scratch_bytes(B, res)),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.up_zsplat(V, B, N, res, _p(q), _p(m), _p(depth), _p(color), _p(scratch), scratch.numel(), _stream(dev))
-    _capi.check(rc, "up_zsplat")
+        call("up_zsplat", dev, V, B, N, res, ptr(q), ptr(m), ptr(depth), ptr(color), ptr(scratch), scratch.numel())
     return depth, color
 
 
@@ -94,10 +83,8 @@ def render_views(lmain, rmain, intr, extr, res=None, batch=None, with_points=Fal
         novel = torch.cat([intr.detach()[:nb].reshape(nb, 9), extr.detach()[:nb, :3, :4].reshape(nb, 12)], dim=1).to(dtype=torch.float32).contiguous()
         lib = _capi.lib()
         scratch = torch.empty((max(1, lib.up_splat_scratch_bytes(nb, res)),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.up_flow2render_dev(nb, S, res, _p(f[0]), _p(f[1]), _p(m[0]), _p(m[1]), S * S, _p(im[0]), _p(im[1]), _p(cams), _p(novel),
-                                        _p(scratch), scratch.numel(), _p(img_pred), _p(pts), _stream(dev))
-    _capi.check(rc, "up_flow2render_dev")
+        call("up_flow2render_dev", dev, nb, S, res, ptr(f[0]), ptr(f[1]), ptr(m[0]), ptr(m[1]), S * S, ptr(im[0]), ptr(im[1]), ptr(cams), ptr(novel),
+             ptr(scratch), scratch.numel(), ptr(img_pred), ptr(pts))
     return img_pred, pts
 
 

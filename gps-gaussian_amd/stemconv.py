@@ -11,25 +11,12 @@ directly in NCHW with the input patch of an output tile in LDS and wave-uniform 
   convert(module)                            turn every supported nn.Conv2d of a module tree into a FusedStemConv2d, in place
 
 `GPSGS_ACCELERATE=stemconv` makes the reference's UnetExtractor call convert() on itself (accelerate.py)."""
-import ctypes as C
-
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-
-_DTYPES = {torch.float32: 0, torch.float16: 1}
-
-
-def _aligned(t):
-    """Contiguous and 16-byte aligned (a fresh allocation always is; a view into a larger tensor may start anywhere)."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, ptr
 
 
 def _pair(v):
@@ -52,7 +39,7 @@ class _StemConv(torch.autograd.Function):
             raise RuntimeError("gps_gaussian_amd: conv2d input must live on a GPU (no CPU fallback)")
         if x.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4 or bias is None:
             raise RuntimeError("gps_gaussian_amd: conv2d takes an fp32 [N, C_in, H, W] input, a [C_out, C_in, K, K] weight and a bias")
-        if out_dtype not in _DTYPES:
+        if out_dtype not in DTYPE_CODE:
             raise RuntimeError("gps_gaussian_amd: conv2d returns fp32 or fp16, not %s" % out_dtype)
         N, Ci, H, W = x.shape
         Co, Ci_w, K, K2 = weight.shape
@@ -61,15 +48,12 @@ class _StemConv(torch.autograd.Function):
             raise RuntimeError("gps_gaussian_amd: conv2d: unsupported configuration: input %s, weight %s, stride %d, padding %d"
                                % (tuple(x.shape), tuple(weight.shape), s, p))
         dev = x.device
-        xc = _aligned(x.detach())
+        xc = aligned16(x.detach())
         w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
         b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
         Ho, Wo = (H + 2 * p - K) // s + 1, (W + 2 * p - K) // s + 1
         y = torch.empty((N, Co, Ho, Wo), dtype=out_dtype, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sc_forward(_ptr(xc), _ptr(w), _ptr(b), N, Ci, Co, H, W, K, s, p, _ptr(y), _DTYPES[out_dtype],
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "sc_forward")
+        call("sc_forward", dev, ptr(xc), ptr(w), ptr(b), N, Ci, Co, H, W, K, s, p, ptr(y), DTYPE_CODE[out_dtype])
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(xc, w)
             ctx.dims = (N, Ci, Co, H, W, K, s, p, weight.dtype, bias.dtype)
@@ -83,17 +67,14 @@ class _StemConv(torch.autograd.Function):
         N, Ci, Co, H, W, K, s, p, wdt, bdt = ctx.dims
         dev = xc.device
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        dyc = _aligned(dy if dy.dtype in _DTYPES else dy.to(torch.float32))
+        dyc = aligned16(dy if dy.dtype in DTYPE_CODE else dy.to(torch.float32))
         dx = torch.empty_like(xc) if need_x else None      # the input-gradient kernel runs only when x wants one
         dw = db = scratch = None
         if need_w or need_b:
             dw = torch.empty((Co, Ci, K, K), dtype=torch.float32, device=dev)
             db = torch.empty((Co,), dtype=torch.float32, device=dev)
             scratch = torch.empty((lib.sc_scratch_bytes(N, Ci, Co, H, W, K, s, p) // 4 + 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sc_backward(_ptr(xc), _ptr(w), _ptr(dyc), _DTYPES[dyc.dtype], N, Ci, Co, H, W, K, s, p, _ptr(dx), _ptr(dw), _ptr(db),
-                                 _ptr(scratch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "sc_backward")
+        call("sc_backward", dev, ptr(xc), ptr(w), ptr(dyc), DTYPE_CODE[dyc.dtype], N, Ci, Co, H, W, K, s, p, ptr(dx), ptr(dw), ptr(db), ptr(scratch))
         return dx, dw.to(wdt) if need_w else None, db.to(bdt) if need_b else None, None, None, None
 
 
@@ -103,11 +84,6 @@ def conv2d(x, weight, bias, stride, padding, *, out_dtype=torch.float32):
     `out_dtype` (fp32 or fp16).  Gradients come back in the parameters' dtypes, x.grad in fp32; the input-gradient kernel is launched only if x
     requires grad."""
     return _StemConv.apply(x, weight, bias, stride, padding, out_dtype)
-
-
-def _autocast_dtype():
-    get = getattr(torch, "get_autocast_dtype", None)      # newer torch; the older accessor warns there
-    return get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
 
 
 def _out_dtype(m, x):
@@ -121,7 +97,7 @@ def _out_dtype(m, x):
     if x.shape[1] != m.in_channels or not supported(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups):
         return None
     if torch.is_autocast_enabled():
-        return torch.float16 if _autocast_dtype() == torch.float16 else None   # conv2d is on autocast's lower-precision list; bf16 is ATen's
+        return torch.float16 if autocast_dtype() == torch.float16 else None   # conv2d is on autocast's lower-precision list; bf16 is ATen's
     return torch.float32
 
 

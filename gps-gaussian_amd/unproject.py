@@ -6,11 +6,9 @@ pts_valid [B,S*S]) and is differentiable w.r.t. the predicted flow.  The camera 
 are gathered into one [B,31] tensor by a torch.cat and the kernels read them from there (up_unproject_*_dev) -- the reference's scripts
 keep them on the GPU (train_stage2.py:154-156), and reading them back (round 3) put a device synchronisation in the middle of every network forward.
 No CPU fallback."""
-import ctypes as C
-
 import torch
 
-from . import _capi
+from ._ops import call, ptr
 
 
 def _cams(ref_intr, intr, extr, tf_x, B, dev):
@@ -22,7 +20,6 @@ def _cams(ref_intr, intr, extr, tf_x, B, dev):
 class _Unproject(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, mask, ref_intr, intr, extr, tf_x):
-        lib = _capi.lib()
         if not flow.is_cuda:
             raise RuntimeError("gps_gaussian_amd: unproject inputs must live on a GPU (no CPU fallback)")
         B, _, S, S2_ = flow.shape
@@ -35,30 +32,21 @@ class _Unproject(torch.autograd.Function):
         depth = torch.empty((B, 1, S, S), dtype=torch.float32, device=dev)
         xyz = torch.empty((B, S * S, 3), dtype=torch.float32, device=dev)
         valid = torch.empty((B, S * S), dtype=torch.bool, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.up_unproject_forward_dev(B, S, p(f), p(m), m.stride(0), p(cams), p(depth), p(xyz), p(valid),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "up_unproject_forward_dev")
+        call("up_unproject_forward_dev", dev, B, S, ptr(f), ptr(m), m.stride(0), ptr(cams), ptr(depth), ptr(xyz), ptr(valid))
         ctx.save_for_backward(depth, m, cams)
         ctx.mark_non_differentiable(valid)
         return depth, xyz, valid
 
     @staticmethod
     def backward(ctx, g_depth, g_xyz, _g_valid):
-        lib = _capi.lib()
         depth, m, cams = ctx.saved_tensors
         B, _, S, _ = depth.shape
         dev = depth.device
         gd = g_depth.float().contiguous() if g_depth is not None else None
         gx = g_xyz.float() if g_xyz is not None else None
         d_flow = torch.empty((B, 1, S, S), dtype=torch.float32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         st = (gx.stride(0), gx.stride(1), gx.stride(2)) if gx is not None else (0, 0, 0)
-        with torch.cuda.device(dev):
-            rc = lib.up_unproject_backward_dev(B, S, p(depth), p(m), m.stride(0), p(cams), p(gd), p(gx), st[0], st[1], st[2], p(d_flow),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _capi.check(rc, "up_unproject_backward_dev")
+        call("up_unproject_backward_dev", dev, B, S, ptr(depth), ptr(m), m.stride(0), ptr(cams), ptr(gd), ptr(gx), st[0], st[1], st[2], ptr(d_flow))
         return d_flow, None, None, None, None, None
 
 

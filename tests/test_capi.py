@@ -34,6 +34,15 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.gpsgs_build_info()
 
 
+def test_every_listed_symbol_has_its_prototype():
+    """The prototype table and the four symbol tuples are one list, and lib() leaves no symbol on ctypes' default conversion (which would pass a
+    64-bit device pointer as a C int)."""
+    names = _capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS
+    assert tuple(_capi.PROTOTYPES) == names
+    lib = _capi.lib()
+    assert [n for n in names if getattr(lib, n).argtypes is None] == []
+
+
 def test_python_constants_mirror_the_header():
     """Every GSR_FLAG_* / GPSGS_E_* the ctypes shim uses has the value include/gpsgs.h gives it (a flag added on one side only would
     silently select a different kernel path)."""
