@@ -1,9 +1,8 @@
-// corr_pyramid.hip -- the neighbours of the 1-D correlation sampler inside RAFT-Stereo, for gfx950:
+// corr_pyramid.hip -- the neighbours of the 1-D correlation sampler (corr_sampler.hip: the single-volume and the all-levels lookup) inside
+// RAFT-Stereo, for gfx950:
 //
 //   cv_build_forward / cv_build_backward     all-pairs 1-D correlation volume + its average-pool pyramid
 //                                            (/root/reference/core/corr.py:31-61: CorrBlockFast1D.__init__ / .corr)
-//   cs_lookup_forward / cs_lookup_backward   the 2r+1-tap lookup in ALL pyramid levels in one launch, written straight into the
-//                                            concatenated [N, L*(2r+1), H, W] tensor (core/corr.py:44-51: CorrBlockFast1D.__call__)
 //   cu_upsample_forward / cu_upsample_backward   convex-combination upsampling of the flow (core/raft_stereo_human.py:69-81)
 //
 // The volume is GEMM-shaped work -- per (image, row): C[w1, w2] = sum_d F1[d, w1] F2[d, w2] / sqrt(D), 128 x 192 x 128 at the
@@ -13,23 +12,11 @@
 // columns live in neighbouring lanes: three lane-xor exchanges), so the level-0 volume is never re-read.  The backward
 // folds the four per-level gradients back into d(level 0) while it stages that operand, and runs the two transposed GEMMs
 // with the same tile engine.  fp16 tensors (stage 2 runs under AMP) are widened on load and rounded once on store.
-#include <hip/hip_fp16.h>
-
-#include "gsr_common.h"
+#include "op_common.h"
 
 namespace {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
-
-template <typename T> __device__ __forceinline__ float ldf(const T *p);
-template <> __device__ __forceinline__ float ldf<float>(const float *p) { return *p; }
-template <> __device__ __forceinline__ float ldf<__half>(const __half *p) { return __half2float(*p); }
-template <typename T> __device__ __forceinline__ void stf(T *p, float v);
-template <> __device__ __forceinline__ void stf<float>(float *p, float v) { *p = v; }
-template <> __device__ __forceinline__ void stf<__half>(__half *p, float v) { *p = __float2half(v); }
-template <typename T> __device__ __forceinline__ float rnd(float v);  // round to the storage type (fp16 pyramids are pooled level by level)
-template <> __device__ __forceinline__ float rnd<float>(float v) { return v; }
-template <> __device__ __forceinline__ float rnd<__half>(float v) { return __half2float(__float2half(v)); }
 
 constexpr int TK = 32;  // K-chunk staged through LDS per step
 
@@ -128,13 +115,6 @@ template <typename T> __device__ __forceinline__ bool vec4_ok(const T *base, int
 }
 
 // ---- forward: volume + pyramid ----------------------------------------------------------------------------------------
-struct PyrPtrs {
-    void *p[4];
-};
-struct PyrConstPtrs {
-    const void *p[4];
-};
-
 constexpr int FWD_MT = 2;  // 128 w1 rows per workgroup: at the reference's 128-wide feature maps F2 is fetched once per (image, row)
 
 template <typename T>
@@ -264,73 +244,10 @@ __global__ __launch_bounds__(256, 2) void k_cv_bwd(const T *__restrict__ fother,
     }
 }
 
-// ---- fused multi-level lookup -------------------------------------------------------------------------------------------
-#pragma clang fp contract(off)
-template <typename T>
-__global__ __launch_bounds__(256) void k_lookup_fwd(PyrConstPtrs pyr, const float *__restrict__ coords, T *__restrict__ out, int total, int H1,
-                                                    int W1, int W2, int levels, int r) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;  // (n*H1 + y)*W1 + x
-    if (idx >= total) return;
-    const int hw = H1 * W1;
-    const int n = idx / hw, yx = idx - n * hw;
-    const int rd = 2 * r + 1;
-    const float x = coords[idx];
-    int wl = W2;
-    float inv = 1.f;
-    for (int l = 0; l < levels; l++) {
-        const float x0 = x * inv;  // coords / 2^l is exact
-        const float fl = floorf(x0);
-        const float dx = x0 - fl;
-        const int xs = (int)fl - r;
-        const T *v = reinterpret_cast<const T *>(pyr.p[l]) + (size_t)idx * wl;
-        float prev = (xs >= 0 && xs < wl) ? ldf(v + xs) : 0.f;
-        T *o = out + ((size_t)n * levels * rd + (size_t)l * rd) * hw + yx;
-        for (int k = 0; k < rd; k++) {
-            const int x1 = xs + k + 1;
-            const float next = (x1 >= 0 && x1 < wl) ? ldf(v + x1) : 0.f;
-            stf(o + (size_t)k * hw, prev * (1.0f - dx) + next * dx);
-            prev = next;
-        }
-        wl >>= 1;
-        inv *= 0.5f;
-    }
-}
-
-// one thread per level-0 COLUMN position e = (row idx, c): writes element c of every level whose row is at least c+1 wide
-// (each gradient row is owned by one (n, y, x), so there is no scatter and the zero fill is fused)
-template <typename T>
-__global__ __launch_bounds__(256) void k_lookup_bwd(const float *__restrict__ coords, const T *__restrict__ grad_out, PyrPtrs gpyr, size_t total,
-                                                    int H1, int W1, int W2, int levels, int r) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % W2);
-    const size_t idx = e / W2;
-    const int hw = H1 * W1;
-    const int n = (int)(idx / hw), yx = (int)(idx - (size_t)n * hw);
-    const int rd = 2 * r + 1;
-    const float x = coords[idx];
-    int wl = W2;
-    float inv = 1.f;
-    for (int l = 0; l < levels; l++) {
-        if (c < wl) {
-            const float x0 = x * inv;
-            const float fl = floorf(x0);
-            const float dx = x0 - fl;
-            const int i = c - ((int)fl - r);  // tap index of this element, valid 0..rd
-            float gsum = 0.f;
-            if (i >= 0 && i <= rd) {
-                const T *go = grad_out + ((size_t)n * levels * rd + (size_t)l * rd) * hw + yx;
-                if (i > 0) gsum += ldf(go + (size_t)(i - 1) * hw) * dx;
-                if (i < rd) gsum += ldf(go + (size_t)i * hw) * (1.0f - dx);
-            }
-            stf(reinterpret_cast<T *>(gpyr.p[l]) + idx * wl + c, gsum);
-        }
-        wl >>= 1;
-        inv *= 0.5f;
-    }
-}
-
 // ---- convex upsampling --------------------------------------------------------------------------------------------------
+// No FMA contraction from here to the end of the file.  These kernels were first compiled behind the lookup kernels' pragma (the lookup has since
+// moved to corr_sampler.hip) and their bits are pinned as they came out then; the GEMM kernels above stay contract-on.
+#pragma clang fp contract(off)
 // out[n, c, h f + i, w f + j] = sum_k softmax_k(mask[n, k f^2 + i f + j, h, w]) * f * flow[n, c, h + k / 3 - 1, w + k % 3 - 1]   (zero padded)
 // One thread per (n, h, w, i, j) with the fine column fastest: mask reads walk j (stride H W: the 9 f^2 planes are read
 // once, coalesced along w for fixed (i, j) by the neighbouring threads of other w), output stores are coalesced.
@@ -460,7 +377,7 @@ __global__ __launch_bounds__(256) void k_up_bwd_flow(const float *__restrict__ S
 }  // namespace
 
 static bool dims_ok(int N, int D, int H, int W1, int W2, int levels, int dtype) {
-    return N >= 0 && D >= 0 && H >= 0 && W1 >= 0 && W2 >= 0 && levels >= 1 && levels <= 4 && (dtype == 0 || dtype == 1);
+    return N >= 0 && D >= 0 && H >= 0 && W1 >= 0 && W2 >= 0 && levels >= 1 && levels <= 4 && dtype_ok(dtype);
 }
 
 extern "C" int cv_build_forward(const void *fmap1, const void *fmap2, void *const *pyramid, int N, int D, int H, int W1, int W2, int levels, int dtype,
@@ -469,18 +386,14 @@ extern "C" int cv_build_forward(const void *fmap1, const void *fmap2, void *cons
     if ((size_t)N * H == 0 || W1 == 0 || W2 == 0) return GPSGS_OK;
     if (!fmap1 || !fmap2 || (size_t)N * H > 65535u) return GPSGS_E_INVALID;
     PyrPtrs pp;
-    for (int l = 0; l < 4; l++) {
-        pp.p[l] = l < levels ? pyramid[l] : nullptr;
-        if (l < levels && !pp.p[l] && (W2 >> l) > 0) return GPSGS_E_INVALID;
-    }
+    if (!pyr_ptrs(pp, pyramid, levels, W2)) return GPSGS_E_INVALID;
     const dim3 grid((W2 + 63) / 64, (W1 + 64 * FWD_MT - 1) / (64 * FWD_MT), N * H);
     const float scale = 1.0f / sqrtf((float)D);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_cv_fwd<float>, grid, dim3(256), 0, s, (const float *)fmap1, (const float *)fmap2, pp, D, H, W1, W2, levels, scale);
-    else
-        hipLaunchKernelGGL(k_cv_fwd<__half>, grid, dim3(256), 0, s, (const __half *)fmap1, (const __half *)fmap2, pp, D, H, W1, W2, levels, scale);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    with_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::T T;
+        hipLaunchKernelGGL(k_cv_fwd<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T *)fmap1, (const T *)fmap2, pp, D, H, W1, W2, levels, scale);
+    });
+    return launched();
 }
 
 extern "C" int cv_build_backward(const void *fmap1, const void *fmap2, const void *const *grad_pyramid, void *grad_fmap1, void *grad_fmap2, int N, int D,
@@ -489,89 +402,21 @@ extern "C" int cv_build_backward(const void *fmap1, const void *fmap2, const voi
     if ((size_t)N * H == 0 || D == 0) return GPSGS_OK;
     if (!fmap1 || !fmap2 || (!grad_fmap1 && !grad_fmap2) || (size_t)N * H > 65535u) return GPSGS_E_INVALID;
     PyrConstPtrs gp;
-    for (int l = 0; l < 4; l++) gp.p[l] = l < levels ? grad_pyramid[l] : nullptr;
+    for (int l = 0; l < 4; l++) gp.p[l] = l < levels ? grad_pyramid[l] : nullptr;  // a NULL level is a zero gradient
     const float scale = 1.0f / sqrtf((float)D);
-    hipStream_t s = (hipStream_t)stream;
-    if (grad_fmap1 && W1 > 0) {
-        const dim3 grid((W1 + 63) / 64, (D + 64 * BWD_MT - 1) / (64 * BWD_MT), N * H);
-        if (dtype == 0)
-            hipLaunchKernelGGL((k_cv_bwd<float, true>), grid, dim3(256), 0, s, (const float *)fmap2, gp, (float *)grad_fmap1, D, H, W1, W2, levels, scale);
-        else
-            hipLaunchKernelGGL((k_cv_bwd<__half, true>), grid, dim3(256), 0, s, (const __half *)fmap2, gp, (__half *)grad_fmap1, D, H, W1, W2, levels, scale);
-    }
-    if (grad_fmap2 && W2 > 0) {
-        const dim3 grid((W2 + 63) / 64, (D + 64 * BWD_MT - 1) / (64 * BWD_MT), N * H);
-        if (dtype == 0)
-            hipLaunchKernelGGL((k_cv_bwd<float, false>), grid, dim3(256), 0, s, (const float *)fmap1, gp, (float *)grad_fmap2, D, H, W1, W2, levels, scale);
-        else
-            hipLaunchKernelGGL((k_cv_bwd<__half, false>), grid, dim3(256), 0, s, (const __half *)fmap1, gp, (__half *)grad_fmap2, D, H, W1, W2, levels, scale);
-    }
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
-}
-
-// N * H1 * W1 (non-negative ints) where an int holds it -- the lookup kernels index the (n, y, x) rows in int -- else -1; no intermediate product overflows
-static long long lookup_rows(int N, int H1, int W1) {
-    const long long a = (long long)N * H1;  // < 2^62
-    if (a == 0 || W1 == 0) return 0;
-    if (a > 0x7fffffffLL) return -1;
-    const long long t = a * W1;  // < 2^62
-    return t > 0x7fffffffLL ? -1 : t;
-}
-
-// 2 * radius + 1 must fit an int
-static bool lookup_radius_ok(int radius) { return radius >= 0 && radius <= 0x3fffffff; }
-
-extern "C" int cs_lookup_forward(const void *const *pyramid, const float *coords, void *out, int N, int H1, int W1, int W2, int levels, int radius,
-                                 int dtype, void *stream) {
-    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || !lookup_radius_ok(radius) || !pyramid) return GPSGS_E_INVALID;
-    const long long total = lookup_rows(N, H1, W1);
-    if (total == 0) return GPSGS_OK;
-    if (!coords || !out || total < 0) return GPSGS_E_INVALID;
-    PyrConstPtrs pp;
-    for (int l = 0; l < 4; l++) {
-        pp.p[l] = l < levels ? pyramid[l] : nullptr;
-        if (l < levels && !pp.p[l] && (W2 >> l) > 0) return GPSGS_E_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_lookup_fwd<float>, grid, dim3(256), 0, s, pp, coords, (float *)out, (int)total, H1, W1, W2, levels, radius);
-    else
-        hipLaunchKernelGGL(k_lookup_fwd<__half>, grid, dim3(256), 0, s, pp, coords, (__half *)out, (int)total, H1, W1, W2, levels, radius);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
-}
-
-extern "C" int cs_lookup_backward(const float *coords, const void *grad_out, void *const *grad_pyramid, int N, int H1, int W1, int W2, int levels,
-                                  int radius, int dtype, void *stream) {
-    if (!dims_ok(N, 0, H1, W1, W2, levels, dtype) || !lookup_radius_ok(radius) || !grad_pyramid) return GPSGS_E_INVALID;
-    const long long rows = lookup_rows(N, H1, W1);
-    if (rows == 0 || W2 == 0) return GPSGS_OK;
-    if (!coords || !grad_out || rows < 0) return GPSGS_E_INVALID;
-    const size_t total = (size_t)rows * W2;  // < 2^62
-    const size_t blocks = (total + 255) / 256;  // one thread per level-0 element in blocks of 256
-    if (blocks > 0x7fffffffULL) return GPSGS_E_INVALID;  // more than a grid's x holds: refused, not truncated
-    PyrPtrs pp;
-    for (int l = 0; l < 4; l++) {
-        pp.p[l] = l < levels ? grad_pyramid[l] : nullptr;
-        if (l < levels && !pp.p[l] && (W2 >> l) > 0) return GPSGS_E_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_lookup_bwd<float>, grid, dim3(256), 0, s, coords, (const float *)grad_out, pp, total, H1, W1, W2, levels, radius);
-    else
-        hipLaunchKernelGGL(k_lookup_bwd<__half>, grid, dim3(256), 0, s, coords, (const __half *)grad_out, pp, total, H1, W1, W2, levels, radius);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
-}
-
-// One thread per element in blocks of 256: does the block count of a * b * c * d elements (non-negative ints) fit a grid's x (<= 0x7fffffff)?
-static bool blocks_fit(int a, int b, int c, int d) {
-    const unsigned long long cap = 0x7fffffffULL * 256;
-    unsigned long long n = (unsigned long long)a * (unsigned long long)b;  // < 2^62
-    if (n > cap) return false;
-    n *= (unsigned long long)c;  // < 2^39 * 2^31
-    if (n > cap) return false;
-    return d == 0 || n <= cap / (unsigned long long)d;
+    with_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::T T;
+        hipStream_t s = (hipStream_t)stream;
+        if (grad_fmap1 && W1 > 0) {
+            const dim3 grid((W1 + 63) / 64, (D + 64 * BWD_MT - 1) / (64 * BWD_MT), N * H);
+            hipLaunchKernelGGL((k_cv_bwd<T, true>), grid, dim3(256), 0, s, (const T *)fmap2, gp, (T *)grad_fmap1, D, H, W1, W2, levels, scale);
+        }
+        if (grad_fmap2 && W2 > 0) {
+            const dim3 grid((W2 + 63) / 64, (D + 64 * BWD_MT - 1) / (64 * BWD_MT), N * H);
+            hipLaunchKernelGGL((k_cv_bwd<T, false>), grid, dim3(256), 0, s, (const T *)fmap1, gp, (T *)grad_fmap2, D, H, W1, W2, levels, scale);
+        }
+    });
+    return launched();
 }
 
 // the kernels form H * factor, W * factor and (backward) W + 63 in int
@@ -584,8 +429,8 @@ extern "C" int cu_upsample_forward(const float *flow, const float *mask, float *
     if ((size_t)N * H == 0 || W == 0) return GPSGS_OK;
     if (!flow || !mask || !out || !fine_dims_fit(H, W, factor) || !blocks_fit(N, H, factor * factor, W)) return GPSGS_E_INVALID;
     const size_t total = (size_t)N * H * factor * W * factor;
-    hipLaunchKernelGGL(k_up_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flow, mask, out, N, C, H, W, factor);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    hipLaunchKernelGGL(k_up_fwd, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, flow, mask, out, N, C, H, W, factor);
+    return launched();
 }
 
 extern "C" size_t cu_upsample_scratch_bytes(int N, int C, int H, int W) {
@@ -605,7 +450,7 @@ extern "C" int cu_upsample_backward(const float *flow, const float *mask, const 
     hipLaunchKernelGGL(k_up_bwd_cells, dim3((W + 63) / 64, H, N), dim3(256), 0, s, flow, mask, grad_out, grad_mask, S, C, H, W, factor);
     if (grad_flow) {
         const size_t tf = total * C;
-        hipLaunchKernelGGL(k_up_bwd_flow, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, s, S, grad_flow, N, C, H, W, factor);
+        hipLaunchKernelGGL(k_up_bwd_flow, dim3((unsigned)cdiv(tf, 256)), dim3(256), 0, s, S, grad_flow, N, C, H, W, factor);
     }
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }

@@ -17,7 +17,7 @@
 //                dL/dpred = gL1 * (sign(x1 - x2) / N) + gSSIM * ((F*M1 + 2 x1 F*M2 + x2 F*M3) / N).
 // HBM traffic: forward reads 8 B and writes 12 B per element, backward reads 20 B and writes 4 B -- against roughly 30
 // full-tensor passes in the eager version.
-#include "gsr_common.h"
+#include "op_common.h"
 
 namespace {
 
@@ -266,7 +266,7 @@ extern "C" int fl_l1_ssim_forward(const float *pred, const float *gt, int planes
     hipLaunchKernelGGL(k_loss_fwd, grid, dim3(256), 0, s, pred, gt, H, W, make_window(), m1, m2, m3, (float2 *)scratch);
     const int n = (int)(grid.x * grid.y * grid.z);
     hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, s, (const float2 *)scratch, n, 1.0 / ((double)planes * H * W), out2);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 extern "C" int fl_l1_ssim_backward(const float *pred, const float *gt, const float *m1, const float *m2, const float *m3, int planes, int H,
@@ -278,5 +278,5 @@ extern "C" int fl_l1_ssim_backward(const float *pred, const float *gt, const flo
     const dim3 grid((W + TS - 1) / TS, (H + TS - 1) / TS, planes);
     hipLaunchKernelGGL(k_loss_bwd, grid, dim3(256), 0, (hipStream_t)stream, pred, gt, m1, m2, m3, H, W, make_window(), grad_out2,
                        (float)(1.0 / ((double)planes * H * W)), d_pred);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }

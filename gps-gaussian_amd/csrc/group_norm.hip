@@ -26,53 +26,15 @@
 // INNER sign, recomputed from x, mean, rstd, gamma, beta with the forward's own expression GN_Y (same bits as the forward stored, so no normalised
 // activation is kept); the GroupNorm backward then runs on dy inside the same two kernels.  The masks are ATen's threshold_backward (v <= 0 -> +0.0f),
 // the sums keep their order: the result is bit for bit what relu_ / add / relu around the EP_NONE kernels give.
-#include <hip/hip_fp16.h>
-
 #include <type_traits>
 
-#include "gsr_common.h"
+#include "op_common.h"
 
 namespace {
 
 constexpr int GN_CHUNK = 8192;               // elements per workgroup
 constexpr int GN_THREADS = 256;              // 4 waves, one per SIMD
 constexpr int GN_PT = GN_CHUNK / GN_THREADS;  // 32 elements per thread, all in registers
-
-// x / dx in their storage type: DT 0 = fp32 (4 elements per 16 bytes), 1 = fp16 (8)
-template <int DT> struct XT;
-template <> struct XT<0> {
-    typedef float T;
-    static constexpr int V = 4;
-    static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
-        const float4 f = *reinterpret_cast<const float4 *>(p);
-        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-    static __device__ __forceinline__ float load1(const T *p) { return *p; }
-    static __device__ __forceinline__ void store1(T *p, float v) { *p = v; }
-};
-template <> struct XT<1> {
-    typedef __half T;
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
-        const uint4 u = *reinterpret_cast<const uint4 *>(p);
-        const __half2 *h = reinterpret_cast<const __half2 *>(&u);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float2 f = __half22float2(h[q]);
-            v[2 * q] = f.x; v[2 * q + 1] = f.y;
-        }
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[8]) {  // one rounding per element
-        uint4 u;
-        __half2 *h = reinterpret_cast<__half2 *>(&u);
-#pragma unroll
-        for (int q = 0; q < 4; q++) h[q] = __floats2half2_rn(v[2 * q], v[2 * q + 1]);
-        *reinterpret_cast<uint4 *>(p) = u;
-    }
-    static __device__ __forceinline__ float load1(const T *p) { return __half2float(*p); }
-    static __device__ __forceinline__ void store1(T *p, float v) { *p = __float2half(v); }
-};
 
 // V consecutive fp32 (y, dy) at an element index that is a multiple of V
 template <int V> __device__ __forceinline__ void load_f32(const float *p, float (&v)[V]) {
@@ -145,8 +107,8 @@ __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *red /*[4]
 }
 
 template <int DT>
-__global__ __launch_bounds__(GN_THREADS) void k_gn_moments(const typename XT<DT>::T *__restrict__ x, int L, int chunks, float2 *__restrict__ partial) {
-    constexpr int V = XT<DT>::V, NV = GN_PT / V;
+__global__ __launch_bounds__(GN_THREADS) void k_gn_moments(const typename Storage<DT>::T *__restrict__ x, int L, int chunks, float2 *__restrict__ partial) {
+    constexpr int V = Storage<DT>::V, NV = GN_PT / V;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
     const unsigned row = blockIdx.x / (unsigned)chunks, ck = blockIdx.x - row * (unsigned)chunks;
@@ -155,11 +117,11 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_moments(const typename XT<DT>
     float v[NV][V], ev = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; j++)
-        if (j * GN_THREADS + tid < s.nvec) XT<DT>::load(x + s.v0 + (size_t)(j * GN_THREADS + tid) * V, v[j]);
+        if (j * GN_THREADS + tid < s.nvec) Storage<DT>::load(x + s.v0 + (size_t)(j * GN_THREADS + tid) * V, v[j]);
     size_t ei;
     const bool edge = edge_index(s, tid, ei);
-    if (edge) ev = XT<DT>::load1(x + ei);
-    const float x0 = XT<DT>::load1(x + b);  // the shift: sums of x - x0 keep their digits when |mean| >> spread
+    if (edge) ev = Storage<DT>::load1(x + ei);
+    const float x0 = Storage<DT>::load1(x + b);  // the shift: sums of x - x0 keep their digits when |mean| >> spread
     float a = edge ? ev - x0 : 0.f;
 #pragma unroll
     for (int j = 0; j < NV; j++)
@@ -181,11 +143,11 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_moments(const typename XT<DT>
 
 // res: the residual of EP_RELU_ADD_RELU (not read otherwise)
 template <int DT, int EP>
-__global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ gamma,
+__global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename Storage<DT>::T *__restrict__ x, const float *__restrict__ gamma,
                                                          const float *__restrict__ beta, const float2 *__restrict__ partial, int L, int chunks, int HW,
                                                          int cpg, int G, float eps, float *__restrict__ y, float *__restrict__ mean_out,
                                                          float *__restrict__ rstd_out, const float *__restrict__ res) {
-    constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr int V = Storage<DT>::V, NV = GN_PT / V;
     constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
@@ -195,10 +157,10 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::
     float v[NV][V], ev = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; j++)
-        if (j * GN_THREADS + tid < s.nvec) XT<DT>::load(x + s.v0 + (size_t)(j * GN_THREADS + tid) * V, v[j]);
+        if (j * GN_THREADS + tid < s.nvec) Storage<DT>::load(x + s.v0 + (size_t)(j * GN_THREADS + tid) * V, v[j]);
     size_t ei;
     const bool edge = edge_index(s, tid, ei);
-    if (edge) ev = XT<DT>::load1(x + ei);
+    if (edge) ev = Storage<DT>::load1(x + ei);
     float rv[RES ? NV : 1][V], er = 0.f;  // the residual's loads are in flight with x's, over the combine below
     if constexpr (RES) {
 #pragma unroll
@@ -260,12 +222,12 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_apply(const typename XT<DT>::
 // EP != EP_NONE: `dy` is the gradient of the epilogue's output; it is masked here, element by element, to the gradient of y (see the top of the file).
 // out: the forward's output, read by EP_RELU_ADD_RELU only.
 template <int DT, int EP>
-__global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ dy,
+__global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename Storage<DT>::T *__restrict__ x, const float *__restrict__ dy,
                                                             const float *__restrict__ mean, int HW, int chunks, int C, int cpg, int G,
                                                             float2 *__restrict__ partial, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, const float *__restrict__ rstd,
                                                             const float *__restrict__ out) {
-    constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr int V = Storage<DT>::V, NV = GN_PT / V;
     constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
@@ -286,7 +248,7 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT
     for (int j = 0; j < NV; j++) {
         const int vi = j * GN_THREADS + tid;
         if (vi < s.nvec) {
-            XT<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
+            Storage<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
             load_f32<V>(dy + s.v0 + (size_t)vi * V, gv[j]);
             if constexpr (RES) load_f32<V>(out + s.v0 + (size_t)vi * V, ov[j]);
         }
@@ -311,12 +273,12 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT
     if (edge_index(s, tid, ei)) {
         float g = dy[ei];
         if constexpr (RES) g = mask_f(out[ei], g);
-        if constexpr (EP != EP_NONE) g = mask_f(GN_Y(XT<DT>::load1(x + ei), mu, rs, gm, bt), g);
+        if constexpr (EP != EP_NONE) g = mask_f(GN_Y(Storage<DT>::load1(x + ei), mu, rs, gm, bt), g);
         if constexpr (EP == EP_NONE) {
             s1 += g;
-            s2 += g * (XT<DT>::load1(x + ei) - mu);
+            s2 += g * (Storage<DT>::load1(x + ei) - mu);
         } else {
-            gn_acc_fused(s1, s2, g, XT<DT>::load1(x + ei) - mu);
+            gn_acc_fused(s1, s2, g, Storage<DT>::load1(x + ei) - mu);
         }
     }
     const float2 t = block_sum2(s1, s2, red);
@@ -326,13 +288,13 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_sums(const typename XT<DT
 // gchunks = chunks (one workgroup per chunk, dx and / or dres written) or 1 (neither wanted: one workgroup per plane, which only stores the plane's
 // sums).  dres (EP_RELU_ADD_RELU only; NULL = not wanted) receives the outer-masked gradient.
 template <int DT, int EP>
-__global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<DT>::T *__restrict__ x, const float *__restrict__ dy,
+__global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename Storage<DT>::T *__restrict__ x, const float *__restrict__ dy,
                                                              const float *__restrict__ gamma, const float *__restrict__ mean,
                                                              const float *__restrict__ rstd, const float2 *__restrict__ partial, int HW, int chunks,
-                                                             int gchunks, int C, int cpg, int G, typename XT<DT>::T *__restrict__ dx,
+                                                             int gchunks, int C, int cpg, int G, typename Storage<DT>::T *__restrict__ dx,
                                                              float2 *__restrict__ sums, const float *__restrict__ beta,
                                                              const float *__restrict__ out, float *__restrict__ dres) {
-    constexpr int V = XT<DT>::V, NV = GN_PT / V;
+    constexpr int V = Storage<DT>::V, NV = GN_PT / V;
     constexpr bool RES = EP == EP_RELU_ADD_RELU;
     __shared__ float2 red[4];
     const int tid = threadIdx.x;
@@ -357,7 +319,7 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
     for (int j = 0; j < NV; j++) {
         const int vi = j * GN_THREADS + tid;
         if (vi < s.nvec) {
-            XT<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
+            Storage<DT>::load(x + s.v0 + (size_t)vi * V, xv[j]);
             load_f32<V>(dy + s.v0 + (size_t)vi * V, gv[j]);
             if constexpr (RES) load_f32<V>(out + s.v0 + (size_t)vi * V, ov[j]);
         }
@@ -365,7 +327,7 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
     size_t ei;
     const bool edge = edge_index(s, tid, ei);
     if (edge) {
-        ex = XT<DT>::load1(x + ei);
+        ex = Storage<DT>::load1(x + ei);
         eg = dy[ei];
         if constexpr (RES) eo = out[ei];
     }
@@ -413,12 +375,12 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_bwd_apply(const typename XT<D
                 if constexpr (EP != EP_NONE) gv[j][k] = mask_f(GN_Y(xv[j][k], mu, rs, gm, bt), gv[j][k]);
                 o[k] = GN_DX(kd, gv[j][k], c1, xv[j][k] - mu, c2);
             }
-            XT<DT>::store(dx + s.v0 + (size_t)vi * V, o);
+            Storage<DT>::store(dx + s.v0 + (size_t)vi * V, o);
         }
     }
     if (edge) {
         if constexpr (EP != EP_NONE) eg = mask_f(GN_Y(ex, mu, rs, gm, bt), eg);
-        XT<DT>::store1(dx + ei, GN_DX(kd, eg, c1, ex - mu, c2));
+        Storage<DT>::store1(dx + ei, GN_DX(kd, eg, c1, ex - mu, c2));
     }
 }
 
@@ -436,12 +398,9 @@ __global__ __launch_bounds__(GN_THREADS) void k_gn_param_grad(const float2 *__re
     dbeta[c] = db;
 }
 
-inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // common argument checks: 0 = go on, 1 = nothing to do, < 0 = refused
 int gn_check(int dtype, int N, int C, int G, int HW) {
-    if (N < 0 || C < 0 || HW < 0 || G <= 0 || (dtype != 0 && dtype != 1) || C % G != 0) return GPSGS_E_INVALID;
+    if (N < 0 || C < 0 || HW < 0 || G <= 0 || !dtype_ok(dtype) || C % G != 0) return GPSGS_E_INVALID;
     if ((size_t)N * C * HW == 0) return 1;
     if ((size_t)(C / G) * HW > 0x7fffffffu || (size_t)N * C * cdiv(HW, GN_CHUNK) > 0x7fffffffu ||
         (size_t)N * G * cdiv((size_t)(C / G) * HW, GN_CHUNK) > 0x7fffffffu)
@@ -464,7 +423,7 @@ namespace {
 template <int DT, int EP>
 void launch_forward(const void *x, const float *gamma, const float *beta, const float *res, int N, int C, int G, int HW, float eps, float *out,
                     float *mean, float *rstd, void *scratch, hipStream_t s) {
-    typedef const typename XT<DT>::T *XP;
+    typedef const typename Storage<DT>::T *XP;
     const int cpg = C / G, L = cpg * HW, chunks = (int)cdiv(L, GN_CHUNK);
     const dim3 grid((unsigned)((size_t)N * G * chunks)), block(GN_THREADS);
     float2 *partial = (float2 *)scratch + (size_t)N * C;
@@ -476,7 +435,7 @@ void launch_forward(const void *x, const float *gamma, const float *beta, const 
 template <int DT, int EP>
 void launch_backward(const void *x, const float *dout, const float *out, const float *gamma, const float *beta, const float *mean, const float *rstd,
                      int N, int C, int G, int HW, void *dx, float *dres, float *dgamma, float *dbeta, void *scratch, hipStream_t s) {
-    typedef typename XT<DT>::T X;
+    typedef typename Storage<DT>::T X;
     const int cpg = C / G, chunks = (int)cdiv(HW, GN_CHUNK), gchunks = dx || dres ? chunks : 1;
     const dim3 block(GN_THREADS);
     float2 *sums = (float2 *)scratch, *partial = sums + (size_t)N * C;
@@ -491,18 +450,14 @@ void launch_backward(const void *x, const float *dout, const float *out, const f
 
 // f(dt, ep) with the run-time dtype and epilogue as compile-time constants: the six <DT, EP> instantiations of whatever f launches
 template <class F> void dispatch(int dtype, int ep, F f) {
-    auto with_dt = [&](auto dt) {
+    with_dtype(dtype, [&](auto dt) {
         if (ep == EP_NONE)
             f(dt, std::integral_constant<int, EP_NONE>());
         else if (ep == EP_RELU)
             f(dt, std::integral_constant<int, EP_RELU>());
         else
             f(dt, std::integral_constant<int, EP_RELU_ADD_RELU>());
-    };
-    if (dtype == 0)
-        with_dt(std::integral_constant<int, 0>());
-    else
-        with_dt(std::integral_constant<int, 1>());
+    });
 }
 
 // gn_forward (EP_NONE, no residual) and gne_forward (EP_RELU, or EP_RELU_ADD_RELU with a residual)
@@ -511,11 +466,11 @@ int forward(int ep, const void *x, int dtype, const float *gamma, const float *b
     const int rc = gn_check(dtype, N, C, G, HW);
     if (rc != 0) return rc < 0 ? rc : GPSGS_OK;
     if (!x || !gamma || !beta || !out || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
-    if (!aligned16(x) || !aligned16(out) || !aligned16(residual) || ((uintptr_t)scratch & 7) != 0) return GPSGS_E_INVALID;
+    if (!aligned(x, 16) || !aligned(out, 16) || !aligned(residual, 16) || !aligned(scratch, 8)) return GPSGS_E_INVALID;
     dispatch(dtype, ep, [&](auto dt, auto e) {
-        launch_forward<decltype(dt)::value, decltype(e)::value>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, (hipStream_t)stream);
+        launch_forward<decltype(dt)::DT, decltype(e)::value>(x, gamma, beta, residual, N, C, G, HW, eps, out, mean, rstd, scratch, (hipStream_t)stream);
     });
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 // gn_backward (EP_NONE: no beta, out or dres) and gne_backward (EP_RELU, or EP_RELU_ADD_RELU with the forward's out).  An invalid argument is
@@ -528,14 +483,14 @@ int backward(int ep, const void *x, int dtype, const float *dout, const float *o
     if (dres && !out) return GPSGS_E_INVALID;  // only the residual form has a residual to differentiate
     if (rc != 0) return GPSGS_OK;
     if (!x || !dout || !gamma || (ep != EP_NONE && !beta) || !mean || !rstd || !scratch) return GPSGS_E_INVALID;
-    if (!aligned16(x) || !aligned16(dout) || !aligned16(out) || !aligned16(dx) || !aligned16(dres) || ((uintptr_t)scratch & 7) != 0)
+    if (!aligned(x, 16) || !aligned(dout, 16) || !aligned(out, 16) || !aligned(dx, 16) || !aligned(dres, 16) || !aligned(scratch, 8))
         return GPSGS_E_INVALID;
     if (!dx && !dres && !dgamma) return GPSGS_OK;
     dispatch(dtype, ep, [&](auto dt, auto e) {
-        launch_backward<decltype(dt)::value, decltype(e)::value>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch,
+        launch_backward<decltype(dt)::DT, decltype(e)::value>(x, dout, out, gamma, beta, mean, rstd, N, C, G, HW, dx, dres, dgamma, dbeta, scratch,
                                                                  (hipStream_t)stream);
     });
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 }  // namespace

@@ -15,7 +15,7 @@
 //   k_pack_bwd     per pixel: planar gradients of the maps from the packed row gradients (zero where invalid): the
 //                  fill and the scatter are one pass, no memset, no atomics
 // HBM-bound: 57 B read per pixel + 56 B written per valid pixel.
-#include "gsr_common.h"
+#include "op_common.h"
 
 #pragma clang fp contract(off)  // rgb = img * 0.5 + 0.5 must round like torch's separate mul and add
 
@@ -157,7 +157,7 @@ extern "C" int gsr_pack_views(int B, int n_views, int S2, const GsrStrided *vali
     if (B < 0 || n_views < 1 || n_views > MAXV || S2 < 0) return GPSGS_E_INVALID;
     if (!sample_offsets) return GPSGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || S2 == 0) return hipMemsetAsync(sample_offsets, 0, (size_t)(B + 1) * 4, s) == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    if (B == 0 || S2 == 0) return launched(hipMemsetAsync(sample_offsets, 0, (size_t)(B + 1) * 4, s));
     if (!valid || !xyz || !img || !rot || !scale || !opacity || !out_xyz || !out_rgb || !out_rot || !out_scale || !out_opacity ||
         !row_of_pixel || !scratch)
         return GPSGS_E_INVALID;
@@ -171,7 +171,7 @@ extern "C" int gsr_pack_views(int B, int n_views, int S2, const GsrStrided *vali
     hipLaunchKernelGGL(k_pack_count, grid, dim3(PB), 0, s, a, scratch);
     hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, s, scratch, B * n_views * a.nblk, n_views * a.nblk, B, sample_offsets);
     hipLaunchKernelGGL(k_pack_gather, grid, dim3(PB), 0, s, a, scratch, out_xyz, out_rgb, out_rot, out_scale, out_opacity, row_of_pixel);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 extern "C" int gsr_pack_views_backward(int B, int n_views, int S2, const uint32_t *row_of_pixel, const float *g_xyz, const float *g_rgb,
@@ -193,5 +193,5 @@ extern "C" int gsr_pack_views_backward(int B, int n_views, int S2, const uint32_
     }
     hipLaunchKernelGGL(k_pack_bwd, dim3((S2 + 255) / 256, n_views, B), dim3(256), 0, (hipStream_t)stream, a, row_of_pixel, g_xyz, g_rgb, g_rot,
                        g_scale, g_opacity);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }

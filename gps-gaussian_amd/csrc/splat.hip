@@ -13,6 +13,7 @@
 //   resolve  one lane per target pixel: tag 0 leaves the pixel alone, otherwise the winner's z and colour are gathered
 // Deterministic: the reference's atomic_max on the depth followed by a separate, non-atomic colour write can keep the colour of the farther of two
 // points landing on a pixel at the same time; here the colour always belongs to the key that won.
+#include "op_common.h"
 #include "unproject_common.h"
 
 #pragma clang fp contract(off)
@@ -124,8 +125,6 @@ __global__ __launch_bounds__(TPB) void k_f2r_resolve(F2RViews a, const uint64_t 
 #pragma unroll
     for (int k = 0; k < 3; k++) img_pred[((size_t)b * 3 + k) * R2 + pix] = rgb[k];
 }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH; }
 
 }  // namespace
 

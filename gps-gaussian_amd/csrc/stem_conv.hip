@@ -20,9 +20,7 @@
 // No atomics; every sum has a fixed order: the same bits on every run.  Element offsets into x, y, dy, dx are 64-bit.
 // Guarded global loads are written as an unconditional load from a clamped (always valid) address followed by a select: a branch around each load
 // makes the compiler wait for every one of them in turn (measured: the fp16 backward ran 3x slower that way).
-#include <hip/hip_fp16.h>
-
-#include "gsr_common.h"
+#include "op_common.h"
 
 namespace {
 
@@ -65,26 +63,6 @@ __device__ __forceinline__ void stage_patch(float *xs, const float *__restrict__
     }
 }
 
-template <int DT> struct YT;  // y / dy in their storage type: 0 = fp32, 1 = fp16
-template <> struct YT<0> {
-    typedef float T;
-    static __device__ __forceinline__ float load1(const T *p) { return *p; }
-    static __device__ __forceinline__ void store1(T *p, float v) { *p = v; }
-    static __device__ __forceinline__ void store4(T *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct YT<1> {
-    typedef __half T;
-    static __device__ __forceinline__ float load1(const T *p) { return __half2float(*p); }
-    static __device__ __forceinline__ void store1(T *p, float v) { *p = __float2half_rn(v); }
-    static __device__ __forceinline__ void store4(T *p, const float (&v)[4]) {
-        uint2 u;
-        __half2 *h = reinterpret_cast<__half2 *>(&u);
-        h[0] = __floats2half2_rn(v[0], v[1]);
-        h[1] = __floats2half2_rn(v[2], v[3]);
-        *reinterpret_cast<uint2 *>(p) = u;
-    }
-};
-
 struct Dims {
     int N, C_out, H, W, Ho, Wo, pad, tiles_x, tiles_y;
 };
@@ -93,9 +71,9 @@ struct Dims {
 // loop, 250 registers and one wave per SIMD for CIN = 3)
 template <int CIN, int K, int S, int DT>
 __global__ __launch_bounds__(SC_THREADS, 4) void k_sc_fwd(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
-                                                       typename YT<DT>::T *__restrict__ y, Dims d) {
+                                                       typename Storage<DT>::T *__restrict__ y, Dims d) {
     typedef Patch<CIN, K, S> P;
-    typedef typename YT<DT>::T Y;
+    typedef typename Storage<DT>::T Y;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     const unsigned b = blockIdx.x, tx = b % (unsigned)d.tiles_x, ty = (b / (unsigned)d.tiles_x) % (unsigned)d.tiles_y;
@@ -149,11 +127,11 @@ __global__ __launch_bounds__(SC_THREADS, 4) void k_sc_fwd(const float *__restric
                 const size_t o = ((n * d.C_out + co0 + c) * (size_t)d.Ho + oy) * (size_t)d.Wo + ox;
                 Y *p = y + o;
                 if (ox + SC_PX <= d.Wo && ((uintptr_t)p & (SC_PX * sizeof(Y) - 1)) == 0) {
-                    YT<DT>::store4(p, acc[c]);
+                    Storage<DT>::store4(p, acc[c]);
                 } else {
 #pragma unroll
                     for (int j = 0; j < SC_PX; j++)
-                        if (ox + j < d.Wo) YT<DT>::store1(p + j, acc[c][j]);
+                        if (ox + j < d.Wo) Storage<DT>::store1(p + j, acc[c][j]);
                 }
             }
         }
@@ -166,9 +144,9 @@ __global__ __launch_bounds__(SC_THREADS, 4) void k_sc_fwd(const float *__restric
 // lanes of a wave read consecutive dy columns.
 constexpr int SC_IR = 4;
 template <int CIN, int K, int S, int DT>
-__global__ __launch_bounds__(S * S * 64) void k_sc_bwd_input(const typename YT<DT>::T *__restrict__ dy, const float *__restrict__ w,
+__global__ __launch_bounds__(S * S * 64) void k_sc_bwd_input(const typename Storage<DT>::T *__restrict__ dy, const float *__restrict__ w,
                                                              float *__restrict__ dx, Dims d, int bx, int by) {
-    typedef typename YT<DT>::T Y;
+    typedef typename Storage<DT>::T Y;
     constexpr int T = (K + S - 1) / S;  // taps per axis at most
     constexpr int R = SC_IR, M = R + T - 1;
     const unsigned b = blockIdx.x, ibx = b % (unsigned)bx, iby = (b / (unsigned)bx) % (unsigned)by;
@@ -206,7 +184,7 @@ __global__ __launch_bounds__(S * S * 64) void k_sc_bwd_input(const typename YT<D
 #pragma unroll
         for (int m = 0; m < M; m++)
 #pragma unroll
-            for (int c = 0; c < T; c++) g[m][c] = ok[m][c] ? YT<DT>::load1(&raw[m][c]) : 0.f;
+            for (int c = 0; c < T; c++) g[m][c] = ok[m][c] ? Storage<DT>::load1(&raw[m][c]) : 0.f;
 #pragma unroll
         for (int a = 0; a < T; a++)
 #pragma unroll
@@ -229,7 +207,7 @@ __global__ __launch_bounds__(S * S * 64) void k_sc_bwd_input(const typename YT<D
 
 // partial[tile][co * (CIN*K*K) + tap] for co < C_out, then partial[tile][C_out * CIN*K*K + co] = the tile's sum of dy[co]
 template <int CIN, int K, int S, int DT>
-__global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_weight(const float *__restrict__ x, const typename YT<DT>::T *__restrict__ dy,
+__global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_weight(const float *__restrict__ x, const typename Storage<DT>::T *__restrict__ dy,
                                                               float *__restrict__ partial, Dims d) {
     typedef Patch<CIN, K, S> P;
     constexpr int TAPS = CIN * K * K, NSL = SC_THREADS / TAPS, NPIX = SC_TH * SC_TW;
@@ -255,12 +233,12 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_weight(const float *__res
         __syncthreads();  // the patch is staged (first round); the previous round's sums have been read
         {  // a thread stages NPIX / 256 pixels x 8 channels: every load issued before the first LDS store, zeros outside the output
             float g[NPIX / SC_THREADS][SC_CB];
-            typename YT<DT>::T raw[NPIX / SC_THREADS][SC_CB];  // unconditional loads from a clamped address, masked after
+            typename Storage<DT>::T raw[NPIX / SC_THREADS][SC_CB];  // unconditional loads from a clamped address, masked after
 #pragma unroll
             for (int q = 0; q < NPIX / SC_THREADS; q++) {
                 const int p = tid + q * SC_THREADS, py = p / SC_TW, px = p - py * SC_TW;
                 const bool in = py < ph && px < pw;
-                const typename YT<DT>::T *src = dy + (n * d.C_out + co0) * HoWo + (in ? (size_t)(oy0 + py) * d.Wo + (ox0 + px) : 0);
+                const typename Storage<DT>::T *src = dy + (n * d.C_out + co0) * HoWo + (in ? (size_t)(oy0 + py) * d.Wo + (ox0 + px) : 0);
 #pragma unroll
                 for (int c = 0; c < SC_CB; c++) raw[q][c] = src[(size_t)c * HoWo];
             }
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_weight(const float *__res
                 const int p = tid + q * SC_THREADS, py = p / SC_TW, px = p - py * SC_TW;
                 const bool in = py < ph && px < pw;
 #pragma unroll
-                for (int c = 0; c < SC_CB; c++) g[q][c] = in ? YT<DT>::load1(&raw[q][c]) : 0.f;
+                for (int c = 0; c < SC_CB; c++) g[q][c] = in ? Storage<DT>::load1(&raw[q][c]) : 0.f;
             }
 #pragma unroll
             for (int q = 0; q < NPIX / SC_THREADS; q++) {
@@ -336,9 +314,6 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_reduce(const float *__res
     }
 }
 
-inline size_t cdiv(size_t a, size_t b) { return (a + b - 1) / b; }
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 bool supported(int C_in, int C_out, int K, int stride, int pad) {
     return (C_in == 1 || C_in == 3) && K == 5 && stride == 2 && pad == 2 && C_out >= 8 && C_out <= 64 && C_out % 8 == 0;
 }
@@ -361,10 +336,10 @@ template <int CIN, int K, int S>
 void launch_fwd(const float *x, const float *w, const float *bias, void *y, int y_dtype, const Dims &d, hipStream_t s) {
     const dim3 grid((unsigned)((size_t)d.N * d.tiles_y * d.tiles_x)), block(SC_THREADS);
     const size_t lds = sizeof(float) * Patch<CIN, K, S>::ELEMS;
-    if (y_dtype == 0)
-        hipLaunchKernelGGL((k_sc_fwd<CIN, K, S, 0>), grid, block, lds, s, x, w, bias, (float *)y, d);
-    else
-        hipLaunchKernelGGL((k_sc_fwd<CIN, K, S, 1>), grid, block, lds, s, x, w, bias, (__half *)y, d);
+    with_dtype(y_dtype, [&](auto t) {
+        typedef decltype(t) Y;
+        hipLaunchKernelGGL((k_sc_fwd<CIN, K, S, Y::DT>), grid, block, lds, s, x, w, bias, (typename Y::T *)y, d);
+    });
 }
 
 template <int CIN, int K, int S>
@@ -373,18 +348,18 @@ void launch_bwd(const float *x, const float *w, const void *dy, int dy_dtype, co
     if (dx) {
         const int bx = (int)cdiv(d.W, 64 * S), by = (int)cdiv(d.H, S * SC_IR);
         const dim3 grid((unsigned)((size_t)d.N * CIN * by * bx)), block(S * S * 64);
-        if (dy_dtype == 0)
-            hipLaunchKernelGGL((k_sc_bwd_input<CIN, K, S, 0>), grid, block, 0, s, (const float *)dy, w, dx, d, bx, by);
-        else
-            hipLaunchKernelGGL((k_sc_bwd_input<CIN, K, S, 1>), grid, block, 0, s, (const __half *)dy, w, dx, d, bx, by);
+        with_dtype(dy_dtype, [&](auto t) {
+            typedef decltype(t) Y;
+            hipLaunchKernelGGL((k_sc_bwd_input<CIN, K, S, Y::DT>), grid, block, 0, s, (const typename Y::T *)dy, w, dx, d, bx, by);
+        });
     }
     if (dw) {
         const int tiles = d.N * d.tiles_y * d.tiles_x, MW = d.C_out * CIN * K * K, M = MW + d.C_out;
         const size_t lds = sizeof(float) * (Patch<CIN, K, S>::ELEMS + SC_CB * SC_TH * SC_TW);
-        if (dy_dtype == 0)
-            hipLaunchKernelGGL((k_sc_bwd_weight<CIN, K, S, 0>), dim3(tiles), dim3(SC_THREADS), lds, s, x, (const float *)dy, scratch, d);
-        else
-            hipLaunchKernelGGL((k_sc_bwd_weight<CIN, K, S, 1>), dim3(tiles), dim3(SC_THREADS), lds, s, x, (const __half *)dy, scratch, d);
+        with_dtype(dy_dtype, [&](auto t) {
+            typedef decltype(t) Y;
+            hipLaunchKernelGGL((k_sc_bwd_weight<CIN, K, S, Y::DT>), dim3(tiles), dim3(SC_THREADS), lds, s, x, (const typename Y::T *)dy, scratch, d);
+        });
         const unsigned jb = (unsigned)cdiv(M, SC_THREADS);
         const float *in = scratch;
         int parts = tiles;
@@ -422,7 +397,7 @@ extern "C" int sc_forward(const float *x, const float *w, const float *bias, int
                           void *y, int y_dtype, void *stream) {
     Dims d;
     if (!make_dims(N, C_in, C_out, H, W, K, stride, pad, d)) return GPSGS_E_INVALID;
-    if (y_dtype != 0 && y_dtype != 1) return GPSGS_E_INVALID;
+    if (!dtype_ok(y_dtype)) return GPSGS_E_INVALID;
     if (!x || !w || !bias || !y) return GPSGS_E_INVALID;
     if (!aligned(x, 16) || !aligned(y, 16) || !aligned(w, 4) || !aligned(bias, 4)) return GPSGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
@@ -430,14 +405,14 @@ extern "C" int sc_forward(const float *x, const float *w, const float *bias, int
         launch_fwd<1, 5, 2>(x, w, bias, y, y_dtype, d, s);
     else
         launch_fwd<3, 5, 2>(x, w, bias, y, y_dtype, d, s);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 extern "C" int sc_backward(const float *x, const float *w, const void *dy, int dy_dtype, int N, int C_in, int C_out, int H, int W, int K, int stride,
                            int pad, float *dx, float *dw, float *dbias, void *scratch, void *stream) {
     Dims d;
     if (!make_dims(N, C_in, C_out, H, W, K, stride, pad, d)) return GPSGS_E_INVALID;
-    if (dy_dtype != 0 && dy_dtype != 1) return GPSGS_E_INVALID;
+    if (!dtype_ok(dy_dtype)) return GPSGS_E_INVALID;
     if ((dw != nullptr) != (dbias != nullptr)) return GPSGS_E_INVALID;
     if (!x || !w || !dy || (dw && !scratch)) return GPSGS_E_INVALID;
     if (!aligned(x, 16) || !aligned(dy, 16) || !aligned(dx, 16) || !aligned(w, 4) || !aligned(dw, 4) || !aligned(dbias, 4) || !aligned(scratch, 16))
@@ -448,5 +423,5 @@ extern "C" int sc_backward(const float *x, const float *w, const void *dy, int d
         launch_bwd<1, 5, 2>(x, w, dy, dy_dtype, d, dx, dw, dbias, (float *)scratch, s);
     else
         launch_bwd<3, 5, 2>(x, w, dy, dy_dtype, d, dx, dw, dbias, (float *)scratch, s);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }

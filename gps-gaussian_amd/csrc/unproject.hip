@@ -8,6 +8,7 @@
 // Backward: d_flow = (g_depth - z^2 * g_xyz . R^T[ax, ay, 1]) * mask / Tf_x with ax = (u + 0.5 - cx) / fx.
 // HBM-bound: 8 B read + 17 B written per pixel forward.  Evaluated without FMA contraction in the reference's operation
 // order: depth and valid are bit-identical to torch's, xyz differs only by the summation order of the 3x3 product.
+#include "op_common.h"
 #include "unproject_common.h"
 
 #pragma clang fp contract(off)
@@ -93,7 +94,7 @@ extern "C" int up_unproject_forward(int B, int S, const float *flow, const float
         hipLaunchKernelGGL(k_unproject_fwd, dim3((S * S + 255) / 256, nb), dim3(256), 0, (hipStream_t)stream, a, (const float *)nullptr, flow + b0 * S2,
                            mask + (int64_t)b0 * mask_batch_stride, mask_batch_stride, depth + b0 * S2, xyz + b0 * S2 * 3, valid + b0 * S2);
     }
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 extern "C" int up_unproject_backward(int B, int S, const float *depth, const float *mask, int64_t mask_batch_stride, const float *ref_intr_host,
@@ -113,7 +114,7 @@ extern "C" int up_unproject_backward(int B, int S, const float *depth, const flo
                            g_xyz ? g_xyz + (int64_t)b0 * gx_batch_stride : nullptr, gx_batch_stride, gx_pixel_stride, gx_channel_stride,
                            d_flow + b0 * S2);
     }
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 // The same two entry points with the cameras in DEVICE memory: cams_dev[B][31] = {ref_intr 3x3, intr 3x3, extr rows 0..2 (3x4, row-major), Tf_x} per sample.
@@ -126,7 +127,7 @@ extern "C" int up_unproject_forward_dev(int B, int S, const float *flow, const f
     UnprojArgs a;
     a.B = B; a.S = S;
     hipLaunchKernelGGL(k_unproject_fwd, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, a, cams_dev, flow, mask, mask_batch_stride, depth, xyz, valid);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }
 
 extern "C" int up_unproject_backward_dev(int B, int S, const float *depth, const float *mask, int64_t mask_batch_stride, const float *cams_dev, const float *g_depth,
@@ -139,5 +140,5 @@ extern "C" int up_unproject_backward_dev(int B, int S, const float *depth, const
     a.B = B; a.S = S;
     hipLaunchKernelGGL(k_unproject_bwd, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, a, cams_dev, depth, mask, mask_batch_stride, g_depth, g_xyz,
                        gx_batch_stride, gx_pixel_stride, gx_channel_stride, d_flow);
-    return hipGetLastError() == hipSuccess ? GPSGS_OK : GPSGS_E_LAUNCH;
+    return launched();
 }

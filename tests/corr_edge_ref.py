@@ -1,5 +1,5 @@
-"""Shared references for the edge tests of the 1-D correlation sampler (csrc/corr_sampler.hip: k_cs_fwd, k_cs_bwd, k_cs_bwd4) and the fused
-multi-level lookup (csrc/corr_pyramid.hip: k_lookup_fwd, k_lookup_bwd).  TEST INFRASTRUCTURE ONLY: everything here runs on the CPU.
+"""Shared references for the edge tests of the 1-D correlation sampler (k_cs_fwd, k_cs_bwd, k_cs_bwd4) and the fused multi-level lookup
+(k_lookup_fwd, k_lookup_bwd), both in csrc/corr_sampler.hip.  TEST INFRASTRUCTURE ONLY: everything here runs on the CPU.
 
   * hat_lookup: the lookup written as a sum over the whole row with the hat weight max(0, 1 - |c / 2^l - r + k - j|), in fp64 torch.  There is no
     floor, no fractional part and no tap index in it, and its backward is torch autograd: it owes nothing to the kernels' arithmetic, to the C twin

@@ -1,5 +1,5 @@
-"""GPU (-m gpu): the 1-D correlation sampler (csrc/corr_sampler.hip: k_cs_fwd, k_cs_bwd, k_cs_bwd4) and the fused multi-level lookup
-(csrc/corr_pyramid.hip: k_lookup_fwd, k_lookup_bwd) at their edges.  References: the C twin, value for value (A, B, D, E, F); the fp64 hat function
+"""GPU (-m gpu): the 1-D correlation sampler (k_cs_fwd, k_cs_bwd, k_cs_bwd4) and the fused multi-level lookup (k_lookup_fwd, k_lookup_bwd), both
+in csrc/corr_sampler.hip, at their edges.  References: the C twin, value for value (A, B, D, E, F); the fp64 hat function
 within the derived bound 4 * 2^-24 * S (A, B; both in tests/corr_edge_ref.py, tied to each other and to the reference's grid_sample path by
 tests/test_corr_lookup_ref.py); and exact statements that owe nothing to either (C, G).  Coordinates: tests/corr_edge_ref.py special_coords --
 exact integers, one ulp either side, negative, half or wholly outside the row, far away.  Every shape is tiny; the file runs in a few seconds."""
@@ -309,6 +309,25 @@ def test_block_tails(nhw, dtype):
         assert R.same_values(out, _as(R.twin_lookup(pyr, c, r), dtype)), W2
         for l, (g, want) in enumerate(zip(grads, R.twin_lookup_backward(R.widths(W2, levels), c, gl, r))):
             assert R.same_values(g, _as(want, dtype)), (W2, l)
+
+
+# ---- D2. one level of the fused lookup IS the sampler ------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("r", [0, 4])
+@pytest.mark.parametrize("W2", [8, 7])
+def test_one_level_lookup_is_the_sampler(W2, r, dtype):
+    """cs_lookup_* with levels = 1 and cs_forward / cs_backward on the same volume, coordinates and grad_out give the same bits: the four kernels
+    share one sampling core (sample_row, tap_grad).  W2 = 8 takes k_cs_bwd4, W2 = 7 the scalar k_cs_bwd; 260 rows = one full block and a tail."""
+    N, H1, W1 = 1, 2, 130
+    sc = R.special_coords(W2, r, "D2")
+    c = sc.repeat(-(-N * H1 * W1 // sc.numel()))[:N * H1 * W1].reshape(N, 1, H1, W1)
+    vol = R.randn((N, H1, W1, W2), ("D2", W2, r), _half(dtype))
+    gout = R.randn((N, 2 * r + 1, H1, W1), ("D2-g", W2, r), _half(dtype))
+    out_s, gv_s = gpu_sampler(vol, c, gout, r, dtype)
+    out_l, (gv_l,) = gpu_lookup([vol], c, gout, r, dtype)
+    assert R.same_bits(out_l, out_s)
+    assert R.same_bits(gv_l, gv_s)
+    assert bool(out_s.any()) and bool(gv_s.any())
 
 
 # ---- E. zero fill and bounds, through the C-ABI -----------------------------------------------------------------------------------
