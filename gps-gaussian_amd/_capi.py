@@ -131,6 +131,11 @@ _GSR = {
     "gsr_pack_scratch_bytes": (sz, [i32, i32, i32]),
     "gsr_pack_views": (i32, [i32, i32, i32, sp, sp, sp, sp, sp, sp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gsr_pack_views_backward": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, pp, pp, pp, pp, pp, vp]),
+    "gsr_head_supported": (i32, [i32, i32, i32]),
+    "gsr_head_tile": (i32, []),
+    "gsr_head_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "gsr_head_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
+    "gsr_head_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
     "fl_scratch_bytes": (sz, [i32, i32, i32]),
     "fl_l1_ssim_forward": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "fl_l1_ssim_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),

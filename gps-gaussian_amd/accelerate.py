@@ -37,6 +37,13 @@ A fourth, `stemconv` (GPSGS_ACCELERATE=stemconv; its own tuple OPT_IN_CONV, neve
 `groupnorm` / `resblock` use and does only what was asked: `stemconv` alone leaves every norm an `nn.GroupNorm` (and ResidualBlock, which has no such
 layer, unwrapped); `groupnorm` or `resblock` alone leave `in_ds[0]` a plain `nn.Conv2d`.
 
+A fifth, `gshead` (GPSGS_ACCELERATE=gshead; its own tuple OPT_IN_HEAD, never implied by "all" or by the names above), wraps the constructor of
+lib/gs_parm_network.py's GSRegresser the same way: after the reference's `__init__` the wrapper runs `gshead.convert(self)`, which turns the
+ReLU -> Conv2d(32, 4 | 3 | 1, 1) -> nothing | Softplus | Sigmoid tail of `rot_head`, `scale_head` and `opacity_head` (:34-50) into one
+`FusedHeadConv` each on the kernels of csrc/gshead.hip, with nn.Identity in the ReLU's and the activation's slots.  That wrapper converts heads and
+nothing else; the encoder and block constructors GSRegresser calls are wrapped, or not, by the names above as before.  `GSRegresser.forward` (its
+`F.normalize` and `clamp_max` included) runs as it is.
+
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
 import importlib.abc
@@ -49,10 +56,11 @@ FEATURES = ("pack", "loss", "corr", "upsample", "unproject")
 OPT_IN = ("splat", "groupnorm")   # accepted by name only, never implied by "all"
 OPT_IN_FUSED = ("resblock",)      # likewise by name only; implies the groupnorm conversion and replaces ResidualBlock.forward (see above)
 OPT_IN_CONV = ("stemconv",)       # likewise by name only: the encoders' stem convolutions (see above)
+OPT_IN_HEAD = ("gshead",)         # likewise by name only: the ReLU -> 1x1 convolution -> activation tails of the Gaussian heads (see above)
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
-calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV}
+calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV + OPT_IN_HEAD}
 # calls that went THROUGH a replacement but were handed on to the reference's own function (a configuration the fused kernel does not implement):
 # counted, so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
 calls["loss_passthrough"] = 0
@@ -60,8 +68,10 @@ calls["unproject_passthrough"] = 0
 calls["groupnorm_passthrough"] = 0   # FusedGroupNorm forwards handed to nn.GroupNorm.forward (CPU, channels-last, bf16, ...: groupnorm.py)
 calls["resblock_passthrough"] = 0    # residual blocks without GroupNorm layers (norm_fn batch / instance / none): the reference's own forward
 calls["stemconv_passthrough"] = 0    # FusedStemConv2d forwards handed to nn.Conv2d.forward (CPU, channels-last, bf16 autocast, ...: stemconv.py)
+calls["gshead_passthrough"] = 0      # FusedHeadConv forwards computed with torch.relu / nn.Conv2d.forward / the activation (CPU, channels-last, ...: gshead.py)
 _convert_norms = False   # set while `groupnorm` or `resblock` is requested: the constructor wrappers then run groupnorm.convert
 _convert_convs = False   # set while `stemconv` is requested: the UnetExtractor wrapper then runs stemconv.convert
+_convert_heads = False   # set while `gshead` is requested: the GSRegresser wrapper then runs gshead.convert
 _fuse_relu = False       # set while `resblock` is requested: the constructor wrappers then also run groupnorm.fuse_sequential_relu
 _installed = {}          # "module.attr" -> feature
 _originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), and the two pass-through cases below
@@ -81,7 +91,7 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV
+    known = FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV + OPT_IN_HEAD
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
@@ -143,11 +153,18 @@ def _depth2pc(depth, extrinsic, intrinsic):
     return _originals["lib.utils.depth2pc"][2](depth, extrinsic, intrinsic)
 
 
-def _converting_init(key):
+def _converting_init(key, heads=False):
     """core/extractor.py:7, :64 -- the reference's own constructor (from _originals), then whatever was asked for: this package's GroupNorm layers in
-    place of nn.GroupNorm (`groupnorm`, `resblock`), the stem's ReLU folded into its norm (`resblock`), the stem convolution (`stemconv`)."""
+    place of nn.GroupNorm (`groupnorm`, `resblock`), the stem's ReLU folded into its norm (`resblock`), the stem convolution (`stemconv`).
+    heads=True, lib/gs_parm_network.py:8 -- the constructor of the class that owns the Gaussian heads: their tails (`gshead`) and nothing else; the
+    encoder and the blocks it builds went through their own wrappers inside the reference's constructor."""
     def __init__(self, *args, **kwargs):
         _originals[key][2](self, *args, **kwargs)
+        if heads:
+            if _convert_heads:
+                from . import gshead
+                gshead.convert(self)
+            return
         if _convert_norms:
             from . import groupnorm
             groupnorm.convert(self)
@@ -161,7 +178,7 @@ def _converting_init(key):
 
 _resblock_init = _converting_init("core.extractor.ResidualBlock.__init__")
 _unet_init = _converting_init("core.extractor.UnetExtractor.__init__")
-
+_regresser_init = _converting_init("lib.gs_parm_network.GSRegresser.__init__", heads=True)
 
 
 def _resblock_forward(self, x):
@@ -206,6 +223,8 @@ def _table(features):
                                                                 ("core.extractor", "UnetExtractor.__init__", _unet_init)]
     elif "stemconv" in t:                     # the stem convolution alone: only the class that has one
         t["stemconv"].append(("core.extractor", "UnetExtractor.__init__", _unet_init))
+    if "gshead" in t:
+        t["gshead"].append(("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init))
     if "resblock" in t:
         t["resblock"].append(("core.extractor", "ResidualBlock.forward", _resblock_forward))
     return t
@@ -225,7 +244,7 @@ def _loaded(name):
 def apply(features=None):
     """Rebind whatever can be rebound NOW (idempotent; called after every reference module finishes loading).  Returns the number of new
     bindings made."""
-    global _fuse_relu, _convert_norms, _convert_convs
+    global _fuse_relu, _convert_norms, _convert_convs, _convert_heads
     feats = requested() if features is None else tuple(features)
     if not feats:
         return 0
@@ -234,6 +253,7 @@ def apply(features=None):
         _fuse_relu = _fuse_relu or "resblock" in feats
         _convert_norms = _convert_norms or "groupnorm" in feats or "resblock" in feats
         _convert_convs = _convert_convs or "stemconv" in feats
+        _convert_heads = _convert_heads or "gshead" in feats
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -270,7 +290,7 @@ def apply(features=None):
 
 def restore():
     """Undo every rebinding (tests)."""
-    global _fuse_relu, _convert_norms, _convert_convs
+    global _fuse_relu, _convert_norms, _convert_convs, _convert_heads
     with _lock:
         for key, (holder, name, orig) in list(_originals.items()):
             repl = holder.__dict__.get(name) if isinstance(holder, type) else getattr(holder, name, None)
@@ -282,7 +302,7 @@ def restore():
                         d[name] = orig
         _originals.clear()
         _installed.clear()
-        _fuse_relu = _convert_norms = _convert_convs = False
+        _fuse_relu = _convert_norms = _convert_convs = _convert_heads = False
         for k in calls:
             calls[k] = 0
 

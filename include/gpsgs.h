@@ -41,6 +41,10 @@
  *       the two full-resolution stem convolutions, torch.nn.Conv2d(3 | 1, 32, 5, stride 2, padding 2) of core/extractor.py:66-70 (the depth
  *       encoder's through lib/gs_parm_network.py:14) and their autograd backward: the library's implicit-GEMM kernels with a K step of 4 and the
  *       NCHW <-> NHWC transposes around them.
+ *   gsr_head_forward / gsr_head_backward (+ gsr_head_supported, gsr_head_tile, gsr_head_scratch_bytes)
+ *       the tail of the three Gaussian-parameter heads, nn.ReLU -> nn.Conv2d(32, 4 | 3 | 1, 1) -> nothing | nn.Softplus(beta=100) | nn.Sigmoid of
+ *       lib/gs_parm_network.py:34-50 on the full-resolution hidden tensor, and its autograd backward: ATen's clamp pass, the library's 1x1
+ *       implicit GEMM between NCHW <-> NHWC transposes, and the elementwise activation.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -68,7 +72,9 @@ extern "C" {
                                still 4 after the depth-distortion map: GsrDistort, gsr_forward_distort, gsr_backward_distort (additive)
                                still 4 after GroupNorm: gn_chunk_elems, gn_scratch_bytes, gn_forward, gn_backward (additive)
                                still 4 after the GroupNorm epilogues: gne_forward, gne_backward (additive)
-                               still 4 after the stem convolution: sc_supported, sc_tile, sc_scratch_bytes, sc_forward, sc_backward (additive) */
+                               still 4 after the stem convolution: sc_supported, sc_tile, sc_scratch_bytes, sc_forward, sc_backward (additive)
+                               still 4 after the Gaussian heads: gsr_head_supported, gsr_head_tile, gsr_head_scratch_bytes, gsr_head_forward,
+                                  gsr_head_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -500,6 +506,36 @@ int gsr_pack_views(int B, int n_views, int S2, const GsrStrided *valid /*u8*/, c
 int gsr_pack_views_backward(int B, int n_views, int S2, const uint32_t *row_of_pixel, const float *g_xyz, const float *g_rgb,
                             const float *g_rot, const float *g_scale, const float *g_opacity, float *const *d_xyz,
                             float *const *d_img, float *const *d_rot, float *const *d_scale, float *const *d_opacity, void *stream);
+
+/* ---- Gaussian-parameter heads: ReLU -> 1x1 convolution -> activation in one pass (lib/gs_parm_network.py:34-50) -------------------------
+ * y[n,k,p] = act( bias[k] + sum_c w[k,c] * max(h[n,c,p], 0) ),  h [N,C_in,H,W] and y [N,C_out,H,W] contiguous NCHW, w [C_out,C_in] (a 1x1
+ * convolution's weight as it lies), p over the H*W pixels of a plane; everything fp32.  z = bias, then fmaf over c in index order.
+ * act: 0 = none; 1 = softplus(beta, threshold) with torch's definition, z where beta*z > threshold, else log1p(exp(beta*z)) / beta; 2 = sigmoid.
+ * beta and threshold are read for act 1 only.
+ * gsr_head_supported: 1 for C_in in {16, 32, 64}, 1 <= C_out <= 4 and act in {0, 1, 2}; otherwise 0.
+ * gsr_head_tile: the pixels of one sample one workgroup covers (in both directions; the weight gradient has one partial per workgroup).
+ * Any H, W >= 1: where H*W is a multiple of 4 and h, y (backward: h, dy, dh) are 16-byte aligned the kernels move 16 bytes per access, otherwise
+ * (plane bases then lie off 16-byte boundaries) 4; 4-byte alignment is all that is required.
+ * gsr_head_backward takes dy, the gradient of y, and WRITES dh (NULL = not wanted: nothing is computed for it) and dw [C_out,C_in] / dbias
+ * [C_out] (both or neither; NULL = not wanted):
+ *     dz = dy * act'(z)      dh[n,c,p] = (h > 0) * sum_k w[k,c] dz_k  (zero at h == 0)      dw[k,c] = sum_{n,p} dz_k max(h_c, 0)      dbias[k] = sum dz_k
+ * z is recomputed from h with the forward's arithmetic; `y` (the forward's output) is NOT read and may be NULL -- the argument is kept so that a
+ * variant that takes act' from y needs no new entry point.  One launch reads h and dy once for both dh and the sums.  dw and dbias are two-stage
+ * sums: per workgroup, then over the workgroups in index order (in groups of 64, then the groups) -- no atomics, the same bits on every run.
+ * scratch (needed for dw / dbias only): DEVICE, at least gsr_head_scratch_bytes(...) =
+ *     4 * C_out * (C_in + 1) * (parts + ceil(parts / 64))   bytes,  parts = N * ceil(H*W / gsr_head_tile())
+ * and 0 for arguments the other entry points would refuse (the activation is not among its arguments).
+ * GPSGS_E_INVALID, before any HIP call: a (C_in, C_out, act) gsr_head_supported refuses, a non-positive N, H or W, beta <= 0 (or NaN) with act 1,
+ * a NULL required pointer (h, w, bias, y; h, w, bias, dy, and scratch where dw is wanted) or one off a 4-byte boundary, one of dw / dbias without
+ * the other, H*W > INT_MAX - gsr_head_tile() (a pixel index inside a plane is an int; offsets into the tensors are 64-bit, so N*C*H*W has no limit
+ * of its own) and N * ceil(H*W / tile) > INT_MAX (a grid's width).  A backward that wants neither dh nor dw returns GPSGS_OK and launches nothing. */
+int gsr_head_supported(int C_in, int C_out, int act);
+int gsr_head_tile(void);
+size_t gsr_head_scratch_bytes(int N, int C_in, int C_out, int H, int W);
+int gsr_head_forward(const float *h, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int act, float beta,
+                     float threshold, float *y, void *stream);
+int gsr_head_backward(const float *h, const float *w, const float *bias, const float *y, const float *dy, int N, int C_in, int C_out, int H, int W,
+                      int act, float beta, float threshold, float *dh, float *dw, float *dbias, void *scratch, void *stream);
 
 /* ---- fused L1 + SSIM loss (lib/loss.py:36-83 as used at train_stage2.py:70-72) ------------------------------------------
  * pred, gt: contiguous fp32 [planes = B*C, H, W].  out2 (device) = {mean |pred - gt|, mean SSIM map} (11x11 Gaussian window,
