@@ -242,6 +242,17 @@ def means3D_chain(scene, oracle, part):
     return (without + zpart).numpy(), without.numpy()
 
 
+def stack(n, W, H, opacity, scale, seed, dz=0.005, spread=0.05):
+    """n splats on a W x H image, dz apart in depth from z = 2 on, within `spread` of the optical axis: the scenes dense_definition is for."""
+    from conftest import gaussians, simple_scene
+    rng = np.random.default_rng(seed)
+    cam = simple_scene(W, H, 20.0, bg=(0.1, 0.2, 0.3))
+    xyz = np.stack([rng.uniform(-spread, spread, n), rng.uniform(-spread, spread, n), 2.0 + dz * np.arange(n)], 1)
+    q = rng.standard_normal((n, 4))  # anisotropic and rotated: every gradient of the stack is a real number, none an analytic zero
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    return dict(cam, **gaussians(xyz, rng.uniform(0, 1, (n, 3)), opacity, scale * rng.uniform(0.8, 1.25, (n, 3)), q))
+
+
 def dense_definition(scene, g):
     """distort_definition for scenes in which EVERY splat is blended into EVERY pixel (stacks of faint, wide splats): no decision is ever taken, so
     the blend is a closed form -- alpha = opacity exp(power) for all (splat, pixel) pairs at once, T the exclusive product of 1 - alpha in depth

@@ -11,6 +11,7 @@ import pytest
 from conftest import fragile_bounds, oracle_render
 
 from absgrad_ref import absgrad_jacobian, absgrad_replay, norm_err, tiny_scene
+from raster_run import small
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -35,16 +36,11 @@ def test_replay_equals_the_jacobian_on_tiny_scenes(seed):
     assert np.median(jab[vis, 0] / np.maximum(np.abs(jsg[vis, 0]), 1e-300)) > 1.5
 
 
-def _small():
-    from test_gpu_raster_contrib import _small
-    return _small()
-
-
 @pytest.mark.parametrize("name", ["96x64", "256"])
 def test_replay_signed_sums_equal_the_oracle_backward(name):
     """The replay's signed sums are the oracle's dL/dmeans2D: the walk, the recurrence and the units are the backward's own."""
     from gps_gaussian_amd import synthetic as S
-    g = _small() if name == "96x64" else S.make_scene(256, 30000)
+    g = small() if name == "96x64" else S.make_scene(256, 30000)
     dpix = np.random.default_rng(7).standard_normal((3, g["H"], g["W"])).astype(np.float32)
     o, _, _ = oracle_render(g)
     ref = o.backward(dpix)["means2D"][:, :2]

@@ -96,9 +96,8 @@ def test_replay_closed_forms():
 def test_dense_definition_equals_the_definition_on_a_stack():
     """65 faint, wide splats at distinct depths on an 8 x 8 image: every one is blended into every pixel, and the closed-form blend gives what the
     one-hot renders give (the GPU test walks stacks of up to 129 with it)."""
-    from test_gpu_raster_distortion import _stack
-    from distort_ref import dense_definition
-    s = _stack(65, 8, 8, 0.02, 2.0, 65)
+    from distort_ref import dense_definition, stack
+    s = stack(65, 8, 8, 0.02, 2.0, 65)
     g = _g(s, 65)
     dmap, ref = distort_definition(s, g)
     emap, got = dense_definition(s, g)

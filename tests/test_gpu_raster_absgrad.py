@@ -8,131 +8,24 @@ of the fp64 torch renderer) and against identities the renderer's other outputs 
 import numpy as np
 import pytest
 
-from conftest import assert_grad_parity, fragile_bounds, gaussians, simple_scene
+from conftest import assert_grad_parity, fragile_bounds
+from raster_run import batch as _batch, check_absgrad_structure as _check_structure, decode, leaves, pad as _pad, rasterize, render_ex_rows, run_view
+from raster_run import scene as _scene, settings, small as _small, valu_fixture
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(autouse=True)
-def _valu(monkeypatch):
-    """The plain runs the absgrad runs are compared with use the VALU family too (the absgrad runs always do)."""
-    monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
+_valu = valu_fixture()  # the plain runs the absgrad runs are compared with use the VALU family too (the absgrad runs always do)
 
 
-def _run(g, absgrad=True, dpix=None, extras=False, gdepth=None, galpha=None, aa=False, contrib=False, feats=None, shs=None, cov=None, cam=False,
-         pinned=False, keep_ws=False, color_grad=True, dpix2=None):
-    """One view through GaussianRasterizer, then the backward of sum(img * dpix) (+ sum(depth * gdepth) + sum(alpha * galpha)).  dpix2: a second
-    backward over the retained graph.  -> dict of numpy arrays: img, radii, depth / alpha, the statistics (w, m, n), abs0 (absgrad before any
-    backward), abs (after the last one), grads; with keep_ws the exported state (st)."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    want = dpix is not None
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(want and (color_grad or k != "colors")) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=want)
-    ft = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev) if feats is not None else None
-    cdev = torch.device("cpu") if pinned else dev
-    view, proj = (torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)) for k in ("view", "proj"))
-    if pinned:
-        view, proj = view.pin_memory(), proj.pin_memory()
-    view, proj = view.to(cdev).requires_grad_(cam), proj.to(cdev).requires_grad_(cam)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    kw = dict(return_depth_alpha=extras, antialiasing=aa, camera_grad=cam)
-    if ft is not None:
-        kw["features"] = ft
-    if contrib:
-        kw["return_contrib"] = True
-    if absgrad:
-        kw["return_absgrad"] = True
-    RZ._debug_keep_ws = keep_ws
-    try:
-        out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                        scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"), **kw)
-    finally:
-        RZ._debug_keep_ws = False
-    r = {"img": out[0], "radii": out[1]}
-    if keep_ws:
-        last = RZ._tls.__dict__.pop("last_ws")
-        r["st"] = RZ.export_state(last["ws"], g["means3D"].shape[0], g["W"], g["H"], last["cap"], last["bin_cap"])
-    if extras:
-        r["depth"], r["alpha"] = out[2], out[3]
-    assert len(out) == 2 + (2 if extras else 0) + (3 if contrib else 0) + (1 if absgrad else 0)
-    rest = out
-    if absgrad:
-        a = out[-1]
-        rest = out[:-1]
-        assert a.dtype == torch.float32 and tuple(a.shape) == (g["means3D"].shape[0], 2) and not a.requires_grad and a.grad_fn is None
-        r["abs0"] = a.clone()
-    if contrib:
-        r["w"], r["m"], r["n"] = rest[-3:]
-    if want:
-        def loss(d):
-            v = (out[0] * torch.from_numpy(d).to(dev)).sum()
-            if gdepth is not None:
-                v = v + (r["depth"] * torch.from_numpy(gdepth).to(dev)).sum()
-            if galpha is not None:
-                v = v + (r["alpha"] * torch.from_numpy(galpha).to(dev)).sum()
-            return v
-        if dpix2 is not None:
-            loss(dpix).backward(retain_graph=True)
-            for x in list(t.values()) + [m2]:
-                x.grad = None
-            loss(dpix2).backward()
-        else:
-            loss(dpix).backward()
-        gr = {k: t[k].grad.cpu().numpy() for k in names if t[k].requires_grad}
-        gr["means2D"] = m2.grad.cpu().numpy()
-        if cam:
-            gr["view"], gr["proj"] = view.grad.cpu().numpy(), proj.grad.cpu().numpy()
-        r["grads"] = gr
-    if absgrad:
-        r["abs"] = a
-    torch.cuda.synchronize()
-    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in r.items()}
-
-
-def _small(seed=5, n=1500, W=96, H=64):
-    rng = np.random.default_rng(seed)
-    cam = simple_scene(W, H, 70.0, bg=(0.2, 0.1, 0.3))
-    xyz = np.stack([rng.uniform(-0.7, 0.7, n), rng.uniform(-0.45, 0.45, n), rng.uniform(1.5, 3.0, n)], 1)
-    scale = np.exp(rng.uniform(np.log(0.003), np.log(0.05), (n, 3)))
-    q = rng.standard_normal((n, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    return dict(cam, **gaussians(xyz, rng.uniform(0, 1, (n, 3)), rng.uniform(0.05, 0.95, n), scale, q))
-
-
-def _scene(name):
-    from gps_gaussian_amd import synthetic as S
-    if name == "96x64":
-        return _small()
-    if name == "256":
-        return S.make_scene(256, 30000)
-    if name == "config2":
-        return S.make_scene(1024, 600000)
-    return S.make_scene(1024, 600000, render_res=2048)
+def _run(g, absgrad=True, dpix=None, gdepth=None, galpha=None, dpix2=None, **kw):
+    """run_view with absgrad on by default and features that need no gradient; the backward of sum(img * dpix) (+ sum(depth * gdepth) +
+    sum(alpha * galpha)); dpix2: a second backward over the retained graph."""
+    cot = dict(img=dpix, depth=gdepth, alpha=galpha)
+    return run_view(g, cot, dict(cot, img=dpix2) if dpix2 is not None else None, absgrad=absgrad, feat_grad=False, **kw)
 
 
 def _dpix(g, seed):
     return np.random.default_rng(seed).standard_normal((3, g["H"], g["W"])).astype(np.float32)
-
-
-def _pad(a):
-    return np.concatenate([a, np.zeros((a.shape[0], 1), a.dtype)], 1)
-
-
-def _check_structure(r):
-    """Finite, never negative, zero for culled Gaussians, and the triangle inequality against the signed gradient at the suite's tolerance."""
-    a, gm = r["abs"], r["grads"]["means2D"][:, :2]
-    assert np.isfinite(a).all() and (a >= 0).all()
-    assert (a[r["radii"] == 0] == 0).all()
-    assert (np.abs(gm) <= a + 1e-3 * (a + 1e-3 * np.abs(gm).max())).all()
 
 
 # ---- against the two references -------------------------------------------------------------------------------------------------------------------
@@ -254,20 +147,12 @@ def test_backward_overwrites_in_place():
 
 def test_option_off_call_unchanged():
     """return_absgrad=False is the call without the keyword: same outputs, same count."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
     g = _scene("96x64")
-    dev = torch.device("cuda:0")
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3, torch.from_numpy(g["campos"]).to(dev),
-                                          False, False)
-    m2 = torch.zeros_like(t["means3D"])
-    kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"])
-    x = RZ.GaussianRasterizer(rs)(**kw)
-    y = RZ.GaussianRasterizer(rs)(**kw, return_absgrad=False)
+    rs, t = settings(g), leaves(g)
+    x = decode(rasterize(rs, t), g, False)
+    y = decode(rasterize(rs, t, return_absgrad=False), g, False)
     assert len(x) == len(y) == 2
-    np.testing.assert_array_equal(x[0].cpu().numpy(), y[0].cpu().numpy())
+    np.testing.assert_array_equal(x["color"].cpu().numpy(), y["color"].cpu().numpy())
 
 
 # ---- combinations ---------------------------------------------------------------------------------------------------------------------------------
@@ -381,18 +266,6 @@ def test_empty_and_all_culled_views():
 
 # ---- pts2render -----------------------------------------------------------------------------------------------------------------------------------
 
-def _batch(B):
-    import torch
-    from test_gpu_raster_depth_alpha import _batch_data
-    data = _batch_data(B)
-    nv = data["novel_view"]  # the cameras on the device (as training hands them over): no host copy inside pts2render
-    nv["world_view_transform"], nv["full_proj_transform"] = nv["world_view_transform"].cuda(), nv["full_proj_transform"].cuda()
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
-    torch.cuda.synchronize()
-    return data
-
-
 @pytest.mark.parametrize("form", ["batch", "loop"])
 def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
     """pts2render(with_absgrad=True) at B = 4: zeros before the backward; after img.sum().backward() the two maps have the bits of four
@@ -418,12 +291,9 @@ def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
     data2 = _batch(B)
     xyz, rgb, rot, scale, opacity, offsets, rows = pack_views(data2, return_rows=True)
     xyz, rgb, rot, scale, opacity = (t.detach() for t in (xyz, rgb, rot, scale, opacity))  # (four separate backwards: not through the one pack node)
-    offs = offsets.tolist()
     parts = []
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg, absgrad=True)
-        assert tuple(r["absgrad"].shape) == (offs[i + 1] - offs[i], 2) and float(r["absgrad"].abs().max()) == 0.0
+    for i, sl, r in render_ex_rows(data2, (xyz, rgb, rot, scale, opacity), offsets, bg, absgrad=True):
+        assert tuple(r["absgrad"].shape) == (sl.stop - sl.start, 2) and float(r["absgrad"].abs().max()) == 0.0
         r["img"].sum().backward()
         parts.append(r["absgrad"])
     packed = torch.cat(parts).cpu().numpy()

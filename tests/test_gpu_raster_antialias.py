@@ -14,6 +14,7 @@ import pytest
 from conftest import assert_grad_parity, fragile_bounds, gaussians, oracle_render, simple_scene
 
 from aa_ref import aa_grads_dense, aa_vjp, chain_oracle, opacity_eff
+from raster_run import batch_data, batch_with_xyz_grad, leaves, rasterize, render_ex_rows, run_view, scene, settings, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -21,54 +22,16 @@ RGB_TOL = 1e-4
 GRAD_TOL = 1e-3
 
 
-def _render(g, aa=True, dpix=None, extras=False, shs=None, cov=None, settings_attr=False, keyword=True, colors=None, bg=None):
-    """One view through GaussianRasterizer.  -> dict(img, radii, depth, alpha, grads | None, st = export_state of the forward's workspace)."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    if colors is not None:
-        src["colors"] = colors
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(dpix is not None) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=dpix is not None)
-    bgv = g["bg"] if bg is None else np.asarray(bg, np.float32)
-    args = (g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(bgv).to(dev), float(g.get("scale_modifier", 1.0)),
-            torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3, torch.from_numpy(g["campos"]).to(dev), False, False)
-    kw = {}
+def _render(g, aa=True, dpix=None, settings_attr=False, keyword=True, **kw):
+    """run_view with antialiasing on by default, always with the forward's state (st).  settings_attr: the flag travels as the `antialiasing`
+    attribute of a settings object of the newer upstream shape, not as the keyword; keyword=False: the call without the keyword."""
+    make = None
     if settings_attr:
         from collections import namedtuple
+        from gps_gaussian_amd import rasterizer as RZ
         S = namedtuple("NewerSettings", RZ.GaussianRasterizationSettings._fields + ("antialiasing",))
-        rs = S(*args, bool(aa))
-    else:
-        rs = RZ.GaussianRasterizationSettings(*args)
-        if keyword:
-            kw["antialiasing"] = aa
-    if extras:
-        kw["return_depth_alpha"] = True
-    RZ._debug_keep_ws = True
-    try:
-        out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                        scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"), **kw)
-    finally:
-        RZ._debug_keep_ws = False
-    last = RZ._tls.__dict__.pop("last_ws")
-    P = g["means3D"].shape[0]
-    st = RZ.export_state(last["ws"], P, g["W"], g["H"], last["cap"], last["bin_cap"]) if P else None
-    res = dict(img=out[0], radii=out[1].cpu().numpy(), depth=out[2] if extras else None, alpha=out[3] if extras else None, grads=None,
-               st=st)
-    if dpix is not None:
-        out[0].backward(torch.from_numpy(np.ascontiguousarray(dpix, dtype=np.float32)).to(dev))
-        res["grads"] = {k: t[k].grad.cpu().numpy() for k in names}
-        res["grads"]["means2D"] = m2.grad.cpu().numpy()
-    for k in ("img", "depth", "alpha"):
-        if res[k] is not None:
-            res[k] = res[k].detach().cpu().numpy()
-    return res
+        make = lambda *args: S(*args, bool(aa))  # noqa: E731
+    return run_view(g, dict(img=dpix), aa=aa if keyword and not settings_attr else None, keep_ws=True, make_settings=make, **kw)
 
 
 def _op_eff(r):
@@ -201,15 +164,9 @@ def test_against_the_dense_fp64_reference(inputs, family):
 
 def _scene(name):
     from gps_gaussian_amd import synthetic as S
-    if name == "c1_256_30k":
-        return S.make_scene(256, 30000)
-    if name == "config2_1024_600k":
-        return S.make_scene(1024, 600000)
     if name == "config2_at_512":
         return S.make_scene(1024, 600000, render_res=512)
-    if name == "hr_2048_600k":
-        return S.make_scene(1024, 600000, render_res=2048)
-    raise KeyError(name)
+    return scene({"c1_256_30k": "256", "config2_1024_600k": "config2", "hr_2048_600k": "2048"}[name])
 
 
 @pytest.mark.parametrize("name", ["c1_256_30k", "config2_1024_600k", "config2_at_512", "hr_2048_600k"])
@@ -286,21 +243,15 @@ def test_families_and_list_forms(monkeypatch):
 
 def test_stage2_gradient_set_is_bit_equal(monkeypatch):
     """Colours without a gradient (GSR_FLAG_NO_COLOR_GRAD, the tile family drops the colour sums): every other gradient equals the full set's bits."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import synthetic as S
     monkeypatch.setenv("GPSGS_COMPOSITE", "tiles")
     g = S.make_scene(256, 30000)
-    dev = torch.device("cuda:0")
-    dpix = torch.from_numpy(np.random.default_rng(42).standard_normal((3, g["H"], g["W"])).astype(np.float32)).to(dev)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
+    dpix = to_dev(np.random.default_rng(42).standard_normal((3, g["H"], g["W"])))
+    rs = settings(g)
     out = []
     for col_grad in (True, False):
-        t = {k: torch.from_numpy(g[k]).to(dev).requires_grad_(k != "colors" or col_grad) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-        img, _ = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"],
-                                           colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"], antialiasing=True)
+        t = leaves(g, grad=lambda k: k != "colors" or col_grad)
+        img, _ = rasterize(rs, t, antialiasing=True)
         img.backward(dpix)
         out.append({k: t[k].grad.cpu().numpy() for k in ("means3D", "opacities", "scales", "rotations")})
     for k in out[0]:
@@ -385,28 +336,20 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(form, monkeypatch):
     import torch
     from gps_gaussian_amd import render_api
     from gps_gaussian_amd.pack import pack_views
-    from test_gpu_raster_depth_alpha import _batch_data
     monkeypatch.setenv("GPSGS_PTS2RENDER", form)
     monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
     B = 4
-    data = _batch_data(B)
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
+    data = batch_with_xyz_grad(B)
     bg = [0.2, 0.3, 0.4]
     nv = render_api.pts2render(data, bg, antialiasing=True)["novel_view"]
     rng = np.random.default_rng(71)
     gi = torch.from_numpy(rng.standard_normal((B, 3, 64, 64)).astype(np.float32)).cuda()
     (nv["img_pred"] * gi).sum().backward()
     g_batch = [data[v]["xyz"].grad.clone() for v in ("lmain", "rmain")]
-    data2 = _batch_data(B)
-    for v in ("lmain", "rmain"):
-        data2[v]["xyz"].requires_grad_(True)
-    xyz, rgb, rot, scale, opacity, offsets = pack_views(data2)
-    offs = offsets.tolist()
+    data2 = batch_with_xyz_grad(B)
+    *packed, offsets = pack_views(data2)
     loss = 0
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg, antialiasing=True)
+    for i, sl, r in render_ex_rows(data2, packed, offsets, bg, antialiasing=True):
         np.testing.assert_array_equal(nv["img_pred"][i].detach().cpu().numpy(), r["img"].detach().cpu().numpy())
         loss = loss + (r["img"] * gi[i]).sum()
     loss.backward()
@@ -415,7 +358,7 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(form, monkeypatch):
         s = float(gref.abs().max())
         assert s > 0
         assert float((gbat - gref).abs().max()) <= 1e-6 * s, v
-    plain = render_api.pts2render(_batch_data(B), bg)["novel_view"]["img_pred"]
+    plain = render_api.pts2render(batch_data(B), bg)["novel_view"]["img_pred"]
     assert float((plain.detach() - nv["img_pred"].detach()).abs().max()) > 1e-3
 
 

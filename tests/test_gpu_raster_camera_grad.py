@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import fragile_bounds, gaussians, simple_scene
+from raster_run import batch_data, batch_with_xyz_grad, device as _dev, leaves, rasterize, render_ex_rows, run_view, settings, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -17,46 +18,12 @@ VIEW_ZERO = [3, 7, 11, 15]   # row 3 of the viewmatrix: never read
 PROJ_ZERO = [2, 6, 10, 14]   # row 2 of the projmatrix: never read
 
 
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _render(g, dpix, shs=None, cov=None, aa=False, maps=None, camera_grad=True, cam_device=None, pin=False, colors_grad=True):
-    """One view through GaussianRasterizer.  maps: None or (dL_ddepth, dL_dalpha) [H,W].  -> dict(img, radii, grads, cam)"""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = _dev()
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    src = dict(g, shs=shs, cov3D_precomp=cov)
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(k != "colors" or colors_grad) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=True)
-    cdev = dev if cam_device is None else cam_device
-
-    def cam(x):
-        c = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(cdev)
-        if pin:
-            c = c.pin_memory()
-        return c.requires_grad_(camera_grad)
-
-    view, proj, campos = cam(g["view"]), cam(g["proj"]), cam(g["campos"])
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(np.asarray(g["bg"], np.float32)).to(dev), 1.0,
-                                          view, proj, 3, campos, False, False)
-    kw = dict(camera_grad=True) if camera_grad else {}
-    out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                    scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"),
-                                    return_depth_alpha=maps is not None, antialiasing=aa, **kw)
-    loss = (out[0] * torch.from_numpy(np.ascontiguousarray(dpix, dtype=np.float32)).to(dev)).sum()
-    if maps is not None:
-        loss = loss + (out[2].reshape(g["H"], g["W"]) * torch.from_numpy(maps[0]).to(dev)).sum() \
-                    + (out[3].reshape(g["H"], g["W"]) * torch.from_numpy(maps[1]).to(dev)).sum()
-    loss.backward()
-    grads = {k: t[k].grad.cpu().numpy() for k in names if t[k].grad is not None}
-    grads["means2D"] = m2.grad.cpu().numpy()
-    res = dict(img=out[0].detach().cpu().numpy(), radii=out[1].cpu().numpy(), grads=grads, cam=None, cam_tensors=(view, proj, campos))
-    if camera_grad:
-        res["cam"] = dict(view=view.grad, proj=proj.grad, campos=campos.grad)
-    return res
+def _render(g, dpix, maps=None, camera_grad=True, pin=False, colors_grad=True, **kw):
+    """run_view with camera gradients on by default and campos a leaf like the matrices.  maps: None or (dL_ddepth, dL_dalpha) [H,W].
+    -> dict(img, radii, grads, cam: the raw camera gradients, cam_tensors)"""
+    dd, da = maps if maps is not None else (None, None)
+    return run_view(g, dict(img=dpix, depth=dd, alpha=da), extras=maps is not None, cam=camera_grad, pinned=pin, color_grad=colors_grad,
+                    campos_leaf=True, raw_cam=True, **kw)
 
 
 def _ref(g, dpix, shs=None, cov=None, aa=False, maps=None):
@@ -183,15 +150,13 @@ def _qmul_pure(w, q):
 
 def test_rigid_motion_identity_at_config2():
     import torch
-    from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import synthetic as S
     dev = _dev()
     g = S.make_scene(1024, 600000)
     q = g["rotations"].astype(np.float64)
     g["rotations"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
     dpix = np.random.default_rng(91).standard_normal((3, g["H"], g["W"])).astype(np.float32)
-    names = ("means3D", "colors", "opacities", "scales", "rotations")
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev).requires_grad_(True) for k in names}
+    t = leaves(g, grad=True)
     xi = torch.zeros(6, dtype=torch.float32, device=dev, requires_grad=True)   # (omega, v)
     w, v = xi[:3], xi[3:]
     z = torch.zeros((), device=dev)
@@ -201,11 +166,8 @@ def test_rigid_motion_identity_at_config2():
     Vt, Ft = torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev)
     # the row-vector form the reference passes: camera V E  ->  (V E)^T = E^T V^T
     view, proj = E.t() @ Vt, E.t() @ Ft
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
     m2 = torch.zeros_like(t["means3D"], requires_grad=True)
-    img, radii = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                           scales=t["scales"], rotations=t["rotations"], camera_grad=True)
+    img, radii = rasterize(settings(g, view=view, proj=proj), t, m2, camera_grad=True)
     assert int((radii > 0).sum()) > 100000
     (img * torch.from_numpy(dpix).to(dev)).sum().backward()
     d_xi = xi.grad.double().cpu().numpy()
@@ -264,15 +226,9 @@ def test_only_requested_outputs_and_pinned_cpu_cameras():
         assert cpu["cam"][k].device.type == "cpu" and cpu["cam"][k].shape == gpu["cam"][k].shape
         np.testing.assert_array_equal(cpu["cam"][k].numpy(), gpu["cam"][k].cpu().numpy(), err_msg=k)
     # only the projection matrix is learnable
-    from gps_gaussian_amd import rasterizer as RZ
     dev = _dev()
-    view = torch.from_numpy(g["view"]).to(dev)
-    proj = torch.from_numpy(g["proj"]).to(dev).requires_grad_(True)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-    img, _ = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"],
-                                       colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"], camera_grad=True)
+    view, proj = to_dev(g["view"]), to_dev(g["proj"]).requires_grad_(True)
+    img, _ = rasterize(settings(g, view=view, proj=proj), leaves(g), camera_grad=True)
     (img * torch.from_numpy(dpix).to(dev)).sum().backward()
     np.testing.assert_array_equal(proj.grad.cpu().numpy(), gpu["cam"]["proj"].cpu().numpy())
     assert view.grad is None
@@ -294,18 +250,15 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(variant, monkeypatch
     from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import render_api
     from gps_gaussian_amd.pack import pack_views
-    from test_gpu_raster_depth_alpha import _batch_data
     monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
     monkeypatch.setenv("GPSGS_LISTS", "direct" if variant == "direct" else "scanned")
     B, side = 4, 64
-    data = _batch_data(B)
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
+    data = batch_with_xyz_grad(B)
     # a different camera per sample
     for i in range(B):
         data["novel_view"]["world_view_transform"][i, 3, :3] += torch.tensor([0.02 * i, -0.01 * i, 0.03 * i])
         data["novel_view"]["full_proj_transform"][i] = data["novel_view"]["world_view_transform"][i] @ (
-            torch.linalg.inv(_batch_data(1)["novel_view"]["world_view_transform"][0]) @ _batch_data(1)["novel_view"]["full_proj_transform"][0])
+            torch.linalg.inv(batch_data(1)["novel_view"]["world_view_transform"][0]) @ batch_data(1)["novel_view"]["full_proj_transform"][0])
     nv = _cam_leaves(data, pin=variant == "pinned_cpu")
     calls = []
     if variant == "repair":
@@ -329,16 +282,13 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(variant, monkeypatch
     assert got["world_view_transform"].shape == (B, 4, 4) and got["camera_center"].shape == (B, 3)
     assert all(x.device == nv[k].device for k, x in got.items())
     # the same samples, one render_ex each
-    data2 = _batch_data(B)
+    data2 = batch_data(B)
     for i in range(B):
         data2["novel_view"]["world_view_transform"][i] = data["novel_view"]["world_view_transform"][i].detach().cpu()
         data2["novel_view"]["full_proj_transform"][i] = data["novel_view"]["full_proj_transform"][i].detach().cpu()
     nv2 = _cam_leaves(data2, pin=variant == "pinned_cpu")
-    xyz, rgb, rot, scale, opacity, offsets = pack_views(data2)
-    offs = offsets.tolist()
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg, camera_grad=True)
+    *packed, offsets = pack_views(data2)
+    for i, sl, r in render_ex_rows(data2, packed, offsets, bg, camera_grad=True):
         np.testing.assert_array_equal(nv["img_pred"][i].detach().cpu().numpy(), r["img"].detach().cpu().numpy())
         ((r["img"] * gi[i]).sum() + (r["depth"] * gd[i]).sum()).backward()
     for k in ("world_view_transform", "full_proj_transform"):
@@ -362,19 +312,15 @@ def _se3(xi):
 def test_pose_refinement_converges():
     """A novel camera perturbed by ~1 degree and ~1 cm is pulled back by Adam on an se(3) pose through the camera gradients."""
     import torch
-    from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import synthetic as S
     dev = _dev()
     g = S.make_scene(256, 30000)
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
+    t = leaves(g)
     Vt, Ft = torch.from_numpy(g["view"]).double(), torch.from_numpy(g["proj"]).double()
-    bg = torch.from_numpy(g["bg"]).to(dev)
-    campos = torch.from_numpy(g["campos"]).to(dev)
 
     def render(view, proj, camera_grad=False):
-        rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], bg, 1.0, view, proj, 3, campos, False, False)
-        return RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"],
-                                         colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"], camera_grad=camera_grad)[0]
+        img, _ = rasterize(settings(g, view=view, proj=proj), t, camera_grad=camera_grad)
+        return img
 
     target = render(Vt.float().to(dev), Ft.float().to(dev)).detach()
     axis = np.array([0.6, -0.48, 0.64])

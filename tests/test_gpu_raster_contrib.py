@@ -8,118 +8,18 @@ replay of the fp32 oracle's blend (tests/contrib_ref.py) and against identities 
 import numpy as np
 import pytest
 
-from conftest import fragile_bounds, gaussians, simple_scene
+from conftest import fragile_bounds
+from raster_run import RGB_TOL, batch as _batch, check_contrib_structure as _check_structure, close_each as _close, decode, leaves, rasterize
+from raster_run import render_ex_rows, run_view, scene as _scene, settings, small as _small, valu_fixture
 
 pytestmark = pytest.mark.gpu
 
-RGB_TOL = 1e-4  # the suite's RGB tolerance (relative here), with an absolute floor of 1e-7
-GEOM = ("means3D", "means2D", "opacities", "scales", "rotations")
+_valu = valu_fixture()  # the plain runs the statistics runs are compared with use the VALU family too (the statistics runs always do)
 
 
-@pytest.fixture(autouse=True)
-def _valu(monkeypatch):
-    """The plain runs the statistics runs are compared with use the VALU family too (the statistics runs always do)."""
-    monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
-
-
-def _run(g, contrib=True, dpix=None, extras=False, aa=False, feats=None, gfeat=None, shs=None, cov=None, cam=False, pinned=False, keep_ws=False):
-    """One view through GaussianRasterizer (+ backward of sum(img * dpix) + sum(feat * gfeat) when given).  -> dict of numpy arrays: img, radii,
-    depth / alpha, feat, the three statistics, grads; with keep_ws the exported state (st)."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    want = dpix is not None or gfeat is not None
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(want) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=want)
-    ft = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev).requires_grad_(want) if feats is not None else None
-    cdev = torch.device("cpu") if pinned else dev
-    view, proj = (torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)) for k in ("view", "proj"))
-    if pinned:
-        view, proj = view.pin_memory(), proj.pin_memory()
-    view, proj = view.to(cdev).requires_grad_(cam), proj.to(cdev).requires_grad_(cam)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    kw = dict(return_depth_alpha=extras, antialiasing=aa, camera_grad=cam)
-    if ft is not None:
-        kw["features"] = ft
-    if contrib:
-        kw["return_contrib"] = True
-    RZ._debug_keep_ws = keep_ws
-    try:
-        out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                        scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"), **kw)
-    finally:
-        RZ._debug_keep_ws = False
-    r = {"img": out[0], "radii": out[1]}
-    if keep_ws:
-        last = RZ._tls.__dict__.pop("last_ws")
-        r["st"] = RZ.export_state(last["ws"], g["means3D"].shape[0], g["W"], g["H"], last["cap"], last["bin_cap"])
-    if extras:
-        r["depth"], r["alpha"] = out[2], out[3]
-    if ft is not None:
-        r["feat"] = out[4 if extras else 2]
-    if contrib:
-        assert len(out) == 2 + (2 if extras else 0) + (1 if ft is not None else 0) + 3
-        r["w"], r["m"], r["n"] = out[-3:]
-        assert r["w"].dtype == torch.float32 and r["m"].dtype == torch.float32 and r["n"].dtype == torch.int32
-        assert not r["w"].requires_grad and not r["m"].requires_grad and not r["n"].requires_grad
-    if want:
-        loss = 0
-        if dpix is not None:
-            loss = loss + (out[0] * torch.from_numpy(dpix).to(dev)).sum()
-        if gfeat is not None:
-            loss = loss + (r["feat"] * torch.from_numpy(gfeat).to(dev)).sum()
-        loss.backward()
-        gr = {k: t[k].grad.cpu().numpy() for k in names}
-        gr["means2D"] = m2.grad.cpu().numpy()
-        if ft is not None:
-            gr["features"] = ft.grad.cpu().numpy()
-        if cam:
-            gr["view"], gr["proj"] = view.grad.cpu().numpy(), proj.grad.cpu().numpy()
-        r["grads"] = gr
-    torch.cuda.synchronize()
-    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in r.items()}
-
-
-def _small(seed=5, n=1500, W=96, H=64):
-    rng = np.random.default_rng(seed)
-    cam = simple_scene(W, H, 70.0, bg=(0.2, 0.1, 0.3))
-    xyz = np.stack([rng.uniform(-0.7, 0.7, n), rng.uniform(-0.45, 0.45, n), rng.uniform(1.5, 3.0, n)], 1)
-    scale = np.exp(rng.uniform(np.log(0.003), np.log(0.05), (n, 3)))
-    q = rng.standard_normal((n, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    return dict(cam, **gaussians(xyz, rng.uniform(0, 1, (n, 3)), rng.uniform(0.05, 0.95, n), scale, q))
-
-
-def _scene(name):
-    from gps_gaussian_amd import synthetic as S
-    if name == "96x64":
-        return _small()
-    if name == "256":
-        return S.make_scene(256, 30000)
-    if name == "config2":
-        return S.make_scene(1024, 600000)
-    return S.make_scene(1024, 600000, render_res=2048)
-
-
-def _close(a, b, tol=RGB_TOL, floor=1e-7):
-    return np.abs(a - b) <= tol * np.abs(b) + floor
-
-
-def _check_structure(r):
-    w, m, n, radii = r["w"], r["m"], r["n"], r["radii"]
-    assert np.isfinite(w).all() and np.isfinite(m).all()
-    assert (m <= np.minimum(np.float32(0.99), w)).all()
-    assert ((n > 0) == (w > 0)).all() and ((w > 0) == (m > 0)).all()
-    assert (n >= 0).all()
-    culled = radii == 0
-    assert (w[culled] == 0).all() and (m[culled] == 0).all() and (n[culled] == 0).all()
+def _run(g, contrib=True, dpix=None, gfeat=None, **kw):
+    """run_view with the statistics on by default (+ backward of sum(img * dpix) + sum(feat * gfeat) when given)."""
+    return run_view(g, dict(img=dpix, feat=gfeat), contrib=contrib, **kw)
 
 
 # ---- against the oracle's blend -------------------------------------------------------------------------------------------------------------------
@@ -195,20 +95,12 @@ def test_gradients_and_outputs_unchanged_and_reproducible():
 
 def test_option_off_call_unchanged():
     """return_contrib=False is the call without the keyword: same outputs, same count."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
     g = _scene("96x64")
-    dev = torch.device("cuda:0")
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3, torch.from_numpy(g["campos"]).to(dev),
-                                          False, False)
-    m2 = torch.zeros_like(t["means3D"])
-    kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"])
-    x = RZ.GaussianRasterizer(rs)(**kw)
-    y = RZ.GaussianRasterizer(rs)(**kw, return_contrib=False)
+    rs, t = settings(g), leaves(g)
+    x = decode(rasterize(rs, t), g, False)
+    y = decode(rasterize(rs, t, return_contrib=False), g, False)
     assert len(x) == len(y) == 2
-    np.testing.assert_array_equal(x[0].cpu().numpy(), y[0].cpu().numpy())
+    np.testing.assert_array_equal(x["color"].cpu().numpy(), y["color"].cpu().numpy())
 
 
 # ---- combinations ---------------------------------------------------------------------------------------------------------------------------------
@@ -293,18 +185,6 @@ def test_empty_and_all_culled_views():
 
 # ---- pts2render -----------------------------------------------------------------------------------------------------------------------------------
 
-def _batch(B):
-    import torch
-    from test_gpu_raster_depth_alpha import _batch_data
-    data = _batch_data(B)
-    nv = data["novel_view"]  # the cameras on the device (as training hands them over): no host copy inside pts2render
-    nv["world_view_transform"], nv["full_proj_transform"] = nv["world_view_transform"].cuda(), nv["full_proj_transform"].cuda()
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
-    torch.cuda.synchronize()
-    return data
-
-
 @pytest.mark.parametrize("form", ["batch", "loop"])
 def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
     """pts2render(with_contrib=True) at B = 4: the statistics have the bits of four render_ex(contrib=True) calls on the same packed rows; every valid
@@ -325,14 +205,11 @@ def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
 
     data2 = _batch(B)
     xyz, rgb, rot, scale, opacity, offsets, rows = pack_views(data2, return_rows=True)
-    offs = offsets.tolist()
     keys = ("contrib_weight", "contrib_max", "contrib_pixels")
     stats = {k: [] for k in keys}
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg, contrib=True)
+    for i, sl, r in render_ex_rows(data2, (xyz, rgb, rot, scale, opacity), offsets, bg, contrib=True):
         for k in keys:
-            assert tuple(r[k].shape) == (offs[i + 1] - offs[i],)
+            assert tuple(r[k].shape) == (sl.stop - sl.start,)
             stats[k].append(r[k])
     rows = rows.cpu().numpy()
     for k in keys:

@@ -12,107 +12,19 @@ import numpy as np
 import pytest
 
 from conftest import assert_grad_parity, fragile_bounds, oracle_render, simple_scene, gaussians
+from raster_run import batch_with_xyz_grad, check_against_plain as _check_against_plain, depth_alpha_run as _render, render_ex_rows, scene, settings
+from raster_run import valu_fixture, zcol as _zcol, zrow as _zrow
 
 pytestmark = pytest.mark.gpu
 
 RGB_TOL = 1e-4
 GRAD_TOL = 1e-3
-BITWISE = ("opacities", "scales", "rotations", "means2D", "cov3D_precomp", "shs")
 
-
-@pytest.fixture(autouse=True)
-def _valu(monkeypatch):
-    """The plain runs the extras are compared with use the VALU family too (the extras always do)."""
-    monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
-
-
-def _render(g, colors=None, bg=None, dpix=None, dd=None, da=None, extras=False, shs=None, cov=None, sh_degree=3):
-    """One view through GaussianRasterizer.  -> (img, depth|None, alpha|None, grads dict|None, per-Gaussian fp32 view-space depth)."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    src["colors"] = g["colors"] if colors is None else colors
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    want_grad = dpix is not None or dd is not None or da is not None
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(want_grad) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=want_grad)
-    bg = g["bg"] if bg is None else np.asarray(bg, np.float32)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(bg).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), sh_degree,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    RZ._debug_keep_ws = True
-    try:
-        out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                        scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"), return_depth_alpha=extras)
-    finally:
-        RZ._debug_keep_ws = False
-    last = RZ._tls.__dict__.pop("last_ws")
-    P = g["means3D"].shape[0]
-    z = RZ.export_state(last["ws"], P, g["W"], g["H"], last["cap"], last["bin_cap"])["depth"].cpu().numpy() if P else np.zeros(0, np.float32)
-    img = out[0]
-    depth, alpha = (out[2], out[3]) if extras else (None, None)
-    grads = None
-    if want_grad:
-        outs, gts = [], []
-        for o, gt in ((img, dpix), (depth, dd), (alpha, da)):
-            if o is not None and gt is not None:
-                outs.append(o)
-                gts.append(torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32)).to(dev).reshape(o.shape))
-        torch.autograd.backward(outs, gts)
-        grads = {k: t[k].grad.cpu().numpy() for k in names}
-        grads["means2D"] = m2.grad.cpu().numpy()
-    fetch = lambda x: None if x is None else x.detach().cpu().numpy()  # noqa: E731
-    return fetch(img), fetch(depth), fetch(alpha), grads, z
-
-
-def _zcol(z):
-    """The colours of the equivalent plain run: (z_i, 1, 0)."""
-    return np.stack([z, np.ones_like(z), np.zeros_like(z)], 1).astype(np.float32)
-
-
-def _zrow(g):
-    v = np.asarray(g["view"], np.float32).reshape(16)
-    return v[[2, 6, 10]]  # dz/dmeans3D: z = v[2] x + v[6] y + v[10] z + v[14] (column-major flat view matrix)
-
-
-def _check_against_plain(g, dd, da, shs=None, cov=None):
-    """Extras run (random colours, non-zero background, no image gradient) against the plain run with colours (z, 1, 0), background 0 and
-    dL/dpix = (dd, da, 0)."""
-    H, W = g["H"], g["W"]
-    zero = np.zeros((3, H, W), np.float32)
-    _, dep, alp, ga, z = _render(g, bg=(0.3, 0.2, 0.1), dpix=zero, dd=dd, da=da, extras=True, shs=shs, cov=cov)
-    dB = np.stack([np.zeros((H, W), np.float32) if dd is None else dd, np.zeros((H, W), np.float32) if da is None else da, np.zeros((H, W), np.float32)])
-    imgB, _, _, gb, zB = _render(g, colors=_zcol(z), bg=(0.0, 0.0, 0.0), dpix=dB, cov=cov)
-    np.testing.assert_array_equal(z, zB)
-    np.testing.assert_array_equal(dep[0], imgB[0])
-    np.testing.assert_array_equal(alp[0], imgB[1])
-    for k in ga:
-        if k in BITWISE:
-            np.testing.assert_array_equal(ga[k], gb[k], err_msg=k)
-    # dL/dmeans3D: the plain run's, plus dL/dz (= its dL/dcolour R) through the view matrix's third row
-    dz = gb["colors"][:, 0]
-    want = gb["means3D"].astype(np.float64) + dz[:, None].astype(np.float64) * _zrow(g)[None, :].astype(np.float64)
-    s = np.abs(want).max() + 1e-30
-    assert np.abs(ga["means3D"] - want).max() <= 1e-5 * s, np.abs(ga["means3D"] - want).max() / s
-    if dd is not None and np.abs(dd).max() > 0:
-        assert np.abs(ga["means3D"] - gb["means3D"]).max() > 1e-3 * s  # the z term is really there
-    return dep, alp, ga, gb, z
+_valu = valu_fixture()  # the plain runs the extras are compared with use the VALU family too (the extras always do)
 
 
 def _scene(name):
-    from gps_gaussian_amd import synthetic as S
-    if name == "c1_256_30k":
-        return S.make_scene(256, 30000)
-    if name == "config2_1024_600k":
-        return S.make_scene(1024, 600000)
-    if name == "hr_2048_600k":
-        return S.make_scene(1024, 600000, render_res=2048)
-    raise KeyError(name)
+    return scene({"c1_256_30k": "256", "config2_1024_600k": "config2", "hr_2048_600k": "2048"}[name])
 
 
 @pytest.mark.parametrize("name", ["c1_256_30k", "config2_1024_600k", "hr_2048_600k"])
@@ -320,7 +232,7 @@ def test_misaligned_output_pointers():
     torch.cuda.synchronize()
     # torch outputs at an odd element offset (4- but not 16-byte aligned): written exactly like aligned ones
     from types import SimpleNamespace
-    rs = RZ.GaussianRasterizationSettings(H, W, g["tanfovx"], g["tanfovy"], t["bg"], 1.0, t["view"], t["proj"], 3, torch.zeros(3, device=dev), False, False)
+    rs = settings(g, view=t["view"], proj=t["proj"], campos=torch.zeros(3, device=dev))
     opts = RZ._view_options(rs, depth_alpha=True)
     ref = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, opts)
     big = torch.full((2 * H * W + 3,), -7.0, device=dev)
@@ -328,33 +240,8 @@ def test_misaligned_output_pointers():
     out = RZ._forward_impl(SimpleNamespace(), t["means3D"], t["colors"], t["opacities"], t["scales"], t["rotations"], rs, False, opts,
                            out=dict(depth=od, alpha=oa))
     torch.cuda.synchronize()
-    assert torch.equal(out[2], ref[2].reshape(H, W)) and torch.equal(out[3], ref[3].reshape(H, W))
+    assert torch.equal(out.depth, ref.depth.reshape(H, W)) and torch.equal(out.alpha, ref.alpha.reshape(H, W))
     assert float(big[0]) == -7.0 and float(big[1 + H * W]) == -7.0 and float(big[-1]) == -7.0
-
-
-def _batch_data(B):
-    import os
-    import torch
-    from conftest import GOLDEN
-    gold = np.load(os.path.join(GOLDEN, "pts2render_golden.npz"))
-    dev = torch.device("cuda:0")
-    side = 64
-    data = {}
-    for v in ("lmain", "rmain"):
-        d = {k: torch.from_numpy(gold["%s_%s" % (v, k)]).to(dev) for k in ("img", "xyz", "pts_valid", "rot_maps", "scale_maps", "opacity_maps")}
-        rep = (B + d["img"].shape[0] - 1) // d["img"].shape[0]
-        d = {k: torch.cat([x] * rep)[:B].contiguous() for k, x in d.items()}
-        d["xyz"] = d["xyz"] * 0.1 + torch.tensor([0.0, 0.0, 2.0], device=dev)
-        d["scale_maps"] = d["scale_maps"] * 5
-        d["xyz"][2:] = d["xyz"][2:] + torch.tensor([0.05, -0.03, 0.4], device=dev)  # the repeated samples differ from the first ones
-        data[v] = d
-    cam = simple_scene(side, side, 48.0)
-    data["novel_view"] = dict(
-        FovX=torch.tensor([2 * np.arctan(cam["tanfovx"])] * B), FovY=torch.tensor([2 * np.arctan(cam["tanfovy"])] * B),
-        width=torch.tensor([side] * B), height=torch.tensor([side] * B),
-        world_view_transform=torch.from_numpy(cam["view"])[None].repeat(B, 1, 1),
-        full_proj_transform=torch.from_numpy(cam["proj"])[None].repeat(B, 1, 1), camera_center=torch.zeros(B, 3))
-    return data
 
 
 @pytest.mark.parametrize("form", ["batch", "loop"])
@@ -364,9 +251,7 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(form, monkeypatch):
     from gps_gaussian_amd.pack import pack_views
     monkeypatch.setenv("GPSGS_PTS2RENDER", form)
     B = 4
-    data = _batch_data(B)
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
+    data = batch_with_xyz_grad(B)
     bg = [0.2, 0.3, 0.4]
     nv = render_api.pts2render(data, bg, with_depth_alpha=True)["novel_view"]
     assert tuple(nv["depth_pred"].shape) == (B, 1, 64, 64) and tuple(nv["alpha_pred"].shape) == (B, 1, 64, 64)
@@ -376,15 +261,10 @@ def test_pts2render_batch_of_4_against_four_render_ex_calls(form, monkeypatch):
     ((nv["depth_pred"] * gd).sum() + (nv["alpha_pred"] * gd.flip(2)).sum() + (nv["img_pred"] * gi).sum()).backward()
     g_batch = [data[v]["xyz"].grad.clone() for v in ("lmain", "rmain")]
 
-    data2 = _batch_data(B)
-    for v in ("lmain", "rmain"):
-        data2[v]["xyz"].requires_grad_(True)
-    xyz, rgb, rot, scale, opacity, offsets = pack_views(data2)
-    offs = offsets.tolist()
+    data2 = batch_with_xyz_grad(B)
+    *packed, offsets = pack_views(data2)
     loss = 0
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg)
+    for i, sl, r in render_ex_rows(data2, packed, offsets, bg):
         np.testing.assert_array_equal(nv["depth_pred"][i].detach().cpu().numpy(), r["depth"].detach().cpu().numpy())
         np.testing.assert_array_equal(nv["alpha_pred"][i].detach().cpu().numpy(), r["alpha"].detach().cpu().numpy())
         np.testing.assert_array_equal(nv["img_pred"][i].detach().cpu().numpy(), r["img"].detach().cpu().numpy())

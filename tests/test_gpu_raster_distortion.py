@@ -10,78 +10,27 @@ bit identities.  Every comparison prints its measured maximum before it asserts.
 import numpy as np
 import pytest
 
-from conftest import fragile_bounds, gaussians, oracle_render, simple_scene
+from conftest import fragile_bounds, oracle_render
+from distort_ref import stack as _stack
+from raster_run import batch as _batch, decode, leaves, rasterize, render_ex_rows, run_view, scene as _scene, settings, valu_fixture
 
 pytestmark = pytest.mark.gpu
 
 MAP_TOL, GRAD_TOL = 1e-4, 1e-3
 GRADS = ("means3D", "opacities", "scales", "rotations", "means2D", "colors")
 
-
-@pytest.fixture(autouse=True)
-def _valu(monkeypatch):
-    """The runs without the map that the distortion runs are compared with use the VALU family too (the distortion runs always do)."""
-    monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
+_valu = valu_fixture()  # the runs without the map that the distortion runs are compared with use the VALU family too (the distortion runs always do)
 
 
-def _run(g, distortion=True, gdist=None, dpix=None, extras=False, gdepth=None, galpha=None, aa=False, shs=None, cov=None, cam=False, color_grad=True):
-    """One view through GaussianRasterizer, then (if any gradient is given) the backward of sum(dist * gdist) + sum(img * dpix) + sum(depth * gdepth)
-    + sum(alpha * galpha).  -> dict of numpy arrays: img, radii, depth / alpha (extras), dist [H, W], grads."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    want = any(x is not None for x in (gdist, dpix, gdepth, galpha))
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(want and (color_grad or k != "colors")) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=want)
-    view, proj = (torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev).requires_grad_(cam) for k in ("view", "proj"))
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    kw = dict(return_depth_alpha=extras, antialiasing=aa, camera_grad=cam)
-    if distortion:
-        kw["return_distortion"] = True
-    out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                    scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"), **kw)
-    assert len(out) == 2 + (2 if extras else 0) + (1 if distortion else 0)
-    r = {"img": out[0], "radii": out[1]}
-    if extras:
-        r["depth"], r["alpha"] = out[2], out[3]
-    if distortion:
-        d = out[-1]
-        assert d.dtype == torch.float32 and tuple(d.shape) == (1, g["H"], g["W"]) and d.requires_grad == want
-        r["dist"] = d[0]
-    if want:
-        loss = 0.0
-        for key, gr in (("dist", gdist), ("img", dpix), ("depth", gdepth), ("alpha", galpha)):
-            if gr is not None:
-                loss = loss + (r[key] * torch.from_numpy(np.ascontiguousarray(gr, dtype=np.float32)).to(dev).reshape(r[key].shape)).sum()
-        loss.backward()
-        gr = {k: t[k].grad.cpu().numpy() for k in names if t[k].requires_grad}
-        gr["means2D"] = m2.grad.cpu().numpy()
-        if cam:
-            gr["view"], gr["proj"] = view.grad.cpu().numpy(), proj.grad.cpu().numpy()
-        r["grads"] = gr
-    torch.cuda.synchronize()
-    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in r.items()}
+def _run(g, distortion=True, gdist=None, dpix=None, gdepth=None, galpha=None, **kw):
+    """run_view with the map on by default, then (if any gradient is given) the backward of sum(dist * gdist) + sum(img * dpix) + sum(depth * gdepth)
+    + sum(alpha * galpha).  dist comes back as [H, W]."""
+    return run_view(g, dict(dist=gdist, img=dpix, depth=gdepth, alpha=galpha), distortion=distortion, **kw)
 
 
 def _rand(g, seed, ch=None):
     shape = (g["H"], g["W"]) if ch is None else (ch, g["H"], g["W"])
     return np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
-
-
-def _scene(name):
-    from gps_gaussian_amd import synthetic as S
-    if name == "256":
-        return S.make_scene(256, 30000)
-    if name == "config2":
-        return S.make_scene(1024, 600000)
-    return S.make_scene(1024, 600000, render_res=2048)
 
 
 def _equal_grads(a, b):
@@ -169,15 +118,6 @@ def test_256_scene_against_the_oracle_replay():
 
 
 # ---- kernel edges: round boundaries of the running and suffix sums, saturation, closed forms -------------------------------------------------------------
-
-def _stack(n, W, H, opacity, scale, seed, dz=0.005, spread=0.05):
-    rng = np.random.default_rng(seed)
-    cam = simple_scene(W, H, 20.0, bg=(0.1, 0.2, 0.3))
-    xyz = np.stack([rng.uniform(-spread, spread, n), rng.uniform(-spread, spread, n), 2.0 + dz * np.arange(n)], 1)
-    q = rng.standard_normal((n, 4))  # anisotropic and rotated: every gradient of the stack is a real number, none an analytic zero
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    return dict(cam, **gaussians(xyz, rng.uniform(0, 1, (n, 3)), opacity, scale * rng.uniform(0.8, 1.25, (n, 3)), q))
-
 
 @pytest.mark.parametrize("n,W,H", [(63, 8, 8), (64, 17, 9), (65, 8, 8), (129, 17, 9)])
 def test_stacks_across_round_boundaries(n, W, H):
@@ -294,19 +234,10 @@ def test_option_off_zero_gradient_and_reproducibility():
     alone = _run(g)
     np.testing.assert_array_equal(alone["dist"], on["dist"])
     np.testing.assert_array_equal(alone["img"], off["img"])
-    plain, kwoff = _run(g, distortion=False, dpix=dpix), None
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3, torch.from_numpy(g["campos"]).to(dev),
-                                          False, False)
-    args = dict(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
-                rotations=t["rotations"])
-    kwoff = RZ.GaussianRasterizer(rs)(**args, return_distortion=False)
+    plain = _run(g, distortion=False, dpix=dpix)
+    kwoff = decode(rasterize(settings(g), leaves(g), return_distortion=False), g, False)
     assert len(kwoff) == 2
-    np.testing.assert_array_equal(kwoff[0].cpu().numpy(), plain["img"])
+    np.testing.assert_array_equal(kwoff["color"].cpu().numpy(), plain["img"])
 
 
 # ---- combinations and host paths ---------------------------------------------------------------------------------------------------------------------------
@@ -347,18 +278,11 @@ def test_combinations():
     for k in r["grads"]:
         np.testing.assert_array_equal(r["grads"][k], base["grads"][k], err_msg=k)
     # the three refusals, on GPU tensors
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    t = {k: torch.from_numpy(np.ascontiguousarray(g[k], dtype=np.float32)).to(dev) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(g["bg"]).to(dev), 1.0,
-                                          torch.from_numpy(g["view"]).to(dev), torch.from_numpy(g["proj"]).to(dev), 3, torch.from_numpy(g["campos"]).to(dev),
-                                          False, False)
-    args = dict(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
-                rotations=t["rotations"], return_distortion=True)
+    rs, t, dev = settings(g), leaves(g), torch.device("cuda:0")
     for kw, what in ((dict(features=torch.ones(P, 2, device=dev)), "features"), (dict(return_contrib=True), "return_contrib"),
                      (dict(return_absgrad=True), "return_absgrad")):
         with pytest.raises(RuntimeError, match="return_distortion cannot be combined with %s" % what):
-            RZ.GaussianRasterizer(rs)(**args, **kw)
+            rasterize(rs, t, return_distortion=True, **kw)
     torch.cuda.synchronize()
 
 
@@ -419,18 +343,6 @@ def test_empty_and_all_culled_views():
 
 # ---- pts2render ---------------------------------------------------------------------------------------------------------------------------------------------
 
-def _batch(B):
-    import torch
-    from test_gpu_raster_depth_alpha import _batch_data
-    data = _batch_data(B)
-    nv = data["novel_view"]  # the cameras on the device (as training hands them over): no host copy inside pts2render
-    nv["world_view_transform"], nv["full_proj_transform"] = nv["world_view_transform"].cuda(), nv["full_proj_transform"].cuda()
-    for v in ("lmain", "rmain"):
-        data[v]["xyz"].requires_grad_(True)
-    torch.cuda.synchronize()
-    return data
-
-
 @pytest.mark.parametrize("form", ["batch", "loop"])
 def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
     """pts2render(with_distortion=True) at B = 4: 'distortion_pred' has the bits of four render_ex(distortion=True) calls on the same packed rows, the
@@ -459,11 +371,8 @@ def test_pts2render_against_four_render_ex_calls(form, monkeypatch):
 
     data2 = _batch(B)
     xyz, rgb, rot, scale, opacity, offsets = pack_views(data2)
-    offs = offsets.tolist()
     maps = []
-    for i in range(B):
-        sl = slice(offs[i], offs[i + 1])
-        r = render_api.render_ex(data2, i, xyz[sl], rgb[sl], rot[sl], scale[sl], opacity[sl], bg, distortion=True)
+    for i, sl, r in render_ex_rows(data2, (xyz, rgb, rot, scale, opacity), offsets, bg, distortion=True):
         assert set(r) == {"img", "depth", "alpha", "distortion"} and tuple(r["distortion"].shape) == (1, 64, 64)
         maps.append(r["distortion"])
     ref = torch.stack(maps)

@@ -9,68 +9,16 @@ geometry gradient is the plain run's plus the sum of the slice runs' (rounding a
 import numpy as np
 import pytest
 
+from raster_run import GEOM, batch, close as _close, run_view, scene, valu_fixture
+
 pytestmark = pytest.mark.gpu
 
-GEOM = ("means3D", "means2D", "opacities", "scales", "rotations")
+_valu = valu_fixture()  # the plain runs the feature runs are compared with use the VALU family too (the feature runs always do)
 
 
-@pytest.fixture(autouse=True)
-def _valu(monkeypatch):
-    """The plain runs the feature runs are compared with use the VALU family too (the feature runs always do)."""
-    monkeypatch.setenv("GPSGS_COMPOSITE", "valu")
-
-
-def _run(g, colors=None, bg=None, dpix=None, feats=None, gfeat=None, extras=False, aa=False, cam=False, shs=None, cov=None, feat_grad=True,
-         color_grad=True):
-    """One view through GaussianRasterizer (+ backward of sum(img * dpix) + sum(feat * gfeat) when either is given).
-    -> dict: img, radii, feat, depth, alpha (numpy), grads (numpy, incl. 'features' and the camera's when asked)."""
-    import torch
-    from gps_gaussian_amd import rasterizer as RZ
-    dev = torch.device("cuda:0")
-    src = dict(g)
-    if colors is not None:
-        src["colors"] = colors
-    names = ["means3D", "opacities"] + (["colors"] if shs is None else ["shs"]) + (["scales", "rotations"] if cov is None else ["cov3D_precomp"])
-    if shs is not None:
-        src["shs"] = shs
-    if cov is not None:
-        src["cov3D_precomp"] = cov
-    want = dpix is not None or gfeat is not None
-    t = {k: torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)).to(dev).requires_grad_(want and (color_grad or k != "colors")) for k in names}
-    m2 = torch.zeros_like(t["means3D"], requires_grad=want)
-    ft = None
-    if feats is not None:
-        ft = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev).requires_grad_(want and feat_grad)
-    bgv = g["bg"] if bg is None else np.asarray(bg, np.float32)
-    view = torch.from_numpy(g["view"]).to(dev).requires_grad_(cam)
-    proj = torch.from_numpy(g["proj"]).to(dev).requires_grad_(cam)
-    rs = RZ.GaussianRasterizationSettings(g["H"], g["W"], g["tanfovx"], g["tanfovy"], torch.from_numpy(bgv).to(dev), 1.0, view, proj, 3,
-                                          torch.from_numpy(g["campos"]).to(dev), False, False)
-    out = RZ.GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t.get("colors"), shs=t.get("shs"),
-                                    scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"),
-                                    return_depth_alpha=extras, antialiasing=aa, camera_grad=cam, features=ft)
-    r = {"img": out[0], "radii": out[1]}
-    if extras:
-        r["depth"], r["alpha"] = out[2], out[3]
-    if ft is not None:
-        r["feat"] = out[-1]
-        assert len(out) == (5 if extras else 3)
-    if want:
-        loss = 0
-        if dpix is not None:
-            loss = loss + (out[0] * torch.from_numpy(dpix).to(dev)).sum()
-        if gfeat is not None:
-            loss = loss + (r["feat"] * torch.from_numpy(gfeat).to(dev)).sum()
-        loss.backward()
-        gr = {k: t[k].grad.cpu().numpy() for k in names if t[k].grad is not None}
-        gr["means2D"] = m2.grad.cpu().numpy()
-        if ft is not None and feat_grad:
-            gr["features"] = ft.grad.cpu().numpy()
-        if cam:
-            gr["view"], gr["proj"] = view.grad.cpu().numpy(), proj.grad.cpu().numpy()
-        r["grads"] = gr
-    torch.cuda.synchronize()
-    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in r.items()}
+def _run(g, dpix=None, gfeat=None, **kw):
+    """run_view (+ backward of sum(img * dpix) + sum(feat * gfeat) when either is given)."""
+    return run_view(g, dict(img=dpix, feat=gfeat), **kw)
 
 
 def _slices(feats, gfeat=None):
@@ -91,14 +39,7 @@ def _slices(feats, gfeat=None):
 
 
 def _scene(kind):
-    from gps_gaussian_amd import synthetic as S
-    return S.make_scene(256, 30000) if kind == "256" else S.make_scene(1024, 600000)
-
-
-def _close(a, b, tol, what):
-    s = max(float(np.abs(b).max()), 1e-30)
-    err = float(np.abs(a - b).max())
-    assert err <= tol * s, "%s: max error %.3e > %.1e x scale %.3e" % (what, err, tol, s)
+    return scene("256" if kind == "256" else "config2")
 
 
 @pytest.mark.parametrize("kind,F", [("256", 1), ("256", 3), ("256", 8), ("256", 17), ("256", 64), ("cfg2", 3), ("cfg2", 17), ("cfg2", 64)])
@@ -319,15 +260,11 @@ def test_render_ex_features():
 def _batch_feature_data(B, F=5):
     """The depth / alpha tests' B-sample stage-2 batch (tests/golden pts2render fixture) plus an F-channel map per view."""
     import torch
-    from test_gpu_raster_depth_alpha import _batch_data
-    data = _batch_data(B)
+    data = batch(B)
     rng = np.random.default_rng(31)
     for v in ("lmain", "rmain"):
         shp = (B, F) + tuple(data[v]["img"].shape[2:])
         data[v]["sem"] = torch.from_numpy(rng.standard_normal(shp).astype(np.float32)).cuda().requires_grad_(True)
-        data[v]["xyz"].requires_grad_(True)
-    nv = data["novel_view"]  # the cameras on the device (as training hands them over): no host copy inside pts2render
-    nv["world_view_transform"], nv["full_proj_transform"] = nv["world_view_transform"].cuda(), nv["full_proj_transform"].cuda()
     return data
 
 

@@ -36,6 +36,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_grad_parity, fragile_bounds, gaussians, hip_render, oracle_render, simple_scene
+from raster_run import GEOM, check_absgrad_structure, check_against_plain, check_contrib_structure, close, close_each, pad, run_view
 
 RGB_TOL = 1e-4
 SIZE = 16
@@ -323,11 +324,8 @@ def _replays(kind, n):
 @pytest.mark.parametrize("kind,n", OPT_IN_SCENES, ids=["%s_%d" % s for s in OPT_IN_SCENES])
 def test_opt_in_walks_at_round_boundaries(kind, n, lists, monkeypatch):
     """The feature-map, depth / alpha, contribution and absgrad kernels have walk loops of their own: the identities and replays their own tests rely
-    on (driven through those tests' own entry points), on lists that end at a round boundary and on pixels that stop on either side of one."""
-    import test_gpu_raster_absgrad as TA
-    import test_gpu_raster_contrib as TC
-    import test_gpu_raster_depth_alpha as TD
-    import test_gpu_raster_features as TF
+    on (through the runner and the checks those tests share, tests/raster_run.py), on lists that end at a round boundary and on pixels that stop on
+    either side of one."""
     monkeypatch.setenv("GPSGS_COMPOSITE", "valu")   # (what the opt-in kernels are compared with; they always are VALU kernels)
     ref = _reference(kind, n)
     _assert_scene_is_valid(kind, n, ref)
@@ -340,9 +338,9 @@ def test_opt_in_walks_at_round_boundaries(kind, n, lists, monkeypatch):
     (rw, rm, rn), aref = _replays(kind, n)
 
     # F = 3 features equal to the colours (background 0): the feature map has the image's bits; dL/dfeatures is a plain run's dL/dcolours
-    plain = TF._run(g, dpix=dpix)
-    plain2 = TF._run(g, dpix=dpix2)
-    feat = TF._run(g, dpix=dpix, feats=g["colors"], gfeat=dpix2)
+    plain = run_view(g, dict(img=dpix))
+    plain2 = run_view(g, dict(img=dpix2))
+    feat = run_view(g, dict(img=dpix, feat=dpix2), feats=g["colors"])
     np.testing.assert_array_equal(feat["img"], plain["img"])
     np.testing.assert_array_equal(feat["radii"], plain["radii"])
     np.testing.assert_array_equal(feat["feat"], plain["img"])
@@ -352,42 +350,43 @@ def test_opt_in_walks_at_round_boundaries(kind, n, lists, monkeypatch):
     reached = rn > 0   # (a Gaussian behind every pixel's stop is blended nowhere: both gradients are exactly zero)
     assert (b[reached] > 0).all() and not b[~reached].any() and reached.sum() >= ref["n_contrib"].max() - (~ref["solid"]).sum()
     assert (np.abs(a - b) <= 2 * 257 * 2.0 ** -24 * b).all(), float((np.abs(a - b)[reached] / b[reached]).max())
-    for k in TF.GEOM:
-        TF._close(feat["grads"][k], plain["grads"][k].astype(np.float64) + plain2["grads"][k], 1e-5, k)
+    for k in GEOM:
+        close(feat["grads"][k], plain["grads"][k].astype(np.float64) + plain2["grads"][k], 1e-5, k)
 
     # depth / alpha maps and their gradients equal a plain run with colours (z, 1, 0)
-    _, alp, _, _, _ = TD._check_against_plain(g, dd, da)
+    _, alp, _, _, _ = check_against_plain(g, dd, da)
     assert 0.0 <= alp.min() and alp.max() <= 1.0
 
     # contribution statistics and absgrad on / off: image, maps and every gradient keep their bits
-    off = TA._run(g, absgrad=False, dpix=dpix, extras=True, gdepth=dd[None], galpha=da[None])
-    on = TA._run(g, absgrad=True, contrib=True, dpix=dpix, extras=True, gdepth=dd[None], galpha=da[None])
+    cot = dict(img=dpix, depth=dd[None], alpha=da[None])
+    off = run_view(g, cot, extras=True)
+    on = run_view(g, cot, extras=True, contrib=True, absgrad=True)
     np.testing.assert_array_equal(off["img"], plain["img"])
     for k in ("img", "radii", "depth", "alpha"):
         np.testing.assert_array_equal(on[k], off[k], err_msg=k)
     assert set(on["grads"]) == set(off["grads"])
     for k in off["grads"]:
         np.testing.assert_array_equal(on["grads"][k], off["grads"][k], err_msg=k)
-    TA._check_structure(on)
-    TC._check_structure(on)
+    check_absgrad_structure(on)
+    check_contrib_structure(on)
     s_w, s_a = float(on["w"].astype(np.float64).sum()), float(on["alpha"].astype(np.float64).sum())
     assert abs(s_w - s_a) <= 1e-5 * s_a
 
     # ... and against the replays of the oracle's blend (the image's gradient alone, as the replays take it)
-    both = TA._run(g, absgrad=True, contrib=True, dpix=dpix)
+    both = run_view(g, dict(img=dpix), contrib=True, absgrad=True)
     for k in plain["grads"]:
         np.testing.assert_array_equal(both["grads"][k], plain["grads"][k], err_msg=k)
     ok = ~ref["touched"]
     np.testing.assert_array_equal(both["n"][ok], rn[ok])
-    assert TC._close(both["w"][ok], rw[ok]).all() and TC._close(both["m"][ok], rm[ok]).all()
+    assert close_each(both["w"][ok], rw[ok]).all() and close_each(both["m"][ok], rm[ok]).all()
     if kind == "full":
         assert ok.all() and (both["n"] == SIZE * SIZE).all()   # every Gaussian is blended into every pixel
-    assert_grad_parity({"means2D": TA._pad(both["abs"])}, {"means2D": TA._pad(aref)}, ref["touched"], ref["oradii"] > 0, bounds=ref["bounds"],
+    assert_grad_parity({"means2D": pad(both["abs"])}, {"means2D": pad(aref)}, ref["touched"], ref["oradii"] > 0, bounds=ref["bounds"],
                        strict_min=0.0)
     # one pixel in the loss: one term per Gaussian, so the absolute sum is the magnitude of the signed one
     one = np.zeros_like(dpix)
     one[:, 5, 9] = (0.7, -1.3, 0.4)
-    s = TA._run(g, dpix=one)
+    s = run_view(g, dict(img=one), absgrad=True)
     sref = np.abs(s["grads"]["means2D"][:, :2])
     assert (sref > 0).any()
     assert (np.abs(s["abs"] - sref) <= 1e-4 * sref + 1e-6 * sref.max()).all(), np.abs(s["abs"] - sref).max()

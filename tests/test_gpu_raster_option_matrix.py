@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, simple_scene
+from raster_run import output_table
 
 pytestmark = pytest.mark.gpu
 
@@ -60,18 +61,10 @@ def _run_view(c):
                                  return_depth_alpha="depth_alpha" in c, antialiasing="antialiasing" in c, camera_grad="camera_grad" in c,
                                  features=feats, return_contrib="contrib" in c, return_absgrad="absgrad" in c)
     # the documented order, shapes and dtypes
-    want = [("color", (3, H, W), torch.float32, True), ("radii", (P,), torch.int32, False)]
-    if "depth_alpha" in c:
-        want += [("depth", (1, H, W), torch.float32, True), ("alpha", (1, H, W), torch.float32, True)]
-    if "features" in c:
-        want += [("feat", (F, H, W), torch.float32, True)]
-    if "contrib" in c:
-        want += [("contrib_weight", (P,), torch.float32, False), ("contrib_max", (P,), torch.float32, False), ("contrib_pixels", (P,), torch.int32, False)]
-    if "absgrad" in c:
-        want += [("absgrad", (P, 2), torch.float32, False)]
+    want = output_table(P, H, W, extras="depth_alpha" in c, F=F if "features" in c else 0, contrib="contrib" in c, absgrad="absgrad" in c)
     assert isinstance(out, tuple) and len(out) == len(want), (sorted(c), len(out))
     for x, (name, shape, dtype, diff) in zip(out, want):
-        assert tuple(x.shape) == shape and x.dtype == dtype and x.requires_grad == diff and x.device == dev, (sorted(c), name)
+        assert tuple(x.shape) == shape and x.dtype == getattr(torch, dtype) and x.requires_grad == diff and x.device == dev, (sorted(c), name)
     named = dict(zip((w[0] for w in want), out))
     if "absgrad" in c:
         assert float(named["absgrad"].abs().max()) == 0.0  # zeros until a backward has run

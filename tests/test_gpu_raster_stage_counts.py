@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import gaussians, simple_scene
+from raster_run import output_table
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +34,8 @@ def _counts(options, stage=None):
     try:
         _capi.timing_read()  # (drop what earlier calls recorded)
         out = RZ.rasterize_gaussians(t["means3D"], m2, None, t["colors"], t["opacities"], t["scales"], t["rotations"], None, rs, **options)
-        loss = out[0].sum() + (out[2].sum() if options.get("features") is not None else 0.0)  # (the feature map follows colour and radii)
+        fmap = [row[0] for row in output_table(n, 16, 16, F=F)].index("feat")
+        loss = out[0].sum() + (out[fmap].sum() if options.get("features") is not None else 0.0)
         loss.backward()
         torch.cuda.synchronize()
         assert int((out[1] > 0).sum()) > 20  # the view is not empty
