@@ -3,7 +3,7 @@
 Layout:
   csrc/        hand-written HIP kernels for gfx950 + the C-ABI (include/gpsgs.h) -> lib/libgpsgs_hip.so
   _capi.py     ctypes binding of that C-ABI (the only place the .so is touched): one table of prototypes, no torch at import
-  _ops.py      the one way an op module calls it: ptr / call / device_guard, DTYPE_CODE, aligned16, autocast_dtype
+  _ops.py      the one way an op module calls it: ptr / call / device_guard, DTYPE_CODE, aligned16, autocast_dtype; what the converted layers share
   rasterizer.py  GaussianRasterizationSettings / GaussianRasterizer (drop-in for `diff_gaussian_rasterization`)
   corr.py      forward / backward (drop-in for `corr_sampler`)
   render_api.py  render(data, idx, ...) / pts2render(data, bg_color) with the reference's signatures

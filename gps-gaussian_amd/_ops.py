@@ -1,6 +1,9 @@
 """The one way an op module calls the C-ABI: pointers as plain ints, the current stream appended, the device guard only when it is needed, the
-return code checked under the entry point's own name.  The tensor-aware side of _capi.py (which stays free of torch)."""
+return code checked under the entry point's own name.  The tensor-aware side of _capi.py (which stays free of torch).  And what the converted
+layers (groupnorm.py, stemconv.py, gshead.py) say in the same words: how a parameter reaches a kernel, which input and parameters a fused
+forward takes, and the two walks over a module tree that convert it in place."""
 import torch
+from torch import nn
 
 from . import _capi
 
@@ -45,3 +48,34 @@ def aligned16(t):
 def autocast_dtype():
     get = getattr(torch, "get_autocast_dtype", None)      # newer torch; the older accessor warns there
     return get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
+
+
+def fp32_on(dev, weight, bias):
+    """A layer's weight and bias as the kernels read them: detached, fp32, on `dev`, contiguous (one call for the pair: this is on every forward)."""
+    return weight.detach().to(device=dev, dtype=torch.float32).contiguous(), bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def dense_fp32_call(m, x):
+    """x is a contiguous 4-D fp32 GPU tensor with elements in it (not: CPU, fp16 / bf16, empty, channels-last or any other strided view) and the
+    layer m has a bias and keeps it and its weight in fp32 on x's device (one predicate for both: this is on every forward)."""
+    return x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.is_contiguous() and m.bias is not None \
+        and m.weight.dtype == torch.float32 and m.bias.dtype == torch.float32 and m.weight.device == x.device
+
+
+def swap_class(module, old, new, test=None):
+    """Every module of exactly type `old` in `module`'s tree (the module itself included; one reachable through two parents once) that passes
+    `test` becomes a `new`, in place: the instance keeps its parameters, buffers, hooks and state_dict keys.  Returns the number swapped."""
+    n = 0
+    for m in module.modules():
+        if type(m) is old and (test is None or test(m)):
+            m.__class__ = new
+            n += 1
+    return n
+
+
+def sequential_slots(module):
+    """(seq, i) for every pair of adjacent slots i, i + 1 of every nn.Sequential in `module`'s tree (the module itself included)."""
+    for seq in list(module.modules()):
+        if isinstance(seq, nn.Sequential):
+            for i in range(len(seq) - 1):
+                yield seq, i

@@ -1,80 +1,63 @@
 """Opt-in: let the reference's UNMODIFIED scripts reach the fused kernels of SURVEY.md section 8(f).
 
 The two drop-in import names (`diff_gaussian_rasterization`, `corr_sampler`) replace external extensions, so the reference reaches them by
-importing.  The four "(f) next" rows replace code that lives INSIDE the reference (lib/GaussianRender.py:6-40 `pts2render`, lib/loss.py:36-83
-`l1_loss` / `ssim`, core/corr.py:31-61 `CorrBlockFast1D`, core/raft_stereo_human.py:69-81 `upsample_flow`, lib/utils.py:88-120
-`flow2depth` / `depth2pc`), so an unmodified `train_stage2.py` / `test_view_interp.py` never calls them -- unless asked to:
+importing.  Everything below replaces code that lives INSIDE the reference, which an unmodified `train_stage2.py` / `test_view_interp.py` never
+hands over -- unless asked to:
 
     GPSGS_ACCELERATE=pack,loss,corr,upsample,unproject   (or "all"; unset / empty = off, the default)
 
 With the variable set, importing either drop-in installs a `sys.meta_path` finder that lets the reference's modules load from where they lie,
-untouched, and -- after each one has executed -- rebinds the names above to the fused implementations of this package: in the defining module
-and in every loaded module that had already bound the same object with `from ... import ...` (train_stage2.py:16-17 bind `pts2render`,
-`l1_loss`, `ssim` after `lib.network` -> `core.corr` has imported `corr_sampler` at :13, i.e. after this hook is in place).  No reference file
-changes on disk; nothing here runs unless the variable is set; every replacement is the GPU path of this package (no CPU fallback).
+untouched, and -- after each one has executed -- rebinds the rows of `_ROWS` to this package: in the defining module and in every loaded module
+that had already bound the same object with `from ... import ...` (train_stage2.py:16-17 bind `pts2render`, `l1_loss`, `ssim` after
+`lib.network` -> `core.corr` has imported `corr_sampler` at :13, i.e. after this hook is in place).  No reference file changes on disk; nothing
+here runs unless the variable is set; every replacement is the GPU path of this package (no CPU fallback).
 
-One more name is opt-in only, outside "all" (which keeps meaning the five features above): `splat` (GPSGS_ACCELERATE=splat or all,splat).
-lib/TaichiRender.py cannot be imported on this card at all (`import taichi`, `ti.init(ti.cuda)`), so instead of rebinding names after the
-reference's module ran, the finder SERVES a substitute module for `lib.TaichiRender` that exports this package's `splat.TaichiRenderBatch`; the
-reference's file is never executed.  That is what lets train_stage1.py (:16 imports it, after lib.network -> core.corr has imported corr_sampler
-at :11-12, i.e. after this hook is in place) import and run its validation render.
+  name       "all"  what it rebinds or wraps in the reference                                               implemented in
+  pack       yes    lib/GaussianRender.py:6-40 `pts2render`                                                 render_api.py
+  loss       yes    lib/loss.py:36-83 `l1_loss`, `ssim`                                                     loss.py
+  corr       yes    core/corr.py:31-61 `CorrBlockFast1D`                                                    corr.py
+  upsample   yes    core/raft_stereo_human.py:69-81 `FlowUpdateModule.upsample_flow`                        corr.py
+  unproject  yes    lib/utils.py:88-120 `flow2depth`, `depth2pc`                                            unproject.py
+  splat      no     lib/TaichiRender.py, SERVED by the finder instead of executed (`import taichi`,         splat.py
+                    `ti.init(ti.cuda)` cannot run on this card): what lets train_stage1.py:16 import it
+  groupnorm  no     wraps core/extractor.py:7, :64 `ResidualBlock.__init__`, `UnetExtractor.__init__`:      groupnorm.py
+                    after the reference's own constructor every nn.GroupNorm is a FusedGroupNorm
+  resblock   no     `groupnorm`, plus core/extractor.py:48 `ResidualBlock.forward` with each norm + ReLU    groupnorm.py
+                    and the closing add + ReLU in one op, and the stem's (:66-70) ReLU folded into its norm
+  stemconv   no     wraps `UnetExtractor.__init__`: the stem's Conv2d(3 | 1, 32, 5, stride 2, padding 2)    stemconv.py
+                    (`in_ds[0]`, core/extractor.py:66-70) becomes a FusedStemConv2d
+  gshead     no     wraps lib/gs_parm_network.py:8 `GSRegresser.__init__`: the ReLU -> Conv2d(32, 4|3|1, 1) gshead.py
+                    -> nothing | Softplus | Sigmoid tail of its three heads (:34-50) becomes a FusedHeadConv
 
-A second opt-in name, `groupnorm` (GPSGS_ACCELERATE=groupnorm or all,groupnorm), replaces no function of the reference: it wraps the constructors
-of the two classes of core/extractor.py that build `nn.GroupNorm` layers (ResidualBlock, UnetExtractor).  Each wrapper runs the reference's own
-`__init__` and then `groupnorm.convert(self)`, which turns those layers into `FusedGroupNorm` (this package's chip-wide GroupNorm kernels; same
-parameters, same state_dict).  The reference's `forward` bodies run as they are.  Instances are built long after import, so the import order of
-core.extractor against the drop-in does not matter.
-
-A third, `resblock` (GPSGS_ACCELERATE=resblock; its own tuple OPT_IN_FUSED, never implied by "all" either), goes one step further than `groupnorm`,
-which it implies: besides the conversion it rebinds `core.extractor.ResidualBlock.forward` to `groupnorm.residual_block_forward` -- the same block
-with each `relu_(norm(conv(.)))` and the closing `relu(x + y)` inside the GroupNorm kernels -- and the wrapped `UnetExtractor.__init__` runs
-`groupnorm.fuse_sequential_relu(self)`, which folds the stem's Conv -> GroupNorm -> ReLU the same way.  One wrapper per constructor serves both
-names (`_originals` is keyed by attribute); with `groupnorm` alone exactly the two constructors are wrapped and every forward body is the reference's.
-
-A fourth, `stemconv` (GPSGS_ACCELERATE=stemconv; its own tuple OPT_IN_CONV, never implied by "all" or by the names above), makes the wrapped
-`UnetExtractor.__init__` run `stemconv.convert(self)`: the full-resolution `Conv2d(3 | 1, 32, 5, stride 2, padding 2)` that opens each encoder
-(`in_ds[0]`, core/extractor.py:66-70) becomes a `FusedStemConv2d` on the direct-convolution kernels of csrc/stem_conv.hip.  The wrapper is the one
-`groupnorm` / `resblock` use and does only what was asked: `stemconv` alone leaves every norm an `nn.GroupNorm` (and ResidualBlock, which has no such
-layer, unwrapped); `groupnorm` or `resblock` alone leave `in_ds[0]` a plain `nn.Conv2d`.
-
-A fifth, `gshead` (GPSGS_ACCELERATE=gshead; its own tuple OPT_IN_HEAD, never implied by "all" or by the names above), wraps the constructor of
-lib/gs_parm_network.py's GSRegresser the same way: after the reference's `__init__` the wrapper runs `gshead.convert(self)`, which turns the
-ReLU -> Conv2d(32, 4 | 3 | 1, 1) -> nothing | Softplus | Sigmoid tail of `rot_head`, `scale_head` and `opacity_head` (:34-50) into one
-`FusedHeadConv` each on the kernels of csrc/gshead.hip, with nn.Identity in the ReLU's and the activation's slots.  That wrapper converts heads and
-nothing else; the encoder and block constructors GSRegresser calls are wrapped, or not, by the names above as before.  `GSRegresser.forward` (its
-`F.normalize` and `clamp_max` included) runs as it is.
+The names outside "all" are accepted by name only (`all,splat`, `resblock,stemconv`, ...) and imply nothing but what their line says.  A wrapped
+constructor runs the reference's own `__init__` and then the conversions that were asked for (`_ENCODER_STEPS`, `_HEAD_STEPS`): same parameters, same state_dict; the
+reference's `forward` bodies run as they are, `resblock`'s one rebinding apart.  Instances are built long after import, so the import order of
+these modules against the drop-in does not matter.  One wrapper per constructor serves every name that asks for it and does only what was asked:
+`stemconv` alone leaves every norm an `nn.GroupNorm` (and ResidualBlock, which has no stem, unwrapped), `groupnorm` alone leaves `in_ds[0]` a
+plain `nn.Conv2d`, `gshead` touches the heads and nothing else.
 
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
+import importlib
 import importlib.abc
 import importlib.util
 import os
 import sys
 import threading
 
-FEATURES = ("pack", "loss", "corr", "upsample", "unproject")
-OPT_IN = ("splat", "groupnorm")   # accepted by name only, never implied by "all"
-OPT_IN_FUSED = ("resblock",)      # likewise by name only; implies the groupnorm conversion and replaces ResidualBlock.forward (see above)
-OPT_IN_CONV = ("stemconv",)       # likewise by name only: the encoders' stem convolutions (see above)
-OPT_IN_HEAD = ("gshead",)         # likewise by name only: the ReLU -> 1x1 convolution -> activation tails of the Gaussian heads (see above)
+FEATURES = ("pack", "loss", "corr", "upsample", "unproject")          # what "all" means
+OPT_IN = ("splat", "groupnorm", "resblock", "stemconv", "gshead")     # accepted by name only, never implied by "all"
+# features that count, under <name>_passthrough, the calls that went THROUGH a replacement but were handed on to the reference's or torch's own
+# code (a configuration the fused kernel does not implement: ssim with another window, CPU tensors, channels-last, norm_fn batch, ...), so that a
+# run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
+_PASSTHROUGH = ("loss", "unproject", "groupnorm", "resblock", "stemconv", "gshead")
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
-calls = {f: 0 for f in FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV + OPT_IN_HEAD}
-# calls that went THROUGH a replacement but were handed on to the reference's own function (a configuration the fused kernel does not implement):
-# counted, so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
-calls["loss_passthrough"] = 0
-calls["unproject_passthrough"] = 0
-calls["groupnorm_passthrough"] = 0   # FusedGroupNorm forwards handed to nn.GroupNorm.forward (CPU, channels-last, bf16, ...: groupnorm.py)
-calls["resblock_passthrough"] = 0    # residual blocks without GroupNorm layers (norm_fn batch / instance / none): the reference's own forward
-calls["stemconv_passthrough"] = 0    # FusedStemConv2d forwards handed to nn.Conv2d.forward (CPU, channels-last, bf16 autocast, ...: stemconv.py)
-calls["gshead_passthrough"] = 0      # FusedHeadConv forwards computed with torch.relu / nn.Conv2d.forward / the activation (CPU, channels-last, ...: gshead.py)
-_convert_norms = False   # set while `groupnorm` or `resblock` is requested: the constructor wrappers then run groupnorm.convert
-_convert_convs = False   # set while `stemconv` is requested: the UnetExtractor wrapper then runs stemconv.convert
-_convert_heads = False   # set while `gshead` is requested: the GSRegresser wrapper then runs gshead.convert
-_fuse_relu = False       # set while `resblock` is requested: the constructor wrappers then also run groupnorm.fuse_sequential_relu
+calls = {k: 0 for k in FEATURES + OPT_IN + tuple(f + "_passthrough" for f in _PASSTHROUGH)}
+_asked = set()           # the opt-in names apply() has been given so far: what the constructor wrappers convert (_ENCODER_STEPS, _HEAD_STEPS)
 _installed = {}          # "module.attr" -> feature
-_originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), and the two pass-through cases below
+_originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), original(), and the two pass-through cases below
 _armed = False           # set by install(); cleared once every requested name is rebound (late_apply() is then a flag test)
 _lock = threading.RLock()
 _finder = None
@@ -91,7 +74,7 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN + OPT_IN_FUSED + OPT_IN_CONV + OPT_IN_HEAD
+    known = FEATURES + OPT_IN
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
@@ -100,6 +83,14 @@ def requested(value=None):
 
 def installed():
     return dict(_installed)
+
+
+def original(obj, name):
+    """The reference's own attribute `name` that was rebound on the class of `obj` (or on a base of it); None if none was."""
+    for holder, n, orig in list(_originals.values()):
+        if n == name and isinstance(holder, type) and isinstance(obj, holder):
+            return orig
+    return None
 
 
 # ---- the replacements (thin: argument shapes of the reference on the outside, this package's fused ops inside) -------------------------
@@ -153,32 +144,27 @@ def _depth2pc(depth, extrinsic, intrinsic):
     return _originals["lib.utils.depth2pc"][2](depth, extrinsic, intrinsic)
 
 
-def _converting_init(key, heads=False):
-    """core/extractor.py:7, :64 -- the reference's own constructor (from _originals), then whatever was asked for: this package's GroupNorm layers in
-    place of nn.GroupNorm (`groupnorm`, `resblock`), the stem's ReLU folded into its norm (`resblock`), the stem convolution (`stemconv`).
-    heads=True, lib/gs_parm_network.py:8 -- the constructor of the class that owns the Gaussian heads: their tails (`gshead`) and nothing else; the
-    encoder and the blocks it builds went through their own wrappers inside the reference's constructor."""
+# what a wrapped constructor runs on the new instance, in this order: (the names that ask for the step, module of this package, function)
+_ENCODER_STEPS = ((("groupnorm", "resblock"), "groupnorm", "convert"),             # nn.GroupNorm -> FusedGroupNorm
+                  (("resblock",), "groupnorm", "fuse_sequential_relu"),            # the stem's ReLU folded into its norm
+                  (("stemconv",), "stemconv", "convert"))                          # the stem convolution
+# the heads' tails and nothing else: the encoder and the blocks GSRegresser builds went through their own wrappers inside its constructor
+_HEAD_STEPS = ((("gshead",), "gshead", "convert"),)
+
+
+def _converting_init(key, steps):
+    """The reference's own constructor (from _originals), then the steps whose names were asked for."""
     def __init__(self, *args, **kwargs):
         _originals[key][2](self, *args, **kwargs)
-        if heads:
-            if _convert_heads:
-                from . import gshead
-                gshead.convert(self)
-            return
-        if _convert_norms:
-            from . import groupnorm
-            groupnorm.convert(self)
-            if _fuse_relu:
-                groupnorm.fuse_sequential_relu(self)
-        if _convert_convs:
-            from . import stemconv
-            stemconv.convert(self)
+        for names, module, function in steps:
+            if not _asked.isdisjoint(names):
+                getattr(importlib.import_module("." + module, __package__), function)(self)
     return __init__
 
 
-_resblock_init = _converting_init("core.extractor.ResidualBlock.__init__")
-_unet_init = _converting_init("core.extractor.UnetExtractor.__init__")
-_regresser_init = _converting_init("lib.gs_parm_network.GSRegresser.__init__", heads=True)
+_resblock_init = _converting_init("core.extractor.ResidualBlock.__init__", _ENCODER_STEPS)      # core/extractor.py:7
+_unet_init = _converting_init("core.extractor.UnetExtractor.__init__", _ENCODER_STEPS)          # core/extractor.py:64
+_regresser_init = _converting_init("lib.gs_parm_network.GSRegresser.__init__", _HEAD_STEPS)     # lib/gs_parm_network.py:8
 
 
 def _resblock_forward(self, x):
@@ -205,28 +191,33 @@ def _corr_block():
     return _corr_cls
 
 
+_FACTORIES = (_corr_block,)   # replacements made on first use (they import their op module): called with no argument for the object to bind
+
+# (defining module, attribute or 'Class.attr', replacement, the names that ask for the row).  A row is filed -- in _table(), installed() -- under
+# the first REQUESTED name of its list: one wrapper per constructor, whichever name asks (`groupnorm` and `resblock`: filed under `groupnorm`;
+# `stemconv` alone: only the class that has a stem)
+_ROWS = (
+    ("lib.GaussianRender", "pts2render", _pts2render, ("pack",)),
+    ("lib.loss", "l1_loss", _l1_loss, ("loss",)),
+    ("lib.loss", "ssim", _ssim, ("loss",)),
+    ("core.corr", "CorrBlockFast1D", _corr_block, ("corr",)),
+    ("core.raft_stereo_human", "FlowUpdateModule.upsample_flow", _upsample_flow, ("upsample",)),
+    ("lib.utils", "flow2depth", _flow2depth, ("unproject",)),
+    ("lib.utils", "depth2pc", _depth2pc, ("unproject",)),
+    ("core.extractor", "ResidualBlock.__init__", _resblock_init, ("groupnorm", "resblock")),
+    ("core.extractor", "UnetExtractor.__init__", _unet_init, ("groupnorm", "resblock", "stemconv")),
+    ("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init, ("gshead",)),
+    ("core.extractor", "ResidualBlock.forward", _resblock_forward, ("resblock",)),
+)
+
+
 def _table(features):
-    """feature -> [(defining module, attribute or 'Class.attr', replacement)]."""
+    """feature -> [(defining module, attribute or 'Class.attr', replacement)], with an entry for every requested feature."""
     t = {f: [] for f in features}
-    if "pack" in t:
-        t["pack"].append(("lib.GaussianRender", "pts2render", _pts2render))
-    if "loss" in t:
-        t["loss"] += [("lib.loss", "l1_loss", _l1_loss), ("lib.loss", "ssim", _ssim)]
-    if "corr" in t:
-        t["corr"].append(("core.corr", "CorrBlockFast1D", _corr_block()))
-    if "upsample" in t:
-        t["upsample"].append(("core.raft_stereo_human", "FlowUpdateModule.upsample_flow", _upsample_flow))
-    if "unproject" in t:
-        t["unproject"] += [("lib.utils", "flow2depth", _flow2depth), ("lib.utils", "depth2pc", _depth2pc)]
-    if "groupnorm" in t or "resblock" in t:   # one wrapper per constructor, whichever of the two names asks (both: filed under groupnorm)
-        t["groupnorm" if "groupnorm" in t else "resblock"] += [("core.extractor", "ResidualBlock.__init__", _resblock_init),
-                                                                ("core.extractor", "UnetExtractor.__init__", _unet_init)]
-    elif "stemconv" in t:                     # the stem convolution alone: only the class that has one
-        t["stemconv"].append(("core.extractor", "UnetExtractor.__init__", _unet_init))
-    if "gshead" in t:
-        t["gshead"].append(("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init))
-    if "resblock" in t:
-        t["resblock"].append(("core.extractor", "ResidualBlock.forward", _resblock_forward))
+    for modname, attr, repl, names in _ROWS:
+        feat = next((n for n in names if n in t), None)
+        if feat is not None:
+            t[feat].append((modname, attr, repl() if repl in _FACTORIES else repl))
     return t
 
 
@@ -244,16 +235,12 @@ def _loaded(name):
 def apply(features=None):
     """Rebind whatever can be rebound NOW (idempotent; called after every reference module finishes loading).  Returns the number of new
     bindings made."""
-    global _fuse_relu, _convert_norms, _convert_convs, _convert_heads
     feats = requested() if features is None else tuple(features)
     if not feats:
         return 0
     made = 0
     with _lock:
-        _fuse_relu = _fuse_relu or "resblock" in feats
-        _convert_norms = _convert_norms or "groupnorm" in feats or "resblock" in feats
-        _convert_convs = _convert_convs or "stemconv" in feats
-        _convert_heads = _convert_heads or "gshead" in feats
+        _asked.update(f for f in feats if f in OPT_IN)
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -290,7 +277,6 @@ def apply(features=None):
 
 def restore():
     """Undo every rebinding (tests)."""
-    global _fuse_relu, _convert_norms, _convert_convs, _convert_heads
     with _lock:
         for key, (holder, name, orig) in list(_originals.items()):
             repl = holder.__dict__.get(name) if isinstance(holder, type) else getattr(holder, name, None)
@@ -302,7 +288,7 @@ def restore():
                         d[name] = orig
         _originals.clear()
         _installed.clear()
-        _fuse_relu = _convert_norms = _convert_convs = _convert_heads = False
+        _asked.clear()
         for k in calls:
             calls[k] = 0
 

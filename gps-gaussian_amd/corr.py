@@ -49,7 +49,7 @@ def forward(volume, coords, radius):
         _capi.lib()
         _first_call = False
         acc = sys.modules.get("gps_gaussian_amd.accelerate")  # first sampler call of the process: the opt-in hook's safety net (accelerate.py)
-        if acc is not None and acc._armed:
+        if acc is not None:
             acc.late_apply()
     N, H1, W1, W2, c = _args(volume, coords)
     radius = _radius(radius)

@@ -20,7 +20,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, ptr
+from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, fp32_on, ptr, sequential_slots, swap_class
 
 
 class _GroupNorm(torch.autograd.Function):
@@ -47,8 +47,7 @@ class _GroupNorm(torch.autograd.Function):
             raise RuntimeError("gps_gaussian_amd: group_norm: residual must be an fp32 GPU tensor of the input's shape %s" % (tuple(x.shape),))
         xc = aligned16(x.detach())
         res = aligned16(residual.detach()) if residual is not None else None
-        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+        w, b = fp32_on(dev, weight, bias)
         HW = xc.numel() // (N * Cn) if N * Cn else 0
         out = torch.empty(x.shape, dtype=torch.float32, device=dev)
         mean = torch.empty((N, G), dtype=torch.float32, device=dev)
@@ -162,12 +161,7 @@ def convert(module):
     """Make every nn.GroupNorm in `module`'s tree (the module itself included) a FusedGroupNorm, in place: the instance keeps its parameters, buffers,
     hooks and state_dict keys, only its class changes.  A module reachable through two parents is converted once; already converted modules and
     subclasses of nn.GroupNorm are left alone.  Returns the number converted."""
-    n = 0
-    for m in module.modules():
-        if type(m) is nn.GroupNorm:
-            m.__class__ = FusedGroupNorm
-            n += 1
-    return n
+    return swap_class(module, nn.GroupNorm, FusedGroupNorm)
 
 
 def fuse_sequential_relu(module):
@@ -179,23 +173,17 @@ def fuse_sequential_relu(module):
         for c in m.children():
             uses[id(c)] = uses.get(id(c), 0) + 1
     n = 0
-    for seq in module.modules():
-        if not isinstance(seq, nn.Sequential):
-            continue
-        for i in range(len(seq) - 1):
-            if type(seq[i]) in (nn.GroupNorm, FusedGroupNorm) and type(seq[i + 1]) is nn.ReLU and uses.get(id(seq[i]), 0) == 1:
-                seq[i].__class__ = FusedGroupNormReLU
-                seq[i + 1] = nn.Identity()
-                n += 1
+    for seq, i in sequential_slots(module):
+        if type(seq[i]) in (nn.GroupNorm, FusedGroupNorm) and type(seq[i + 1]) is nn.ReLU and uses.get(id(seq[i]), 0) == 1:
+            seq[i].__class__ = FusedGroupNormReLU
+            seq[i + 1] = nn.Identity()
+            n += 1
     return n
 
 
 def _own_forward(block):
     """The forward the block's class defines -- the reference's own where accelerate has rebound it to residual_block_forward."""
-    for holder, name, orig in list(accelerate._originals.values()):
-        if name == "forward" and isinstance(holder, type) and isinstance(block, holder):
-            return orig
-    return type(block).forward
+    return accelerate.original(block, "forward") or type(block).forward
 
 
 def _norm_relu(norm, y, residual=None):

@@ -16,7 +16,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-from ._ops import aligned16, call, ptr
+from ._ops import aligned16, call, dense_fp32_call, fp32_on, ptr, sequential_slots
 
 ACT_CODE = {"none": 0, "softplus": 1, "sigmoid": 2}   # the `act` argument of include/gpsgs.h
 
@@ -40,8 +40,7 @@ class _Head(torch.autograd.Function):
                                % (tuple(x.shape), tuple(weight.shape), act, beta))
         dev = x.device
         xc = aligned16(x.detach())
-        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+        w, b = fp32_on(dev, weight, bias)
         y = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
         cfg = (ACT_CODE[act], float(beta), float(threshold))
         call("gsr_head_forward", dev, ptr(xc), ptr(w), ptr(b), N, C, K, H, W, *cfg, ptr(y))
@@ -86,12 +85,8 @@ def _plain(conv):
 
 
 def _fusable(m, x):
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.is_contiguous()):
-        return False                                      # CPU, fp16 / bf16 input, empty, channels-last or any other strided view
-    if torch.is_autocast_enabled():
-        return False                                      # the heads run outside autocast (lib/network.py:32-33); inside it, ATen decides the dtypes
-    if m.bias is None or m.weight.dtype != torch.float32 or m.bias.dtype != torch.float32 or m.weight.device != x.device:
-        return False
+    if not dense_fp32_call(m, x) or torch.is_autocast_enabled():
+        return False                                      # ... the heads run outside autocast (lib/network.py:32-33); inside it, ATen decides the dtypes
     return x.shape[1] == m.in_channels and _plain(m) and m.act in ACT_CODE and (m.act != "softplus" or m.beta > 0)
 
 
@@ -123,25 +118,22 @@ def convert(module):
     slots become nn.Identity (they have no state), indices stay.  A ReLU followed by anything else, subclasses of these layers and already converted
     chains are left alone.  Returns the number converted."""
     n = 0
-    for seq in list(module.modules()):
-        if not isinstance(seq, nn.Sequential):
+    for seq, i in sequential_slots(module):
+        relu, conv = seq[i], seq[i + 1]
+        if type(relu) is not nn.ReLU or type(conv) is not nn.Conv2d or not _plain(conv):
             continue
-        for i in range(len(seq) - 1):
-            relu, conv = seq[i], seq[i + 1]
-            if type(relu) is not nn.ReLU or type(conv) is not nn.Conv2d or not _plain(conv):
-                continue
-            after = seq[i + 2] if i + 2 < len(seq) else None
-            act, beta, threshold = "none", 1.0, 20.0
-            if type(after) is nn.Softplus:
-                act, beta, threshold = "softplus", after.beta, after.threshold
-            elif type(after) is nn.Sigmoid:
-                act = "sigmoid"
-            if not supported(conv.in_channels, conv.out_channels, act):
-                continue
-            conv.__class__ = FusedHeadConv
-            conv.act, conv.beta, conv.threshold = act, beta, threshold
-            seq[i] = nn.Identity()
-            if act != "none":
-                seq[i + 2] = nn.Identity()
-            n += 1
+        after = seq[i + 2] if i + 2 < len(seq) else None
+        act, beta, threshold = "none", 1.0, 20.0
+        if type(after) is nn.Softplus:
+            act, beta, threshold = "softplus", after.beta, after.threshold
+        elif type(after) is nn.Sigmoid:
+            act = "sigmoid"
+        if not supported(conv.in_channels, conv.out_channels, act):
+            continue
+        conv.__class__ = FusedHeadConv
+        conv.act, conv.beta, conv.threshold = act, beta, threshold
+        seq[i] = nn.Identity()
+        if act != "none":
+            seq[i + 2] = nn.Identity()
+        n += 1
     return n

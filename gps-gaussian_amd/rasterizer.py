@@ -1054,8 +1054,8 @@ class GaussianRasterizer(nn.Module):
         super().__init__()
         self.raster_settings = raster_settings
         acc = sys.modules.get("gps_gaussian_amd.accelerate")  # present only when GPSGS_ACCELERATE is set (opt-in, accelerate.py)
-        if acc is not None and acc._armed:
-            acc.late_apply()
+        if acc is not None:
+            acc.late_apply()                                  # a flag test once everything requested is rebound
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
                 grad_arena=None, return_depth_alpha=False, antialiasing=False, camera_grad=False, features=None, return_contrib=False,

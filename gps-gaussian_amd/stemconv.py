@@ -16,7 +16,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, ptr
+from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, dense_fp32_call, fp32_on, ptr, swap_class
 
 
 def _pair(v):
@@ -49,8 +49,7 @@ class _StemConv(torch.autograd.Function):
                                % (tuple(x.shape), tuple(weight.shape), s, p))
         dev = x.device
         xc = aligned16(x.detach())
-        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        b = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+        w, b = fp32_on(dev, weight, bias)
         Ho, Wo = (H + 2 * p - K) // s + 1, (W + 2 * p - K) // s + 1
         y = torch.empty((N, Co, Ho, Wo), dtype=out_dtype, device=dev)
         call("sc_forward", dev, ptr(xc), ptr(w), ptr(b), N, Ci, Co, H, W, K, s, p, ptr(y), DTYPE_CODE[out_dtype])
@@ -88,11 +87,7 @@ def conv2d(x, weight, bias, stride, padding, *, out_dtype=torch.float32):
 
 def _out_dtype(m, x):
     """The dtype the fused op returns for this call (ATen's), or None: the call is nn.Conv2d.forward's."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.is_contiguous()):
-        return None                                       # CPU, fp16 / bf16 input, empty, channels-last or any other strided view
-    if m.bias is None or m.padding_mode != "zeros":
-        return None
-    if m.weight.dtype != torch.float32 or m.bias.dtype != torch.float32 or m.weight.device != x.device:
+    if not dense_fp32_call(m, x) or m.padding_mode != "zeros":
         return None
     if x.shape[1] != m.in_channels or not supported(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups):
         return None
@@ -120,10 +115,5 @@ def convert(module):
     """Make every nn.Conv2d in `module`'s tree (the module itself included) whose static configuration the kernels implement a FusedStemConv2d, in
     place: the instance keeps its parameters, hooks and state_dict keys, only its class changes.  Subclasses of nn.Conv2d, layers without a bias or
     with another padding mode, and already converted modules are left alone.  Returns the number converted."""
-    n = 0
-    for m in module.modules():
-        if type(m) is nn.Conv2d and m.bias is not None and m.padding_mode == "zeros" and \
-                supported(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups):
-            m.__class__ = FusedStemConv2d
-            n += 1
-    return n
+    return swap_class(module, nn.Conv2d, FusedStemConv2d, lambda m: m.bias is not None and m.padding_mode == "zeros" and supported(
+        m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups))

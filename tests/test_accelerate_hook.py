@@ -5,41 +5,11 @@ Each case runs in a fresh interpreter with the integration path (dropin ahead of
 `train_stage2.py` / `test_view_interp.py` as modules: the import ORDER of those files (train_stage2.py:12-17: lib.human_loader, lib.network ->
 core.raft_stereo_human -> core.corr -> `import corr_sampler` (the hook goes in here), ..., lib.GaussianRender, lib.loss) is what the hook has to cope
 with.  The reference is the checkout in the build container; the tests skip where there is none."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import pytest
 
-from conftest import ROOT
+import hook_run as H
 
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv  # noqa: E402
-
-REF = refenv.reference_dir()
-pytestmark = pytest.mark.skipif(REF is None, reason="no reference checkout here")
-
-_PRELUDE = """
-import os, sys
-ROOT, REF = %r, %r
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv
-refenv.activate(REF)
-os.chdir(refenv.make_workdir(REF, %r))
-"""
-
-
-def _run(body, env_value, tmp_path):
-    code = (_PRELUDE % (ROOT, REF, str(tmp_path / "work"))) + textwrap.dedent(body)
-    env = dict(os.environ)
-    env.pop("GPSGS_ACCELERATE", None)
-    if env_value is not None:
-        env["GPSGS_ACCELERATE"] = env_value
-    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
-
+pytestmark = pytest.mark.skipif(H.REF is None, reason="no reference checkout here")
 
 _CHECK_ALL = """
         import gps_gaussian_amd.accelerate as A, gps_gaussian_amd.corr as MC
@@ -54,7 +24,7 @@ _CHECK_ALL = """
 
 
 def test_train_stage2_binds_the_fused_ops_when_asked(tmp_path):
-    out = _run("""
+    out = H.run("""
         import train_stage2 as T                           # the reference's script, unmodified, imported (not run)
         import gps_gaussian_amd.accelerate as A
         assert T.pts2render is A._pts2render and T.l1_loss is A._l1_loss and T.ssim is A._ssim, A.installed()
@@ -68,7 +38,7 @@ def test_train_stage2_binds_the_fused_ops_when_asked(tmp_path):
 
 
 def test_view_interp_binds_the_fused_ops_when_asked(tmp_path):
-    out = _run("""
+    out = H.run("""
         import test_view_interp as T
         import gps_gaussian_amd.accelerate as A
         assert T.pts2render is A._pts2render, A.installed()
@@ -79,7 +49,7 @@ def test_view_interp_binds_the_fused_ops_when_asked(tmp_path):
 
 
 def test_default_is_off_and_a_subset_touches_only_what_it_names(tmp_path):
-    out = _run("""
+    out = H.run("""
         import train_stage2 as T
         assert "gps_gaussian_amd.accelerate" not in sys.modules                      # not even imported
         import lib.GaussianRender, lib.loss, core.corr, core.raft_stereo_human as RSH, lib.network
@@ -90,7 +60,7 @@ def test_default_is_off_and_a_subset_touches_only_what_it_names(tmp_path):
         print("UNTOUCHED")
     """, None, tmp_path)
     assert "UNTOUCHED" in out
-    out = _run("""
+    out = H.run("""
         import train_stage2 as T
         import gps_gaussian_amd.accelerate as A
         import core.corr, core.raft_stereo_human as RSH, lib.network
@@ -106,7 +76,7 @@ def test_default_is_off_and_a_subset_touches_only_what_it_names(tmp_path):
 def test_renderer_first_import_order_is_caught_by_the_sweep_and_restore_undoes_it(tmp_path):
     # a caller that imports lib.GaussianRender FIRST: the drop-in (and with it the hook) arrives while lib.GaussianRender is still executing, and the
     # caller binds the reference's pts2render; the next reference module that loads triggers the sweep over already-bound names
-    out = _run("""
+    out = H.run("""
         from lib.GaussianRender import pts2render
         assert pts2render.__module__ == "lib.GaussianRender"
         import gps_gaussian_amd.accelerate as A
@@ -134,7 +104,7 @@ def test_a_typo_in_the_feature_list_raises(tmp_path):
 
 def test_calls_handed_on_to_the_reference_are_counted(tmp_path):
     """A configuration the fused kernels do not implement goes to the reference's own function -- and leaves a trace in `calls`."""
-    out = _run("""
+    out = H.run("""
         import train_stage2  # noqa: F401
         import torch
         import gps_gaussian_amd.accelerate as A

@@ -114,12 +114,12 @@ def test_the_op_itself_refuses_cpu_tensors_and_a_residual_without_relu():
 
 
 def test_resblock_is_accepted_by_name_only():
-    assert A.OPT_IN == ("splat", "groupnorm") and A.OPT_IN_FUSED == ("resblock",)
+    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
     assert A.requested("resblock") == ("resblock",)
-    assert A.requested("all") == A.FEATURES and "resblock" not in A.FEATURES + A.OPT_IN
+    assert A.requested("all") == A.FEATURES and "resblock" not in A.FEATURES
     assert A.requested("all,resblock") == A.FEATURES + ("resblock",)
     assert A.requested("resblock,groupnorm,loss") == ("loss", "groupnorm", "resblock")
-    assert A.requested("all,groupnorm,splat") == A.FEATURES + A.OPT_IN
+    assert A.requested("all,groupnorm,splat") == A.FEATURES + ("splat", "groupnorm")
     for k in ("resblock", "resblock_passthrough"):
         assert k in A.calls
     with pytest.raises(ValueError):

@@ -1,31 +1,9 @@
 """CPU: GPSGS_ACCELERATE=groupnorm makes the reference's UNMODIFIED core/extractor.py build FusedGroupNorm layers (accelerate.py wraps the two
 constructors, the reference's forward bodies run as they are); "all" alone converts nothing.
 
-Each case runs in a fresh interpreter with the integration path, the harness of test_splat_hook.py; they skip where there is no reference
+Each case runs in a fresh interpreter with the integration path, the harness of hook_run.py; they skip where there is no reference
 checkout."""
-import os
-import subprocess
-import sys
-import textwrap
-
-import pytest
-
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv  # noqa: E402
-
-REF = refenv.reference_dir()
-needs_ref = pytest.mark.skipif(REF is None, reason="no reference checkout here")
-
-_PRELUDE = """
-import os, sys
-ROOT, REF = %r, %r
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv
-refenv.activate(REF)
-os.chdir(refenv.make_workdir(REF, %r))
-"""
+import hook_run as H
 
 # builds the two classes, prints the class names of their GroupNorm layers, the state_dict keys and a digest of a seeded CPU forward
 _BODY = """
@@ -56,39 +34,24 @@ _BODY = """
 """
 
 
-def _run(body, env_value, tmp_path):
-    code = (_PRELUDE % (ROOT, REF, str(tmp_path / "work"))) + textwrap.dedent(body)
-    env = dict(os.environ)
-    env.pop("GPSGS_ACCELERATE", None)
-    if env_value is not None:
-        env["GPSGS_ACCELERATE"] = env_value
-    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
-
-
-def _lines(out, tag):
-    return [l for l in out.splitlines() if tag in l.split(" ")[:2]]
-
-
-@needs_ref
+@H.needs_ref
 def test_groupnorm_converts_the_extractor_and_all_alone_does_not(tmp_path):
-    plain = _run(_BODY, None, tmp_path)
-    fused = _run(_BODY, "groupnorm", tmp_path)
-    only_all = _run(_BODY, "all", tmp_path)
-    both = _run(_BODY, "all,groupnorm", tmp_path)
+    plain = H.run(_BODY, None, tmp_path)
+    fused = H.run(_BODY, "groupnorm", tmp_path)
+    only_all = H.run(_BODY, "all", tmp_path)
+    both = H.run(_BODY, "all,groupnorm", tmp_path)
 
     for out in (plain, only_all):
-        norms = _lines(out, "NORMS")
+        norms = H.lines(out, "NORMS")
         assert len(norms) == 2 and all("['normalization.GroupNorm']" in l for l in norms), norms
         assert "INSTALLED []" in out and "CALLS 0 0" in out
     for out in (fused, both):
-        norms = _lines(out, "NORMS")
+        norms = H.lines(out, "NORMS")
         assert len(norms) == 2 and all("['groupnorm.FusedGroupNorm']" in l for l in norms), norms          # every one, norm3 included
         assert "INSTALLED ['core.extractor.ResidualBlock.__init__', 'core.extractor.UnetExtractor.__init__']" in out
-        calls = _lines(out, "CALLS")[0].split()
+        calls = H.lines(out, "CALLS")[0].split()
         assert calls[1] == "0" and int(calls[2]) > 0        # CPU tensors: every forward was handed to nn.GroupNorm.forward, and counted
     # the same number of GroupNorm layers, the same state_dict keys, the same bits
-    assert _lines(plain, "NORMS")[0].split()[2] == _lines(fused, "NORMS")[0].split()[2] != "0"
-    assert _lines(plain, "KEYS") == _lines(fused, "KEYS") == _lines(only_all, "KEYS") == _lines(both, "KEYS") and len(_lines(plain, "KEYS")) == 2
-    assert _lines(plain, "DIGEST") == _lines(fused, "DIGEST") == _lines(only_all, "DIGEST") == _lines(both, "DIGEST") and len(_lines(plain, "DIGEST")) == 1
+    assert H.lines(plain, "NORMS")[0].split()[2] == H.lines(fused, "NORMS")[0].split()[2] != "0"
+    assert H.lines(plain, "KEYS") == H.lines(fused, "KEYS") == H.lines(only_all, "KEYS") == H.lines(both, "KEYS") and len(H.lines(plain, "KEYS")) == 2
+    assert H.lines(plain, "DIGEST") == H.lines(fused, "DIGEST") == H.lines(only_all, "DIGEST") == H.lines(both, "DIGEST") and len(H.lines(plain, "DIGEST")) == 1

@@ -93,10 +93,10 @@ def test_the_op_itself_refuses_cpu_tensors():
 
 
 def test_groupnorm_is_accepted_by_name_only():
-    assert A.OPT_IN == ("splat", "groupnorm")
+    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
     assert A.requested("groupnorm") == ("groupnorm",)
     assert A.requested("all") == A.FEATURES and "groupnorm" not in A.FEATURES
-    assert A.requested("all,groupnorm,splat") == A.FEATURES + A.OPT_IN
+    assert A.requested("all,groupnorm,splat") == A.FEATURES + ("splat", "groupnorm")
     assert A.requested("groupnorm,loss") == ("loss", "groupnorm")
     assert "groupnorm" in A.calls and "groupnorm_passthrough" in A.calls
     with pytest.raises(ValueError):

@@ -1,9 +1,9 @@
 """CPU: GPSGS_ACCELERATE=gshead makes the reference's UNMODIFIED lib/gs_parm_network.py build the tails of its three heads as FusedHeadConv, and
 nothing else; every other value of the variable leaves the heads exactly as the reference builds them.
 
-Each case runs in a fresh interpreter with the integration path, the harness of test_groupnorm_hook.py; they skip where there is no reference
+Each case runs in a fresh interpreter with the integration path, the harness of hook_run.py; they skip where there is no reference
 checkout."""
-import test_groupnorm_hook as H
+import hook_run as H
 
 # builds GSRegresser from a small cfg (dims [16, 24, 32], head dim 16), prints the classes of its heads, of the norms and of the stem, the state_dict
 # keys, a digest of the parameters and of a seeded CPU forward, the counters and what was rebound
@@ -53,17 +53,17 @@ _FUSED = {"rot_head": "['conv.Conv2d', 'linear.Identity', 'gshead.FusedHeadConv'
 
 
 def _heads(out):
-    return {l.split()[0]: l.split("HEAD ", 1)[1] for l in H._lines(out, "HEAD")}
+    return {l.split()[0]: l.split("HEAD ", 1)[1] for l in H.lines(out, "HEAD")}
 
 
 @H.needs_ref
 def test_gshead_converts_the_heads_and_nothing_else_does(tmp_path):
-    runs = {v: H._run(_BODY, v, tmp_path) for v in (None, "all", "groupnorm", "resblock", "stemconv", "gshead", "resblock,stemconv,gshead")}
+    runs = {v: H.run(_BODY, v, tmp_path) for v in (None, "all", "groupnorm", "resblock", "stemconv", "gshead", "resblock,stemconv,gshead")}
 
     for v in (None, "all", "groupnorm", "resblock", "stemconv"):                      # nothing of the heads changes
         out = runs[v]
         assert _heads(out) == _PLAIN, v
-        assert H._lines(out, "FUSED")[0].split()[2] == "0" and "CALLS 0 0" in out and _INIT not in out, v
+        assert H.lines(out, "FUSED")[0].split()[2] == "0" and "CALLS 0 0" in out and _INIT not in out, v
     assert "INSTALLED []" in runs[None] and "INSTALLED []" in runs["all"]
 
     out = runs["gshead"]                                                               # gshead alone: the three tails, and only them
@@ -71,20 +71,20 @@ def test_gshead_converts_the_heads_and_nothing_else_does(tmp_path):
     assert "INSTALLED %r" % [(_INIT, "gshead")] in out
     assert "NORMS ['normalization.GroupNorm']" in out                                  # every norm is still nn.GroupNorm
     assert "STEM ['conv.Conv2d', 'normalization.GroupNorm', 'activation.ReLU']" in out    # in_ds[0] is a plain Conv2d
-    assert H._lines(out, "FUSED")[0].split()[2] == "3"
+    assert H.lines(out, "FUSED")[0].split()[2] == "3"
     assert "CALLS 0 3" in out                                                          # a CPU forward: three pass-throughs, counted
 
     out = runs["resblock,stemconv,gshead"]                                             # composes with the encoder's opt-ins
     assert _heads(out) == _FUSED and "CALLS 0 3" in out
     assert "STEM ['stemconv.FusedStemConv2d', 'groupnorm.FusedGroupNormReLU', 'linear.Identity']" in out
-    assert "normalization.GroupNorm" not in H._lines(out, "NORMS")[0]
+    assert "normalization.GroupNorm" not in H.lines(out, "NORMS")[0]
     assert "(%r, 'gshead')" % _INIT in out and "core.extractor.UnetExtractor.__init__" in out and "core.extractor.ResidualBlock.forward" in out
 
     # the same layers under the same names, the same parameters, the same number of convolutions everywhere; the same output bits wherever every
     # forward was torch's own (the pass-through applies the ReLU and the activation itself)
     for tag in ("KEYS", "PARAMS"):
-        lines = [H._lines(o, tag) for o in runs.values()]
+        lines = [H.lines(o, tag) for o in runs.values()]
         assert all(l == lines[0] for l in lines) and len(lines[0]) == 1, tag
-    assert len({H._lines(o, "FUSED")[0].split()[3] for o in runs.values()}) == 1
-    assert H._lines(runs["gshead"], "DIGEST") == H._lines(runs[None], "DIGEST") == H._lines(runs["all"], "DIGEST") == H._lines(runs["stemconv"], "DIGEST")
-    assert len(H._lines(runs[None], "DIGEST")) == 1
+    assert len({H.lines(o, "FUSED")[0].split()[3] for o in runs.values()}) == 1
+    assert H.lines(runs["gshead"], "DIGEST") == H.lines(runs[None], "DIGEST") == H.lines(runs["all"], "DIGEST") == H.lines(runs["stemconv"], "DIGEST")
+    assert len(H.lines(runs[None], "DIGEST")) == 1

@@ -107,7 +107,7 @@ def test_head_has_no_cpu_path():
 
 
 def test_the_opt_in_name():
-    assert A.OPT_IN_HEAD == ("gshead",)
+    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
     assert "gshead" in A.calls and "gshead_passthrough" in A.calls
     assert A.requested("gshead") == ("gshead",)
     assert "gshead" not in A.requested("all") and A.requested("all") == A.FEATURES

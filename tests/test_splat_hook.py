@@ -1,48 +1,17 @@
 """CPU: GPSGS_ACCELERATE=splat serves this package's stand-in for the reference's lib/TaichiRender.py (which imports taichi and cannot load on
 this card), so the reference's UNMODIFIED train_stage1.py imports; "all" keeps meaning the five fused features; the splat refuses CPU tensors.
 
-Each hook case runs in a fresh interpreter with the integration path, the same harness as test_accelerate_hook.py; those skip where there is no
+Each hook case runs in a fresh interpreter with the integration path, the harness of hook_run.py; those skip where there is no
 reference checkout."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import pytest
 import torch
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv  # noqa: E402
-
-REF = refenv.reference_dir()
-needs_ref = pytest.mark.skipif(REF is None, reason="no reference checkout here")
-
-_PRELUDE = """
-import os, sys
-ROOT, REF = %r, %r
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import refenv
-refenv.activate(REF)
-os.chdir(refenv.make_workdir(REF, %r))
-"""
+import hook_run as H
 
 
-def _run(body, env_value, tmp_path):
-    code = (_PRELUDE % (ROOT, REF, str(tmp_path / "work"))) + textwrap.dedent(body)
-    env = dict(os.environ)
-    env.pop("GPSGS_ACCELERATE", None)
-    if env_value is not None:
-        env["GPSGS_ACCELERATE"] = env_value
-    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
-
-
-@needs_ref
+@H.needs_ref
 def test_train_stage1_imports_with_the_splat_substitute(tmp_path):
-    out = _run("""
+    out = H.run("""
         import train_stage1 as T                           # the reference's script, unmodified, imported (not run)
         import gps_gaussian_amd.splat as SP, gps_gaussian_amd.accelerate as A
         import lib.TaichiRender
@@ -55,9 +24,9 @@ def test_train_stage1_imports_with_the_splat_substitute(tmp_path):
     assert "SERVED" in out
 
 
-@needs_ref
+@H.needs_ref
 def test_all_plus_splat_binds_both(tmp_path):
-    out = _run("""
+    out = H.run("""
         import train_stage1 as T
         import gps_gaussian_amd.splat as SP, gps_gaussian_amd.accelerate as A
         import core.corr, gps_gaussian_amd.corr as MC
@@ -70,9 +39,9 @@ def test_all_plus_splat_binds_both(tmp_path):
     assert "BOTH" in out
 
 
-@needs_ref
+@H.needs_ref
 def test_without_the_variable_the_reference_module_is_not_served(tmp_path):
-    out = _run("""
+    out = H.run("""
         import importlib.util
         import gps_gaussian_amd.accelerate as A
         import lib.network  # noqa: F401  (imports corr_sampler: the drop-in, where the hook would install itself)
@@ -89,9 +58,9 @@ def test_without_the_variable_the_reference_module_is_not_served(tmp_path):
     assert "REFERENCE" in out
 
 
-@needs_ref
+@H.needs_ref
 def test_all_alone_does_not_serve_the_substitute(tmp_path):
-    out = _run("""
+    out = H.run("""
         import lib.network  # noqa: F401
         import importlib.util
         spec = importlib.util.find_spec("lib.TaichiRender")

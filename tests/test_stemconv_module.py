@@ -68,7 +68,7 @@ def test_the_op_itself_raises_on_a_cpu_tensor():
 
 
 def test_the_stemconv_name():
-    assert A.OPT_IN_CONV == ("stemconv",)
+    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
     assert A.requested("stemconv") == ("stemconv",)
     assert A.requested("all,stemconv") == A.FEATURES + ("stemconv",)
     assert "stemconv" not in A.requested("all") and A.requested("all") == A.FEATURES
