@@ -176,8 +176,19 @@ _SC = {
     "sc_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "sc_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
+# 3x3 convolution on the matrix cores (the header's last section; tests/test_capi_conv3x3.py)
+_C3 = {
+    "c3_supported": (i32, [i32, i32]),
+    "c3_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "c3_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "c3_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "c3_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+}
 PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC}
 SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC)
+# (a table of its own: tests/test_capi.py pins PROTOTYPES to the four tuples above; lib() sets both)
+C3_PROTOTYPES = dict(_C3)
+C3_SYMBOLS = tuple(_C3)
 
 _lib = None
 
@@ -192,7 +203,7 @@ def lib():
             "gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gps-gaussian_amd/csrc`). There is no CPU fallback for this path." % LIB_PATH)
     l = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **C3_PROTOTYPES}.items():
         fn = getattr(l, name)
         fn.restype, fn.argtypes = restype, argtypes
     if l.gpsgs_abi_version() != 4:

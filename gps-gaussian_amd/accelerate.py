@@ -28,6 +28,8 @@ here runs unless the variable is set; every replacement is the GPU path of this 
                     (`in_ds[0]`, core/extractor.py:66-70) becomes a FusedStemConv2d
   gshead     no     wraps lib/gs_parm_network.py:8 `GSRegresser.__init__`: the ReLU -> Conv2d(32, 4|3|1, 1) gshead.py
                     -> nothing | Softplus | Sigmoid tail of its three heads (:34-50) becomes a FusedHeadConv
+  conv3x3    no     wraps `GSRegresser.__init__` too: `out_conv` + `out_relu` (:31-32) and the Conv2d(32, 32, 3)   conv3x3.py
+                    at the top of each head become FusedConv3x3 (BY_NAME: its two counters appear in `calls` on first request)
 
 The names outside "all" are accepted by name only (`all,splat`, `resblock,stemconv`, ...) and imply nothing but what their line says.  A wrapped
 constructor runs the reference's own `__init__` and then the conversions that were asked for (`_ENCODER_STEPS`, `_HEAD_STEPS`): same parameters, same state_dict; the
@@ -47,6 +49,9 @@ import threading
 
 FEATURES = ("pack", "loss", "corr", "upsample", "unproject")          # what "all" means
 OPT_IN = ("splat", "groupnorm", "resblock", "stemconv", "gshead")     # accepted by name only, never implied by "all"
+# accepted by name only as well, after OPT_IN; their counters (<name>, <name>_passthrough) are created in `calls` when the name is first requested
+# or first counted (counters()), so a process that never asks for one keeps the keys above, in their order
+BY_NAME = ("conv3x3",)
 # features that count, under <name>_passthrough, the calls that went THROUGH a replacement but were handed on to the reference's or torch's own
 # code (a configuration the fused kernel does not implement: ssim with another window, CPU tensors, channels-last, norm_fn batch, ...), so that a
 # run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
@@ -74,11 +79,23 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN
+    known = FEATURES + OPT_IN + BY_NAME
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
+    for f in BY_NAME:
+        if f in names:
+            counters(f)
     return tuple(f for f in known if f in names)
+
+
+def counters(name):
+    """`calls`, with the two counters of the BY_NAME feature `name` in it (created at zero, behind every existing key, the first time)."""
+    if name not in calls:
+        with _lock:
+            calls.setdefault(name, 0)
+            calls.setdefault(name + "_passthrough", 0)
+    return calls
 
 
 def installed():
@@ -149,7 +166,8 @@ _ENCODER_STEPS = ((("groupnorm", "resblock"), "groupnorm", "convert"),          
                   (("resblock",), "groupnorm", "fuse_sequential_relu"),            # the stem's ReLU folded into its norm
                   (("stemconv",), "stemconv", "convert"))                          # the stem convolution
 # the heads' tails and nothing else: the encoder and the blocks GSRegresser builds went through their own wrappers inside its constructor
-_HEAD_STEPS = ((("gshead",), "gshead", "convert"),)
+_HEAD_STEPS = ((("gshead",), "gshead", "convert"),
+               (("conv3x3",), "conv3x3", "convert_regresser"))                     # out_conv + out_relu, and the 3x3 layer that opens each head
 
 
 def _converting_init(key, steps):
@@ -206,7 +224,7 @@ _ROWS = (
     ("lib.utils", "depth2pc", _depth2pc, ("unproject",)),
     ("core.extractor", "ResidualBlock.__init__", _resblock_init, ("groupnorm", "resblock")),
     ("core.extractor", "UnetExtractor.__init__", _unet_init, ("groupnorm", "resblock", "stemconv")),
-    ("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init, ("gshead",)),
+    ("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init, ("gshead", "conv3x3")),
     ("core.extractor", "ResidualBlock.forward", _resblock_forward, ("resblock",)),
 )
 
@@ -240,7 +258,7 @@ def apply(features=None):
         return 0
     made = 0
     with _lock:
-        _asked.update(f for f in feats if f in OPT_IN)
+        _asked.update(f for f in feats if f in OPT_IN + BY_NAME)
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -289,6 +307,9 @@ def restore():
         _originals.clear()
         _installed.clear()
         _asked.clear()
+        for f in BY_NAME:                      # back to the keys a process starts with
+            calls.pop(f, None)
+            calls.pop(f + "_passthrough", None)
         for k in calls:
             calls[k] = 0
 

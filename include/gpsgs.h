@@ -45,6 +45,9 @@
  *       the tail of the three Gaussian-parameter heads, nn.ReLU -> nn.Conv2d(32, 4 | 3 | 1, 1) -> nothing | nn.Softplus(beta=100) | nn.Sigmoid of
  *       lib/gs_parm_network.py:34-50 on the full-resolution hidden tensor, and its autograd backward: ATen's clamp pass, the library's 1x1
  *       implicit GEMM between NCHW <-> NHWC transposes, and the elementwise activation.
+ *   c3_forward / c3_backward (+ c3_supported, c3_tile, c3_scratch_bytes)
+ *       the regresser's full-resolution 3x3 convolutions, nn.Conv2d(52, 32, 3, padding=1) + nn.ReLU (`out_conv`, `out_relu`) and the
+ *       nn.Conv2d(32, 32, 3, padding=1) at the top of each head (lib/gs_parm_network.py:27-50), and their autograd backward.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -74,7 +77,8 @@ extern "C" {
                                still 4 after the GroupNorm epilogues: gne_forward, gne_backward (additive)
                                still 4 after the stem convolution: sc_supported, sc_tile, sc_scratch_bytes, sc_forward, sc_backward (additive)
                                still 4 after the Gaussian heads: gsr_head_supported, gsr_head_tile, gsr_head_scratch_bytes, gsr_head_forward,
-                                  gsr_head_backward (additive) */
+                                  gsr_head_backward (additive)
+                               still 4 after the 3x3 convolutions: c3_supported, c3_tile, c3_scratch_bytes, c3_forward, c3_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -694,6 +698,30 @@ int sc_forward(const float *x, const float *w, const float *bias, int N, int C_i
                int y_dtype, void *stream);
 int sc_backward(const float *x, const float *w, const void *dy, int dy_dtype, int N, int C_in, int C_out, int H, int W, int K, int stride, int pad,
                 float *dx, float *dw, float *dbias, void *scratch, void *stream);
+
+/* ---- 3x3 convolution to 32 channels on the fp32 matrix cores, forward and backward ---------------------------------------------------
+ * y[N,32,H,W] = conv2d(x[N,C_in,H,W], w[32,C_in,3,3], bias[32], stride 1, padding 1), zero padding, contiguous NCHW fp32, followed by ReLU where
+ * relu = 1  (torch.nn.functional.conv2d + relu).  Implicit GEMM on v_mfma_f32_32x32x2_f32: exact fp32, every sum an fmaf chain in a fixed order
+ * (the products first, the bias added last), no layout transposes, no atomics, the same bits on every run.
+ * c3_supported: 1 for C_out == 32 and C_in a multiple of 4 with 4 <= C_in <= 64; otherwise 0.
+ * c3_tile: the output tile (rows, columns) one workgroup of the forward and of the input gradient computes.
+ * x, y, dy, dx and scratch must be 16-byte aligned; H and W may be anything >= 1, rows may start off 16-byte boundaries.
+ * c3_backward takes dy, the gradient of y; relu = 1: g = dy where y > 0, else 0, with y the forward's output (required then; ignored and may be
+ * NULL for relu = 0).  It WRITES dx = conv(g, w flipped and transposed) (NULL = not wanted: that kernel is not launched) and dw / dbias (both or
+ * neither; NULL = not wanted).  dw and dbias are sums over pixels: at most 512 workgroups each walk a fixed, index-ordered set of 4 x 32 pixel
+ * tiles and write one partial; the partials are added in index order, in groups of 32 and then the groups.
+ * scratch (needed for dw / dbias only): DEVICE, at least c3_scratch_bytes(N, C_in, H, W) =
+ *     4 * 32 * (9 * C_in + 1) * (parts + ceil(parts / 32))   bytes,  parts = min(512, N * ceil(H / 4) * ceil(W / 32))
+ * and 0 for arguments c3_forward would refuse.
+ * GPSGS_E_INVALID, before any HIP call: channel counts c3_supported refuses, a non-positive N, H or W, relu outside {0, 1}, 2^31 elements or more
+ * in x or in y, one of dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, y where relu = 1, and scratch where dw is
+ * wanted) or a misaligned one. */
+int c3_supported(int C_in, int C_out);
+int c3_tile(int *tile_h, int *tile_w);
+size_t c3_scratch_bytes(int N, int C_in, int H, int W);
+int c3_forward(const float *x, const float *w, const float *bias, int N, int C_in, int H, int W, int relu, float *y, void *stream);
+int c3_backward(const float *x, const float *w, const float *y, const float *dy, int N, int C_in, int H, int W, int relu, float *dx, float *dw,
+                float *dbias, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }
