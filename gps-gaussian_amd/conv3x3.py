@@ -18,8 +18,8 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _capi, accelerate
-from ._ops import aligned16, call, dense_fp32_call, fp32_on, ptr
+from . import _capi, _ops, accelerate
+from ._ops import aligned16, call, conv_inputs, dense_fp32_call, grad_buffers, param_grads, plain_conv, ptr, sequential_slots
 
 
 def supported(C_in, C_out):
@@ -30,18 +30,13 @@ def supported(C_in, C_out):
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
-        if not x.is_cuda:
-            raise RuntimeError("gps_gaussian_amd: conv3x3 input must live on a GPU (no CPU fallback)")
-        if x.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4 or bias is None:
-            raise RuntimeError("gps_gaussian_amd: conv3x3 takes an fp32 [N, C_in, H, W] input, a [32, C_in, 3, 3] weight and a bias")
+        xc, w, b = conv_inputs("conv3x3", "[N, C_in, H, W]", "[32, C_in, 3, 3]", x, weight, bias)
         N, Ci, H, W = x.shape
         Co = weight.shape[0]
         if tuple(weight.shape[1:]) != (Ci, 3, 3) or bias.numel() != Co or x.numel() == 0 or not supported(Ci, Co):
             raise RuntimeError("gps_gaussian_amd: conv3x3: unsupported configuration: input %s, weight %s" % (tuple(x.shape), tuple(weight.shape)))
         dev = x.device
         relu = bool(relu)
-        xc = aligned16(x.detach())
-        w, b = fp32_on(dev, weight, bias)
         y = torch.empty((N, Co, H, W), dtype=torch.float32, device=dev)
         call("c3_forward", dev, ptr(xc), ptr(w), ptr(b), N, Ci, H, W, int(relu), ptr(y))
         if any(ctx.needs_input_grad):
@@ -56,19 +51,11 @@ class _Conv3x3(torch.autograd.Function):
         xc, w = ctx.saved_tensors[:2]
         y = ctx.saved_tensors[2] if ctx.relu else None
         N, Ci, H, W = xc.shape
-        Co = w.shape[0]
-        dev = xc.device
-        wdt, bdt = ctx.like
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        needs = ctx.needs_input_grad
         dyc = aligned16(dy.to(torch.float32))
-        dx = torch.empty_like(xc) if need_x else None      # the input-gradient kernel runs only when x wants one
-        dw = db = scratch = None
-        if need_w or need_b:
-            dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=dev)
-            db = torch.empty((Co,), dtype=torch.float32, device=dev)
-            scratch = torch.empty((_capi.lib().c3_scratch_bytes(N, Ci, H, W) // 4 + 4,), dtype=torch.float32, device=dev)
-        call("c3_backward", dev, ptr(xc), ptr(w), ptr(y), ptr(dyc), N, Ci, H, W, int(ctx.relu), ptr(dx), ptr(dw), ptr(db), ptr(scratch))
-        return dx, dw.to(wdt) if need_w else None, db.to(bdt) if need_b else None, None
+        dx, dw, db, scratch = grad_buffers(xc, needs, w.shape, _capi.lib().c3_scratch_bytes, N, Ci, H, W)   # dx None: that kernel is not run
+        call("c3_backward", xc.device, ptr(xc), ptr(w), ptr(y), ptr(dyc), N, Ci, H, W, int(ctx.relu), ptr(dx), ptr(dw), ptr(db), ptr(scratch))
+        return (dx,) + param_grads(needs, dw, db, *ctx.like) + (None,)
 
 
 def conv3x3(x, weight, bias, relu=False):
@@ -80,24 +67,13 @@ def conv3x3(x, weight, bias, relu=False):
 
 
 def _plain(conv):
-    """A convolution whose static configuration is the op's: 3x3, stride 1, padding 1, dilation 1, groups 1, zero padding mode, a bias, supported
-    channel counts."""
-    return conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 \
-        and conv.bias is not None and conv.padding_mode == "zeros" and supported(conv.in_channels, conv.out_channels)
-
-
-_TILE = None
+    """A convolution whose static configuration is the op's: 3x3, padding 1, otherwise plain_conv's, supported channel counts."""
+    return plain_conv(conv, 3, 1, supported)
 
 
 def tile():
     """(rows, columns) of the output tile of a workgroup of the forward (c3_tile)."""
-    global _TILE
-    if _TILE is None:
-        import ctypes
-        th, tw = ctypes.c_int(0), ctypes.c_int(0)
-        _capi.check(_capi.lib().c3_tile(ctypes.byref(th), ctypes.byref(tw)), "c3_tile")
-        _TILE = (th.value, tw.value)
-    return _TILE
+    return _ops.tile("c3_tile")
 
 
 def _fusable(m, x):
@@ -147,12 +123,10 @@ def convert(module):
     compose in either order.  Convolutions held as plain attributes, subclasses of nn.Conv2d and already converted layers are left alone.  Returns
     the number converted."""
     n = 0
-    for seq in list(module.modules()):
-        if isinstance(seq, nn.Sequential):
-            for m in seq:
-                if type(m) is nn.Conv2d and _plain(m):
-                    _swap(m, False)
-                    n += 1
+    for seq, i in sequential_slots(module, 1):
+        if type(seq[i]) is nn.Conv2d and _plain(seq[i]):
+            _swap(seq[i], False)
+            n += 1
     return n
 
 

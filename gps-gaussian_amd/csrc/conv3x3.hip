@@ -15,12 +15,12 @@
 //   k_c3_bwd_weight  dw[co][ci, ky, kx] = sum over pixels g[co] x[ci] shifted: M = 32 co, N = (tap, ci), K = pixels.  A workgroup walks the 4 x 32
 //                    pixel tiles b, b + G, b + 2G, ... in index order with all 32 x 9 C_in sums in accumulators (18 blocks of 32 x 32 over 4 waves),
 //                    g [32][128] and the patch of 32 input channels in LDS; it writes ONE partial (and its bias sums) to scratch.
-//   k_c3_bwd_reduce  adds the workgroups' partials in index order, in groups of C3_GROUP and then the groups.
+//   k_sum_partials   (op_reduce.h) adds the workgroups' partials in index order, in groups of C3_GROUP and then the groups.
 // No atomics; every sum has a fixed order: the same bits on every run.  Element offsets are 64-bit.  Guarded global loads are an unconditional load
 // from a clamped (always valid) address followed by a select (stem_conv.hip).
 // Accumulator layout of the MFMA (corr_pyramid.hip tile_gemm): register v of lane l is row (v / 4) * 8 + (l / 32) * 4 + v % 4, column l % 32; the
 // A operand of lane l is A[l % 32][l / 32], the B operand B[l / 32][l % 32].
-#include "op_common.h"
+#include "op_reduce.h"
 
 namespace {
 
@@ -305,23 +305,6 @@ __global__ __launch_bounds__(C3_THREADS, 1) void k_c3_bwd_weight(const float *__
     if ((tid & 7) == 0) out[(size_t)C3_CO * 9 * C + (tid >> 3)] = dbsum;
 }
 
-// out[g][j] = sum over parts t in [g * group, min(parts, (g + 1) * group)) of in[t][j], in index order.  With dw != NULL (the last stage, one group)
-// the M sums go to dw (j < MW) and db instead.
-__global__ __launch_bounds__(C3_THREADS) void k_c3_bwd_reduce(const float *__restrict__ in, int parts, int group, int M, int MW, float *__restrict__ out,
-                                                              float *__restrict__ dw, float *__restrict__ db, int jblocks) {
-    const int j = (int)(blockIdx.x % (unsigned)jblocks) * C3_THREADS + threadIdx.x, g = (int)(blockIdx.x / (unsigned)jblocks);
-    if (j >= M) return;
-    const int t0 = g * group, t1 = min(parts, t0 + group);
-    float s = 0.f;
-#pragma unroll 8
-    for (int t = t0; t < t1; t++) s += in[(size_t)t * M + j];  // (unrolled: the loads in flight together, the adds in index order)
-    if (dw != nullptr) {
-        if (j < MW) dw[j] = s; else db[j - MW] = s;
-    } else {
-        out[(size_t)g * M + j] = s;
-    }
-}
-
 bool supported(int C_in, int C_out) { return C_out == C3_CO && C_in >= 4 && C_in <= 64 && C_in % 4 == 0; }
 
 // fills d; false = refused (unsupported channel counts, a non-positive size, 2^31 elements or more in x or y)
@@ -356,7 +339,7 @@ extern "C" size_t c3_scratch_bytes(int N, int C_in, int H, int W) {
     C3Dims d;
     if (!make_dims(N, C_in, H, W, d)) return 0;
     const size_t parts = weight_parts(d), M = (size_t)C3_CO * (9 * (size_t)C_in + 1);
-    return 4 * M * (parts + cdiv(parts, C3_GROUP));
+    return partials_scratch_bytes(parts, C3_GROUP, M);
 }
 
 extern "C" int c3_forward(const float *x, const float *w, const float *bias, int N, int C_in, int H, int W, int relu, float *y, void *stream) {
@@ -394,25 +377,14 @@ extern "C" int c3_backward(const float *x, const float *w, const float *y, const
             hipLaunchKernelGGL(k_c3_bwd_input<false>, grid, block, 0, s, dy, y, w, dx, d);
     }
     if (dw) {
-        const int tiles = (int)weight_tiles(d), parts0 = (int)weight_parts(d), wtx = (int)cdiv(d.W, C3_WTW), wty = (int)cdiv(d.H, C3_WTH);
+        const int tiles = (int)weight_tiles(d), parts = (int)weight_parts(d), wtx = (int)cdiv(d.W, C3_WTW), wty = (int)cdiv(d.H, C3_WTH);
         const int MW = C3_CO * 9 * C_in, M = MW + C3_CO;
         float *part = (float *)scratch;
         if (relu)
-            hipLaunchKernelGGL(k_c3_bwd_weight<true>, dim3(parts0), dim3(C3_THREADS), 0, s, x, dy, y, part, d, wtx, wty, tiles);
+            hipLaunchKernelGGL(k_c3_bwd_weight<true>, dim3(parts), dim3(C3_THREADS), 0, s, x, dy, y, part, d, wtx, wty, tiles);
         else
-            hipLaunchKernelGGL(k_c3_bwd_weight<false>, dim3(parts0), dim3(C3_THREADS), 0, s, x, dy, y, part, d, wtx, wty, tiles);
-        const unsigned jb = (unsigned)cdiv(M, C3_THREADS);
-        const float *in = part;
-        int parts = parts0;
-        if (parts > C3_GROUP) {
-            const int groups = (int)cdiv(parts, C3_GROUP);
-            float *stage = part + (size_t)parts * M;
-            hipLaunchKernelGGL(k_c3_bwd_reduce, dim3(jb * (unsigned)groups), dim3(C3_THREADS), 0, s, in, parts, C3_GROUP, M, MW, stage, (float *)nullptr,
-                               (float *)nullptr, (int)jb);
-            in = stage;
-            parts = groups;
-        }
-        hipLaunchKernelGGL(k_c3_bwd_reduce, dim3(jb), dim3(C3_THREADS), 0, s, in, parts, parts, M, MW, (float *)nullptr, dw, dbias, (int)jb);
+            hipLaunchKernelGGL(k_c3_bwd_weight<false>, dim3(parts), dim3(C3_THREADS), 0, s, x, dy, y, part, d, wtx, wty, tiles);
+        sum_partials(part, parts, C3_GROUP, M, MW, dw, dbias, s);
     }
     return launched();
 }

@@ -17,13 +17,13 @@
 //              then dh[c] = (h[c] > 0) * sum_k w[k,c] dz[k] (when wanted) and the tile's K*C + K sums of dz[k] * max(h[c], 0) and of dz[k] (when
 //              wanted): a lane's pixels in index order, the wave by wave_sums(), the 4 waves in index order through LDS -> scratch[tile][K*C + K].
 //              One pass over h serves both: the weight sums need no accumulator that outlives a pass (DESIGN.md has the register figures).
-//   k_gh_reduce   adds the tiles' partials in index order, in groups of GH_GROUP and then the groups (the scheme of stem_conv.hip).
+//   k_sum_partials   (op_reduce.h) adds the tiles' partials in index order, in groups of GH_GROUP and then the groups.
 // No atomics; every sum has a fixed order: the same bits on every run.  Element offsets into h, y, dy, dh are 64-bit; a pixel index inside a plane
 // is an int (H*W is refused above INT_MAX - GH_TILE).  Guarded loads are unconditional loads from a clamped address followed by a select, as in
 // stem_conv.hip.
 #include <type_traits>
 
-#include "op_common.h"
+#include "op_reduce.h"
 
 namespace {
 
@@ -271,23 +271,6 @@ __global__ __launch_bounds__(GH_THREADS) void k_gh_bwd(const float *__restrict__
     }
 }
 
-// out[g][j] = sum over parts t in [g * group, min(parts, (g + 1) * group)) of in[t][j], in index order.  With dw != NULL (the last stage, one group)
-// the M sums go to dw (j < MW) and db instead.
-__global__ __launch_bounds__(GH_THREADS) void k_gh_reduce(const float *__restrict__ in, int parts, int group, int M, int MW, float *__restrict__ out,
-                                                          float *__restrict__ dw, float *__restrict__ db) {
-    const int j = threadIdx.x + (int)blockIdx.y * GH_THREADS, g = (int)blockIdx.x;
-    if (j >= M) return;
-    const int t0 = g * group, t1 = min(parts, t0 + group);
-    float s = 0.f;
-#pragma unroll 8
-    for (int t = t0; t < t1; t++) s += in[(size_t)t * M + j];  // (unrolled: the loads in flight together, the adds in index order)
-    if (dw != nullptr) {
-        if (j < MW) dw[j] = s; else db[j - MW] = s;
-    } else {
-        out[(size_t)g * M + j] = s;
-    }
-}
-
 bool supported(int C, int K, int act) { return (C == 16 || C == 32 || C == 64) && K >= 1 && K <= 4 && act >= GH_ACT_NONE && act <= GH_ACT_SIGMOID; }
 
 struct Dims {
@@ -330,18 +313,7 @@ void launch_bwd(bool vec, const float *h, const float *w, const float *bias, con
         hipLaunchKernelGGL((k_gh_bwd<C, K, false>), grid, block, 0, s, h, w, bias, dy, dh, partial, d.HW, d.tiles, a);
     if (!dw) return;
     constexpr int MW = K * C, M = MW + K;
-    const unsigned jb = (unsigned)cdiv(M, GH_THREADS);
-    const float *in = scratch;
-    int parts = (int)d.parts;
-    if (parts > GH_GROUP) {
-        const int groups = (int)cdiv((size_t)parts, GH_GROUP);
-        float *stage = scratch + (size_t)parts * M;
-        hipLaunchKernelGGL(k_gh_reduce, dim3((unsigned)groups, jb), block, 0, s, in, parts, GH_GROUP, M, MW, stage, (float *)nullptr, (float *)nullptr);
-        in = stage;
-        parts = groups;
-    }
-    // the second stage adds up to 2^31 / 64 groups in one thread per sum: a few thousand for the shapes this op is for (a full-resolution stereo batch)
-    hipLaunchKernelGGL(k_gh_reduce, dim3(1, jb), block, 0, s, in, parts, parts, M, MW, (float *)nullptr, dw, db);
+    sum_partials(scratch, (int)d.parts, GH_GROUP, M, MW, dw, db, s);
 }
 
 // f(<C>, <K>) for a supported (C, K): the run-time pair as compile-time constants
@@ -372,7 +344,7 @@ extern "C" size_t gsr_head_scratch_bytes(int N, int C_in, int C_out, int H, int 
     Dims d;
     if (!make_dims(N, C_in, C_out, H, W, GH_ACT_NONE, d)) return 0;
     const size_t M = (size_t)C_out * C_in + C_out;
-    return 4 * M * ((size_t)d.parts + cdiv((size_t)d.parts, GH_GROUP));
+    return partials_scratch_bytes((size_t)d.parts, GH_GROUP, M);
 }
 
 extern "C" int gsr_head_forward(const float *h, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int act, float beta,

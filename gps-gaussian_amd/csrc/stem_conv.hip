@@ -16,11 +16,11 @@
 //   k_sc_bwd_weight  one workgroup per tile: the input patch and, per block of 8 output channels, the dy tile in LDS.  Lane = (tap (ci, ky, kx),
 //                    pixel slice); it accumulates dy * x over its slice's pixels for the 8 channels, the slices are added in index order, and the
 //                    tile's C_out * CIN * K^2 sums + C_out bias sums go to scratch.
-//   k_sc_bwd_reduce  adds the tiles' partials in index order, in groups of SC_GROUP and then the groups.
+//   k_sum_partials   (op_reduce.h) adds the tiles' partials in index order, in groups of SC_GROUP and then the groups.
 // No atomics; every sum has a fixed order: the same bits on every run.  Element offsets into x, y, dy, dx are 64-bit.
 // Guarded global loads are written as an unconditional load from a clamped (always valid) address followed by a select: a branch around each load
 // makes the compiler wait for every one of them in turn (measured: the fp16 backward ran 3x slower that way).
-#include "op_common.h"
+#include "op_reduce.h"
 
 namespace {
 
@@ -297,23 +297,6 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_weight(const float *__res
     }
 }
 
-// out[g][j] = sum over parts t in [g * group, min(parts, (g + 1) * group)) of in[t][j], in index order.  With dw != NULL (the last stage, one group)
-// the M sums go to dw (j < MW) and db instead.
-__global__ __launch_bounds__(SC_THREADS) void k_sc_bwd_reduce(const float *__restrict__ in, int parts, int group, int M, int MW, float *__restrict__ out,
-                                                              float *__restrict__ dw, float *__restrict__ db, int jblocks) {
-    const int j = (int)(blockIdx.x % (unsigned)jblocks) * SC_THREADS + threadIdx.x, g = (int)(blockIdx.x / (unsigned)jblocks);
-    if (j >= M) return;
-    const int t0 = g * group, t1 = min(parts, t0 + group);
-    float s = 0.f;
-#pragma unroll 8
-    for (int t = t0; t < t1; t++) s += in[(size_t)t * M + j];  // (unrolled: the loads in flight together, the adds in index order)
-    if (dw != nullptr) {
-        if (j < MW) dw[j] = s; else db[j - MW] = s;
-    } else {
-        out[(size_t)g * M + j] = s;
-    }
-}
-
 bool supported(int C_in, int C_out, int K, int stride, int pad) {
     return (C_in == 1 || C_in == 3) && K == 5 && stride == 2 && pad == 2 && C_out >= 8 && C_out <= 64 && C_out % 8 == 0;
 }
@@ -360,18 +343,7 @@ void launch_bwd(const float *x, const float *w, const void *dy, int dy_dtype, co
             typedef decltype(t) Y;
             hipLaunchKernelGGL((k_sc_bwd_weight<CIN, K, S, Y::DT>), dim3(tiles), dim3(SC_THREADS), lds, s, x, (const typename Y::T *)dy, scratch, d);
         });
-        const unsigned jb = (unsigned)cdiv(M, SC_THREADS);
-        const float *in = scratch;
-        int parts = tiles;
-        if (tiles > SC_GROUP) {
-            const int groups = (int)cdiv(tiles, SC_GROUP);
-            float *stage = scratch + (size_t)tiles * M;
-            hipLaunchKernelGGL(k_sc_bwd_reduce, dim3(jb * (unsigned)groups), dim3(SC_THREADS), 0, s, in, parts, SC_GROUP, M, MW, stage, (float *)nullptr,
-                               (float *)nullptr, (int)jb);
-            in = stage;
-            parts = groups;
-        }
-        hipLaunchKernelGGL(k_sc_bwd_reduce, dim3(jb), dim3(SC_THREADS), 0, s, in, parts, parts, M, MW, (float *)nullptr, dw, db, (int)jb);
+        sum_partials(scratch, tiles, SC_GROUP, M, MW, dw, db, s);
     }
 }
 
@@ -390,7 +362,7 @@ extern "C" size_t sc_scratch_bytes(int N, int C_in, int C_out, int H, int W, int
     Dims d;
     if (!make_dims(N, C_in, C_out, H, W, K, stride, pad, d)) return 0;
     const size_t tiles = (size_t)N * d.tiles_y * d.tiles_x, M = (size_t)C_out * ((size_t)C_in * K * K + 1);
-    return 4 * M * (tiles + cdiv(tiles, SC_GROUP));
+    return partials_scratch_bytes(tiles, SC_GROUP, M);
 }
 
 extern "C" int sc_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int K, int stride, int pad,

@@ -16,7 +16,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-from ._ops import aligned16, call, dense_fp32_call, fp32_on, ptr, sequential_slots
+from ._ops import aligned16, call, conv_inputs, dense_fp32_call, grad_buffers, param_grads, plain_conv, ptr, sequential_slots
 
 ACT_CODE = {"none": 0, "softplus": 1, "sigmoid": 2}   # the `act` argument of include/gpsgs.h
 
@@ -29,25 +29,21 @@ def supported(C_in, C_out, act="none"):
 class _Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, beta, threshold):
-        if not x.is_cuda:
-            raise RuntimeError("gps_gaussian_amd: head input must live on a GPU (no CPU fallback)")
-        if x.dtype != torch.float32 or x.dim() != 4 or bias is None or weight.dim() not in (2, 4) or weight.numel() != weight.shape[0] * x.shape[1]:
-            raise RuntimeError("gps_gaussian_amd: head takes an fp32 [N, C, H, W] input, a [K, C] (or [K, C, 1, 1]) weight and a bias")
+        xc, w, b = conv_inputs("head", "[N, C, H, W]", "[K, C] (or [K, C, 1, 1])", x, weight, bias, wdims=(2, 4))
         N, C, H, W = x.shape
         K = weight.shape[0]
-        if act not in ACT_CODE or bias.numel() != K or x.numel() == 0 or not supported(C, K, act) or (act == "softplus" and not beta > 0):
+        if weight.numel() != K * C or act not in ACT_CODE or bias.numel() != K or x.numel() == 0 or not supported(C, K, act) \
+                or (act == "softplus" and not beta > 0):
             raise RuntimeError("gps_gaussian_amd: head: unsupported configuration: input %s, weight %s, act %r, beta %r"
                                % (tuple(x.shape), tuple(weight.shape), act, beta))
         dev = x.device
-        xc = aligned16(x.detach())
-        w, b = fp32_on(dev, weight, bias)
         y = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
         cfg = (ACT_CODE[act], float(beta), float(threshold))
         call("gsr_head_forward", dev, ptr(xc), ptr(w), ptr(b), N, C, K, H, W, *cfg, ptr(y))
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(xc, w, b)     # act' is recomputed from x: y is not kept
             ctx.cfg = cfg
-            ctx.like = (weight.shape, weight.dtype, bias.dtype)
+            ctx.like = (weight.dtype, bias.dtype)
         return y
 
     @staticmethod
@@ -56,18 +52,12 @@ class _Head(torch.autograd.Function):
         xc, w, b = ctx.saved_tensors
         N, C, H, W = xc.shape
         K = w.shape[0]
-        dev = xc.device
-        wshape, wdt, bdt = ctx.like
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        needs = ctx.needs_input_grad
         dyc = aligned16(dy.to(torch.float32))
-        dx = torch.empty_like(xc) if need_x else None      # nothing is computed for the input gradient unless x wants one
-        dw = db = scratch = None
-        if need_w or need_b:
-            dw = torch.empty((K, C), dtype=torch.float32, device=dev)
-            db = torch.empty((K,), dtype=torch.float32, device=dev)
-            scratch = torch.empty((_capi.lib().gsr_head_scratch_bytes(N, C, K, H, W) // 4,), dtype=torch.float32, device=dev)
-        call("gsr_head_backward", dev, ptr(xc), ptr(w), ptr(b), None, ptr(dyc), N, C, K, H, W, *ctx.cfg, ptr(dx), ptr(dw), ptr(db), ptr(scratch))
-        return dx, dw.reshape(wshape).to(wdt) if need_w else None, db.to(bdt) if need_b else None, None, None, None
+        # nothing is computed for the input gradient unless x wants one; dw has the weight's shape, [K, C] or [K, C, 1, 1]: the same memory
+        dx, dw, db, scratch = grad_buffers(xc, needs, w.shape, _capi.lib().gsr_head_scratch_bytes, N, C, K, H, W)
+        call("gsr_head_backward", xc.device, ptr(xc), ptr(w), ptr(b), None, ptr(dyc), N, C, K, H, W, *ctx.cfg, ptr(dx), ptr(dw), ptr(db), ptr(scratch))
+        return (dx,) + param_grads(needs, dw, db, *ctx.like) + (None, None, None)
 
 
 def head(x, weight, bias, act="none", beta=1.0, threshold=20.0):
@@ -79,9 +69,8 @@ def head(x, weight, bias, act="none", beta=1.0, threshold=20.0):
 
 
 def _plain(conv):
-    """A convolution whose static configuration is the op's: 1x1, stride 1, no padding, dilation 1, groups 1, a bias, a supported (C_in, C_out)."""
-    return conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 \
-        and conv.bias is not None and conv.padding_mode == "zeros" and supported(conv.in_channels, conv.out_channels)
+    """A convolution whose static configuration is the op's: 1x1, no padding, otherwise plain_conv's, a supported (C_in, C_out)."""
+    return plain_conv(conv, 1, 0, supported)
 
 
 def _fusable(m, x):

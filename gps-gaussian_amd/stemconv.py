@@ -16,7 +16,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi, accelerate
-from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, dense_fp32_call, fp32_on, ptr, swap_class
+from ._ops import DTYPE_CODE, aligned16, autocast_dtype, call, conv_inputs, dense_fp32_call, grad_buffers, param_grads, ptr, swap_class
 
 
 def _pair(v):
@@ -34,47 +34,36 @@ def supported(C_in, C_out, kernel_size, stride, padding, dilation=1, groups=1):
 class _StemConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, out_dtype):
-        lib = _capi.lib()
-        if not x.is_cuda:
-            raise RuntimeError("gps_gaussian_amd: conv2d input must live on a GPU (no CPU fallback)")
-        if x.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4 or bias is None:
-            raise RuntimeError("gps_gaussian_amd: conv2d takes an fp32 [N, C_in, H, W] input, a [C_out, C_in, K, K] weight and a bias")
+        xc, w, b = conv_inputs("conv2d", "[N, C_in, H, W]", "[C_out, C_in, K, K]", x, weight, bias)
         if out_dtype not in DTYPE_CODE:
             raise RuntimeError("gps_gaussian_amd: conv2d returns fp32 or fp16, not %s" % out_dtype)
         N, Ci, H, W = x.shape
         Co, Ci_w, K, K2 = weight.shape
         s, p = int(stride), int(padding)
-        if Ci_w != Ci or K != K2 or bias.numel() != Co or not lib.sc_supported(Ci, Co, K, s, p):
+        if Ci_w != Ci or K != K2 or bias.numel() != Co or not _capi.lib().sc_supported(Ci, Co, K, s, p):
             raise RuntimeError("gps_gaussian_amd: conv2d: unsupported configuration: input %s, weight %s, stride %d, padding %d"
                                % (tuple(x.shape), tuple(weight.shape), s, p))
         dev = x.device
-        xc = aligned16(x.detach())
-        w, b = fp32_on(dev, weight, bias)
         Ho, Wo = (H + 2 * p - K) // s + 1, (W + 2 * p - K) // s + 1
         y = torch.empty((N, Co, Ho, Wo), dtype=out_dtype, device=dev)
         call("sc_forward", dev, ptr(xc), ptr(w), ptr(b), N, Ci, Co, H, W, K, s, p, ptr(y), DTYPE_CODE[out_dtype])
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(xc, w)
-            ctx.dims = (N, Ci, Co, H, W, K, s, p, weight.dtype, bias.dtype)
+            ctx.dims = (N, Ci, Co, H, W, K, s, p)
+            ctx.like = (weight.dtype, bias.dtype)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        lib = _capi.lib()
         xc, w = ctx.saved_tensors
-        N, Ci, Co, H, W, K, s, p, wdt, bdt = ctx.dims
-        dev = xc.device
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        N, Ci, Co, H, W, K, s, p = ctx.dims
+        needs = ctx.needs_input_grad
         dyc = aligned16(dy if dy.dtype in DTYPE_CODE else dy.to(torch.float32))
-        dx = torch.empty_like(xc) if need_x else None      # the input-gradient kernel runs only when x wants one
-        dw = db = scratch = None
-        if need_w or need_b:
-            dw = torch.empty((Co, Ci, K, K), dtype=torch.float32, device=dev)
-            db = torch.empty((Co,), dtype=torch.float32, device=dev)
-            scratch = torch.empty((lib.sc_scratch_bytes(N, Ci, Co, H, W, K, s, p) // 4 + 4,), dtype=torch.float32, device=dev)
-        call("sc_backward", dev, ptr(xc), ptr(w), ptr(dyc), DTYPE_CODE[dyc.dtype], N, Ci, Co, H, W, K, s, p, ptr(dx), ptr(dw), ptr(db), ptr(scratch))
-        return dx, dw.to(wdt) if need_w else None, db.to(bdt) if need_b else None, None, None, None
+        dx, dw, db, scratch = grad_buffers(xc, needs, w.shape, _capi.lib().sc_scratch_bytes, *ctx.dims)   # dx None: that kernel is not run
+        call("sc_backward", xc.device, ptr(xc), ptr(w), ptr(dyc), DTYPE_CODE[dyc.dtype], N, Ci, Co, H, W, K, s, p, ptr(dx), ptr(dw), ptr(db),
+             ptr(scratch))
+        return (dx,) + param_grads(needs, dw, db, *ctx.like) + (None, None, None)
 
 
 def conv2d(x, weight, bias, stride, padding, *, out_dtype=torch.float32):

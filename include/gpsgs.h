@@ -529,6 +529,10 @@ int gsr_pack_views_backward(int B, int n_views, int S2, const uint32_t *row_of_p
  * scratch (needed for dw / dbias only): DEVICE, at least gsr_head_scratch_bytes(...) =
  *     4 * C_out * (C_in + 1) * (parts + ceil(parts / 64))   bytes,  parts = N * ceil(H*W / gsr_head_tile())
  * and 0 for arguments the other entry points would refuse (the activation is not among its arguments).
+ * Scratch layout after a backward with dw, here and for sc_backward and c3_backward below (M = the elements of dw plus those of dbias, G = the group
+ * size, 64 / 64 / 32): the partials as fp32 [parts][M], each row a workgroup's dw sums followed by its dbias sums; then, where parts > G, the group
+ * sums [ceil(parts / G)][M], row g the sum of partials g*G .. min(parts, (g+1)*G) - 1.  Every sum starts from 0 and adds in index order; dw, dbias
+ * are the sum of the group sums (of the partials where parts <= G) in the same way.
  * GPSGS_E_INVALID, before any HIP call: a (C_in, C_out, act) gsr_head_supported refuses, a non-positive N, H or W, beta <= 0 (or NaN) with act 1,
  * a NULL required pointer (h, w, bias, y; h, w, bias, dy, and scratch where dw is wanted) or one off a 4-byte boundary, one of dw / dbias without
  * the other, H*W > INT_MAX - gsr_head_tile() (a pixel index inside a plane is an int; offsets into the tensors are 64-bit, so N*C*H*W has no limit
@@ -687,7 +691,7 @@ int gne_backward(const void *x, int dtype, const float *dout, const float *out, 
  * two-stage sums: per tile, then over the tiles in index order (in groups of 64, then the groups) -- no atomics, the same bits on every run.
  * scratch (needed for dw / dbias only): DEVICE, at least sc_scratch_bytes(...) =
  *     4 * C_out * (C_in * K * K + 1) * (tiles + ceil(tiles / 64))   bytes,  tiles = N * ceil(Ho / tile_h) * ceil(Wo / tile_w)
- * and 0 for arguments sc_forward would refuse.
+ * and 0 for arguments sc_forward would refuse (layout: the partials, then the group sums, as under gsr_head_scratch_bytes).
  * GPSGS_E_INVALID, before any HIP call: a configuration sc_supported refuses, a non-positive N, H or W, a dtype outside {0, 1}, 2^31 elements or
  * more in x or in y, one of dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, and scratch where dw is wanted) or a
  * misaligned one. */
@@ -712,7 +716,7 @@ int sc_backward(const float *x, const float *w, const void *dy, int dy_dtype, in
  * tiles and write one partial; the partials are added in index order, in groups of 32 and then the groups.
  * scratch (needed for dw / dbias only): DEVICE, at least c3_scratch_bytes(N, C_in, H, W) =
  *     4 * 32 * (9 * C_in + 1) * (parts + ceil(parts / 32))   bytes,  parts = min(512, N * ceil(H / 4) * ceil(W / 32))
- * and 0 for arguments c3_forward would refuse.
+ * and 0 for arguments c3_forward would refuse (layout: the partials, then the group sums, as under gsr_head_scratch_bytes).
  * GPSGS_E_INVALID, before any HIP call: channel counts c3_supported refuses, a non-positive N, H or W, relu outside {0, 1}, 2^31 elements or more
  * in x or in y, one of dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, y where relu = 1, and scratch where dw is
  * wanted) or a misaligned one. */

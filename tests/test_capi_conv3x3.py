@@ -10,7 +10,7 @@ import pytest
 from conftest import ROOT
 
 import gps_gaussian_amd  # noqa: F401
-from gps_gaussian_amd import _capi
+from gps_gaussian_amd import _capi, _ops
 
 
 def _lib():
@@ -49,9 +49,7 @@ def test_supported_is_exactly_the_table():
 
 
 def _tile(lib):
-    th, tw = C.c_int(0), C.c_int(0)
-    assert lib.c3_tile(C.byref(th), C.byref(tw)) == 0
-    return th.value, tw.value
+    return _ops.tile("c3_tile")
 
 
 def _formula(N, Ci, H, W):

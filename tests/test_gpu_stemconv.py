@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 
 import gps_gaussian_amd  # noqa: F401
-from gps_gaussian_amd import _capi, accelerate as A
+from gps_gaussian_amd import _ops, accelerate as A
 from gps_gaussian_amd import groupnorm as GN
 from gps_gaussian_amd import stemconv as SC
 
@@ -40,12 +40,8 @@ def _gamma(n):
     return n * U / (1.0 - n * U)
 
 
-@functools.lru_cache(maxsize=None)
 def _tile():
-    import ctypes as C
-    th, tw = C.c_int(0), C.c_int(0)
-    assert _capi.lib().sc_tile(C.byref(th), C.byref(tw)) == 0
-    return th.value, tw.value
+    return _ops.tile("sc_tile")
 
 
 @functools.lru_cache(maxsize=None)
