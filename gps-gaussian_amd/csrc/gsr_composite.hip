@@ -25,6 +25,128 @@
 
 namespace {
 
+// ---- walk rules that the forward and backward kernels must take identically, each written once.  The pieces take and return VALUES, never references
+// to a kernel's locals: a local whose address is taken is allocated differently, and instruction order and register use then change.
+// Staging: lane `lane` puts its fetched record into the wave's LDS slice, the conic pre-scaled for gsr_power2
+__device__ __forceinline__ void stage_record(float4 *wA, float4 *wB, int lane, float4 nA, float4 nB) {
+    wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
+    wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
+}
+template <bool EXTRA>
+__device__ __forceinline__ void stage_record(float4 *wA, float4 *wB, float *wC, float *wD, int lane, float4 nA, float4 nB, float nC, float nD) {
+    stage_record(wA, wB, lane, nA, nB);
+    wC[lane] = nC;
+    if (EXTRA) wD[lane] = nD;
+}
+
+// CONTRIB prefetch of k_composite_fwd: list entry `pos` of bin (bin_x, bin_y), its record and its instance's slot.  By reference ON PURPOSE, the one exception
+// to the rule above: only in this form do these two instantiations compile to the code they had before the rules were shared (by value: 4 more v_mov_b32).
+template <bool EXTRA>
+__device__ __forceinline__ void load_record_slot(const GsrSplat *splats, const uint32_t *point_list, const uint32_t *goff, const uint32_t *gpart, int bin_x,
+                                                     int bin_y, uint32_t pos, float4 &nA, float4 &nB, float &nC, float &nD, uint32_t &nRec) {
+    const uint32_t id = point_list[pos];
+    const SplatRec r = load_record(splats, id);
+    nA = r.A; nB = r.B; nC = r.C.x;
+    if (EXTRA) nD = r.C.y;
+    nRec = inst_slot(goff, gpart, id, r.C, bin_x, bin_y);
+}
+
+// Forward decision for one (pixel, staged splat {a, b}) pair: a pixel that is still active skips the splat if power > 0 or alpha < 1/255, saturates
+// (leaves `active`, without blending it) if T (1 - alpha) < 1e-4, and blends it otherwise.
+struct FwdPair {
+    float w, test_T;              // the blend weight alpha T (0 where nothing is blended) and T behind the splat
+    bool use;                     // this pixel blends the splat
+    lanemask_t blended, active;   // the pixels that blend it, and those still active behind it
+};
+__device__ __forceinline__ FwdPair fwd_pair(float4 a, float4 b, float pxf, float pyf, float T, lanemask_t active) {
+    FwdPair p;
+    const float dx = a.x - pxf, dy = a.y - pyf;
+    const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
+    const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power));
+    const lanemask_t valid = active & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
+    p.test_T = __builtin_fmaf(-alpha, T, T);  // T (1 - alpha), one rounding
+    const lanemask_t sat = __ballot(p.test_T < 0.0001f);
+    p.active = active & ~(valid & sat);
+    p.blended = valid & ~sat;
+    p.use = __builtin_amdgcn_inverse_ballot_w64(p.blended);
+    p.w = p.use ? alpha * T : 0.f;
+    return p;
+}
+
+// Backward decision for the pair (pixel, staged splat {a, b} at 0-based list position pos): the pairs the forward blended are those in front of
+// the pixel's last contributor that pass the forward's two skips (same arithmetic, same bits)
+struct BwdPair { float dx, dy, G, alpha; lanemask_t valid_m; };  // valid_m: the pixels that blended this splat; 0: the wave skips it
+__device__ __forceinline__ BwdPair bwd_pair(float4 a, float4 b, float pxf, float pyf, uint32_t pos, uint32_t last) {
+    BwdPair p;
+    p.dx = a.x - pxf; p.dy = a.y - pyf;
+    const float power = gsr_power2(a.z, a.w, b.x, p.dx, p.dy);
+    p.G = __builtin_amdgcn_exp2f(power);
+    p.alpha = fminf(0.99f, b.y * p.G);
+    p.valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(p.alpha < 1.f / 255.f));
+    return p;
+}
+
+// The backward's recurrence for one pair the wave did not skip, in four straight-line pieces; what an option adds to cd (the features' fd, DISTORT's
+// channel) and w = ae T sit between them at the call site.
+// Branch-free: a lane this splat does not reach (behind its last contributor, power > 0, alpha < 1/255) runs the same arithmetic with alpha = 0 and
+// G = 0: rcp(1) = 1 leaves T, bwd_alpha leaves A (0 * cd + 1 * A), and every sum receives an exact zero.
+struct BwdStep { float Ge, ae, om, rcp, T; };  // T: in front of the splat
+__device__ __forceinline__ BwdStep bwd_step(bool valid, float G, float alpha, float T) {
+    const float Ge = valid ? G : 0.f, ae = valid ? alpha : 0.f, om = 1.f - ae, rcp = __builtin_amdgcn_rcpf(om);
+    return {Ge, ae, om, rcp, T * rcp};
+}
+// cd = colour . dL/dpixel of staged splat j {b, wC[j] (, wD[j])}.  Takes the wave's LDS pointers and j, NOT the loaded values (those reorder k_composite_bwd_feat)
+template <bool EXTRA>
+__device__ __forceinline__ float bwd_colour_dot(float4 b, const float *wC, const float *wD, int j, float d0, float d1, float d2, float dd, float da) {
+    float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
+    if (EXTRA) {
+        // the two extra channels' share of cd, rounded like a colour channel's product-then-accumulate (no fma of z dd + da)
+#pragma clang fp contract(off)
+        const float zd = wD[j] * dd;
+        cd = cd + (zd + da);
+    }
+    return cd;
+}
+// Upstream carries accum_rec (the colour seen behind the splat, 3 channels) with last_alpha / last_color; only its dot product with dL/dpixel is ever
+// used, so the recurrence is carried on that scalar: A <- alpha cd + (1 - alpha) A.  Same order of operations back to front (no cancellation), 14
+// instead of 23 instructions, and nothing but T and A is carried from splat to splat.  nTb = -T_final (bg . dL/dpixel)
+struct BwdAlpha { float dL_dalpha, A; };
+__device__ __forceinline__ BwdAlpha bwd_alpha(float cd, float A, float T, float nTb, float rcp, float ae, float om) {
+    return {(cd - A) * T + nTb * rcp, ae * cd + om * A};
+}
+// Per pair only the colour terms and six MOMENTS of s = dL/dG * G are formed: S0 = sum s, Sx = sum s dx, Sy, Sxx, Sxy, Syy.  dL/dmean2D, dL/dconic and
+// dL/dopacity are linear in them and are finished once per (bin, splat) at flush time (11 fewer instructions per pair than the nine upstream terms here).
+struct BwdMom { float m_0, m_x, m_y, m_xx, m_xy, m_yy; };
+__device__ __forceinline__ BwdMom bwd_moments(float op, float dL_dalpha, float Ge, float dx, float dy) {
+    const float m_0 = (op * dL_dalpha) * Ge;  // s = dL/dG * G, with dL/dG = opacity * dL/dalpha straight through the 0.99 clamp
+    const float m_x = m_0 * dx, m_y = m_0 * dy;
+    return {m_0, m_x, m_y, m_x * dx, m_x * dy, m_y * dy};
+}
+
+// Flush: lane j turns staged splat j's parked sums into ONE 32-byte instance record + its dL/dopacity (+ EXTRA: dL/dz), at the
+// instance's SLOT `rec` (Gaussian-major; gsr_common.h); no atomics.  REC = float4s per staged splat in wAcc.  The caller sets the slot's flag last.
+// dG/d(delta) = -G (A dx + B dy), -G (C dy + B dx);  dL/dconic = -0.5 s {dx^2, dx dy, dy^2};  dL/dop = G dL/dalpha = s / op
+// the staged conic is pre-scaled: A = sa.z / (-0.5 log2 e), B = sa.w / (-log2 e), C = sb.x / (-0.5 log2 e)
+constexpr float GSR_KA = 2.f / GSR_LOG2E, GSR_KB = 1.f / GSR_LOG2E;
+template <bool EXTRA>
+__device__ __forceinline__ void flush_record(const float4 *wAcc, int REC, const float4 *wA, const float4 *wB, int lane, float ddelx_dx, float ddely_dy,
+                                             uint32_t rec, GsrGradAcc *inst_grad, float *inst_dop, float *inst_ddepth) {
+    const float4 v0 = wAcc[REC * lane], v1 = wAcc[REC * lane + 1], rs = wAcc[REC * lane + 2];
+    const float4 sa = wA[lane], sb = wB[lane];  // this lane staged splat `lane` itself: conic (sa.z, sa.w, sb.x), opacity sb.y
+    const float Sx = v0.w, Sy = v1.x, Sxx = v1.y, Sxy = v1.z, Syy = v1.w;
+    const float S0 = (rs.x + rs.y) + (rs.z + rs.w);  // arrives as 4 row sums
+    const float g_mx = ddelx_dx * (GSR_KA * sa.z * Sx + GSR_KB * sa.w * Sy);
+    const float g_my = ddely_dy * (GSR_KA * sb.x * Sy + GSR_KB * sa.w * Sx);
+    float4 *dst = reinterpret_cast<float4 *>(inst_grad + rec);  // one whole 32-byte sector
+    dst[0] = make_float4(v0.x, v0.y, v0.z, g_mx);
+    dst[1] = make_float4(g_my, -0.5f * Sxx, -0.5f * Sxy, -0.5f * Syy);
+    inst_dop[rec] = S0 * __builtin_amdgcn_rcpf(sb.y);
+    if (EXTRA) {
+        const float4 rz = wAcc[REC * lane + 3];
+        inst_ddepth[rec] = (rz.x + rz.y) + (rz.z + rz.w);
+    }
+}
+
 // ---- per-Gaussian contribution statistics (GsrContrib): a max / sum reduce-scatter of eight values ------------------------------------------
 // The forward's CONTRIB instantiation reduces the 64 per-lane weights of each staged splat to a wave sum and a wave max.  Eight splats (one
 // blend group) go through one butterfly reduce-scatter per operation, wave_reduce_scatter9's first 18 instructions: value k ends in every lane
@@ -62,23 +184,6 @@ __device__ __forceinline__ float wave_reduce_scatter8(const float (&v)[8], bool 
     return r;
 }
 
-// CONTRIB: a lane's prefetch of the splat at list position pos -- the record as the plain forward loads it, plus its bin rect (the whole third float4)
-// and from it the instance's slot, as k_composite_bwd's stage() forms it
-template <bool EXTRA>
-__device__ __forceinline__ void contrib_fetch(const GsrSplat *__restrict__ splats, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ goff,
-                                              const uint32_t *__restrict__ gpart, int bin_x, int bin_y, uint32_t pos, float4 &nA, float4 &nB, float &nC,
-                                              float &nD, uint32_t &nRec) {
-    const uint32_t id = point_list[pos];
-    const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-    nA = s[0]; nB = s[1];
-    const float4 c = s[2];
-    nC = c.x;
-    if (EXTRA) nD = c.y;
-    const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-    const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-    nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
-}
-
 // EXTRA: the opt-in depth and alpha maps (GsrViewExt.out_depth / out_alpha) -- two more channels of the same blend, background 0:
 // depth = sum z_i alpha_i T_i (z_i = the view-space depth in the splat record's `depth` slot), alpha = sum alpha_i T_i.  The record already carries
 // z next to b, so the gather is the same 48-byte record; only one LDS word per staged splat and two accumulators are added.
@@ -111,12 +216,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
     const uint32_t list_pos = xcd_list_pos(blockIdx.x, hdr->num_busy_wgs);
     const WaveGeom g = wave_geom(W, H, bx, bins, wg_order, list_pos);
     if (hdr->overflow) {  // nothing can be rendered from truncated lists: a deterministic zero image instead of uninitialised memory
-        fwd_write_blank(g, W, H, out_color, final_T, n_contrib);
-        if (EXTRA && g.inside) {
-            const size_t q = (size_t)g.py * W + g.px;
-            if (out_depth) out_depth[q] = 0.f;
-            if (out_alpha) out_alpha[q] = 0.f;
-        }
+        fwd_write_blank<EXTRA>(g, W, H, out_color, final_T, n_contrib, out_depth, out_alpha);
         if (DISTORT && g.inside) {  // a zero map (the backward of an overflowed view does nothing: the totals are zeroed only for tidiness)
             const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
             out_distort[q] = 0.f;
@@ -134,43 +234,37 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
     float DI = 0.f, DS = 0.f;  // DISTORT: sum_i w_i (zs_i A_<i - DS_<i) and DS = sum w zs, zs = z - z0
     uint32_t last = 0;      // 1-based list position of the last splat that contributed (n_contrib), up to the previous round
     uint32_t last_rnd = 0;  // ... 1-based slot of the last contributor inside the current round (0: none): an inline constant per select
-    // Per-lane predicates live as wave-uniform 64-bit masks in SGPRs and are combined on the scalar unit: one v_cmp per test, never a
-    // second compare for the complement; __builtin_amdgcn_inverse_ballot_w64 hands a mask back to v_cndmask for free.
-    typedef unsigned long long lanemask_t;
     lanemask_t active = __ballot(g.inside);  // pixels inside the image that are not yet saturated
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r0), r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r1);
     float z0 = 0.f;  // DISTORT: the reference depth, the bin list's first entry's (wave-uniform; the backward takes the same)
     if constexpr (DISTORT) {
-        if (r0 < r1) z0 = reinterpret_cast<const float4 *>(splats + point_list[r0])[2].y;
+        if (r0 < r1) z0 = load_record(splats, point_list[r0]).C.y;
     }
 
     float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
     float nC = 0.f, nD = 0.f;
-    uint32_t nRec = 0;  // CONTRIB: the slot of this lane's prefetched instance (k_composite_bwd's stage())
+    uint32_t nRec = 0;  // CONTRIB: the slot of this lane's prefetched instance, as the backward forms it
     if constexpr (CONTRIB) {
-        if (r0 + g.lane < r1) contrib_fetch<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, r0 + g.lane, nA, nB, nC, nD, nRec);  // prefetch round 0
+        if (r0 + g.lane < r1) load_record_slot<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, r0 + g.lane, nA, nB, nC, nD, nRec);  // prefetch round 0
     } else if (r0 + g.lane < r1) {  // prefetch round 0
-        const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[r0 + g.lane]);
-        nA = s[0]; nB = s[1]; nC = s[2].x;
-        if (EXTRA) nD = s[2].y;
+        const SplatRec r = load_record(splats, point_list[r0 + g.lane]);
+        nA = r.A; nB = r.B; nC = r.C.x;
+        if (EXTRA) nD = r.C.y;
     }
     for (uint32_t base = r0; base < r1; base += WAVE) {
         if (active == 0ull) break;  // every pixel of this bin is saturated (or outside the image)
         wave_sync_lds();            // previous round fully consumed
-        wA[g.lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);  // conic pre-scaled for gsr_power2
-        wB[g.lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
-        wC[g.lane] = nC;
-        if (EXTRA) wD[g.lane] = nD;
+        stage_record<EXTRA>(wA, wB, wC, wD, g.lane, nA, nB, nC, nD);
         const uint32_t curRec = nRec;
         wave_sync_lds();
         const uint32_t nk = base + WAVE + g.lane;
         nB.y = 0.f;  // a slot without a splat blends nothing (opacity 0 -> alpha 0 < 1/255; stale x, y, conic stay finite)
         if constexpr (CONTRIB) {
-            if (nk < r1) contrib_fetch<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, nk, nA, nB, nC, nD, nRec);  // prefetch the next round
+            if (nk < r1) load_record_slot<EXTRA>(splats, point_list, goff, gpart, g.bin % bx, g.bin / bx, nk, nA, nB, nC, nD, nRec);  // prefetch the next round
         } else if (nk < r1) {  // prefetch the next round while this one is blended
-            const float4 *s = reinterpret_cast<const float4 *>(splats + point_list[nk]);
-            nA = s[0]; nB = s[1]; nC = s[2].x;
-            if (EXTRA) nD = s[2].y;
+            const SplatRec r = load_record(splats, point_list[nk]);
+            nA = r.A; nB = r.B; nC = r.C.x;
+            if (EXTRA) nD = r.C.y;
         }
         const int cnt = (int)min((uint32_t)WAVE, r1 - base);
         uint32_t n_blend = 0;  // CONTRIB: lane j = the number of pixels staged splat j was blended into (0 for a group that was not walked)
@@ -187,15 +281,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                     const float4 a = wA[j];
                     const float4 b = wB[j];
                     const float c2 = wC[j];
-                    const float dx = a.x - pxf, dy = a.y - pyf;
-                    const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
-                    const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power));
-                    const lanemask_t valid = active & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
-                    const float test_T = __builtin_fmaf(-alpha, T, T);  // T (1 - alpha), one rounding
-                    const lanemask_t sat = __ballot(test_T < 0.0001f);
-                    active &= ~(valid & sat);
-                    const bool use = __builtin_amdgcn_inverse_ballot_w64(valid & ~sat);
-                    const float w = use ? alpha * T : 0.f;
+                    const FwdPair p = fwd_pair(a, b, pxf, pyf, T, active);
+                    active = p.active;
+                    const float w = p.w;
                     C0 += b.z * w;
                     C1 += b.w * w;
                     C2 += c2 * w;
@@ -210,11 +298,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd(int W, int H, int 
                     }
                     if constexpr (CONTRIB) {
                         wv[u] = w;
-                        const uint32_t nb = (uint32_t)__builtin_popcountll(valid & ~sat);  // (scalar)
+                        const uint32_t nb = (uint32_t)__builtin_popcountll(p.blended);  // (scalar)
                         n_blend = __builtin_amdgcn_inverse_ballot_w64(1ull << j) ? nb : n_blend;  // lane j takes it
                     }
-                    T = use ? test_T : T;
-                    last_rnd = use ? (uint32_t)(j + 1) : last_rnd;
+                    T = p.use ? p.test_T : T;
+                    last_rnd = p.use ? (uint32_t)(j + 1) : last_rnd;
                 }
                 if constexpr (CONTRIB) {
                     const bool upper8 = (g.lane & 8) != 0;
@@ -322,7 +410,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             UA = totals[q];
             UD = totals[npix + q];
         }
-        z0 = reinterpret_cast<const float4 *>(splats + point_list[g.r0])[2].y;  // (g.r0 < g.r1 here)
+        z0 = load_record(splats, point_list[g.r0]).C.y;  // (g.r0 < g.r1 here)
     }
     const float bg_dot = bg[0] * d0 + bg[1] * d1 + bg[2] * d2;
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
@@ -344,64 +432,33 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
     const int bin_x = g.bin % bx, bin_y = g.bin / bx;
     auto stage = [&](uint32_t list_pos) {
         const uint32_t id = point_list[list_pos];
-        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-        nA = s[0]; nB = s[1];
-        const float4 c = s[2];
-        nC = c.x;
-        if (EXTRA) nD = c.y;
-        const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-        const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-        nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+        const SplatRec r = load_record(splats, id);
+        nA = r.A; nB = r.B; nC = r.C.x;
+        if (EXTRA) nD = r.C.y;
+        nRec = inst_slot(goff, gpart, id, r.C, bin_x, bin_y);
     };
     if ((int64_t)lane <= max_last - 1) stage(g.r0 + (uint32_t)(max_last - 1 - lane));
     for (int64_t top = max_last - 1; top >= 0; top -= WAVE) {
         const int cnt = (int)min((int64_t)WAVE, top + 1);
         wave_sync_lds();
-        wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);  // conic pre-scaled for gsr_power2 (as the forward)
-        wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
-        wC[lane] = nC;
-        if (EXTRA) wD[lane] = nD;
+        stage_record<EXTRA>(wA, wB, wC, wD, lane, nA, nB, nC, nD);
         const uint32_t curRec = nRec;
         wave_sync_lds();
         const int64_t ntop = top - WAVE;
         if (ntop - lane >= 0) stage(g.r0 + (uint32_t)(ntop - lane));  // prefetch the next round
-        unsigned long long touched = 0ull;  // which staged splats received any gradient (wave-uniform)
+        lanemask_t touched = 0ull;  // which staged splats received any gradient (wave-uniform)
         for (int j = 0; j < cnt; j++) {
             const uint32_t pos = (uint32_t)(top - j);
             const float4 a = wA[j];
             const float4 b = wB[j];
-            const float dx = a.x - pxf, dy = a.y - pyf;
-            const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
-            const float G = __builtin_amdgcn_exp2f(power);
-            const float alpha = fminf(0.99f, b.y * G);
-            const unsigned long long valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
-            if (valid_m == 0ull) continue;  // wave-uniform
-            const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
+            const BwdPair p = bwd_pair(a, b, pxf, pyf, pos, last);
+            if (p.valid_m == 0ull) continue;  // wave-uniform
+            const bool valid = __builtin_amdgcn_inverse_ballot_w64(p.valid_m);
             touched |= 1ull << j;
-
-            // Per pair only the colour terms and six MOMENTS of s = dL/dG * G are formed: S0 = sum s, Sx = sum s dx, Sy, Sxx,
-            // Sxy, Syy.  dL/dmean2D, dL/dconic and dL/dopacity are linear in them and are finished once per (bin, splat)
-            // at flush time (11 fewer instructions per pair than forming the nine upstream terms here).
-            // Branch-free: a lane this splat does not reach (behind its last contributor, power > 0, alpha < 1/255) runs the
-            // same arithmetic with alpha = 0 and G = 0: rcp(1) = 1 leaves T, the recurrence below leaves A (0 * cd + 1 * A), and
-            // every sum receives an exact zero.
-            // Upstream carries accum_rec (the colour seen behind the splat, 3 channels) with last_alpha / last_color; only its
-            // dot product with dL/dpixel is ever used, so the recurrence is carried on that scalar: A <- alpha cd + (1 - alpha) A
-            // with cd = colour . dL/dpixel.  Same order of operations back to front (no cancellation), 14 instead of 23
-            // instructions, and nothing but T and A is carried from splat to splat.
-            const float Ge = valid ? G : 0.f;
-            const float ae = valid ? alpha : 0.f;
-            const float om = 1.f - ae;
-            const float rcp = __builtin_amdgcn_rcpf(om);
-            T = T * rcp;
-            float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
-            if (EXTRA) {
-                // the two extra channels' share of cd, rounded like a colour channel's product-then-accumulate (no fma of z dd + da)
-#pragma clang fp contract(off)
-                const float zd = wD[j] * dd;
-                cd = cd + (zd + da);
-            }
-            const float w = ae * T;  // dchannel/dcolour
+            const BwdStep s = bwd_step(valid, p.G, p.alpha, T);
+            T = s.T;
+            float cd = bwd_colour_dot<EXTRA>(b, wC, wD, j, d0, d1, d2, dd, da);
+            const float w = s.ae * T;  // dchannel/dcolour
             float dzv = 0.f;         // DISTORT: this pixel's g d dist / d z_i
             if constexpr (DISTORT) {
                 const float zs = wD[j] - z0;
@@ -410,25 +467,18 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
                 UA = __builtin_fmaf(-2.f, w, UA);
                 UD = __builtin_fmaf(-2.f * w, zs, UD);
             }
-            const float dL_dalpha = (cd - A) * T + nTb * rcp;
-            A = ae * cd + om * A;
-            const float g_r = w * d0;
-            const float g_g = w * d1;
-            const float g_b = w * d2;
-            const float m_0 = (b.y * dL_dalpha) * Ge;  // s = dL/dG * G, with dL/dG = opacity * dL/dalpha straight through the 0.99 clamp
-            const float m_x = m_0 * dx;
-            const float m_y = m_0 * dy;
-            const float m_xx = m_x * dx;
-            const float m_xy = m_x * dy;
-            const float m_yy = m_y * dy;
-            const float red[9] = {g_r, g_g, g_b, m_x, m_y, m_xx, m_xy, m_yy, m_0};
+            const BwdAlpha r = bwd_alpha(cd, A, T, nTb, s.rcp, s.ae, s.om);
+            A = r.A;
+            const float g_r = w * d0, g_g = w * d1, g_b = w * d2;  // in front of the moments: the statement order decides the schedule
+            const BwdMom mom = bwd_moments(b.y, r.dL_dalpha, s.Ge, p.dx, p.dy);
+            const float red[9] = {g_r, g_g, g_b, mom.m_x, mom.m_y, mom.m_xx, mom.m_xy, mom.m_yy, mom.m_0};
             float ra = 0.f;
             if constexpr (ABSGRAD) {
                 // s (A dx + B dy) and s (C dy + B dx) up to the factor -2 / log2 e of the pre-scaled conic (applied at flush time); a lane the splat
                 // does not reach has m_0 = 0 and adds exact zeros.  (Formed in front of the reduce-scatter so that the two DPP chains interleave.)
                 const float hb = 0.5f * a.w;
-                const float tx = a.z * m_x + hb * m_y;
-                const float ty = b.x * m_y + hb * m_x;
+                const float tx = a.z * mom.m_x + hb * mom.m_y;
+                const float ty = b.x * mom.m_y + hb * mom.m_x;
                 ra = wave_row_sum(swap_absadd32(tx, ty));  // rows 0, 1: |t_x| of the row pairs (0, 2), (1, 3); rows 2, 3: |t_y|
             }
             const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
@@ -444,28 +494,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd(int W, int H, int 
             }
         }
         wave_sync_lds();
-        if ((touched >> lane) & 1ull) {  // lane j parks staged splat j's sums as ONE 32-byte instance record + its dL/dopacity (no atomics)
-            const float4 v0 = wAcc[REC * lane], v1 = wAcc[REC * lane + 1], rs = wAcc[REC * lane + 2];
-            const float4 sa = wA[lane], sb = wB[lane];  // this lane staged splat `lane` itself: conic (sa.z, sa.w, sb.x), opacity sb.y
-            const float Sx = v0.w, Sy = v1.x, Sxx = v1.y, Sxy = v1.z, Syy = v1.w;
-            const float S0 = (rs.x + rs.y) + (rs.z + rs.w);  // arrives as 4 row sums
-            // dG/d(delta) = -G (A dx + B dy), -G (C dy + B dx);  dL/dconic = -0.5 s {dx^2, dx dy, dy^2};  dL/dop = G dL/dalpha = s / op
-            // the staged conic is pre-scaled: A = sa.z / (-0.5 log2 e), B = sa.w / (-log2 e), C = sb.x / (-0.5 log2 e)
-            const float kA = 2.f / GSR_LOG2E, kB = 1.f / GSR_LOG2E;
-            const float g_mx = ddelx_dx * (kA * sa.z * Sx + kB * sa.w * Sy);
-            const float g_my = ddely_dy * (kA * sb.x * Sy + kB * sa.w * Sx);
-            // the record goes to the instance's SLOT (Gaussian-major; gsr_common.h)
-            float4 *dst = reinterpret_cast<float4 *>(inst_grad + curRec);  // one whole 32-byte sector
-            dst[0] = make_float4(v0.x, v0.y, v0.z, g_mx);
-            dst[1] = make_float4(g_my, -0.5f * Sxx, -0.5f * Sxy, -0.5f * Syy);
-            inst_dop[curRec] = S0 * __builtin_amdgcn_rcpf(sb.y);
-            if (EXTRA) {
-                const float4 rz = wAcc[REC * lane + 3];
-                inst_ddepth[curRec] = (rz.x + rz.y) + (rz.z + rz.w);
-            }
+        if ((touched >> lane) & 1ull) {  // lane j flushes staged splat j
+            flush_record<EXTRA>(wAcc, REC, wA, wB, lane, ddelx_dx, ddely_dy, curRec, inst_grad, inst_dop, inst_ddepth);
             if constexpr (ABSGRAD) {  // in the units of g_mx / g_my (NDC-scaled); a fixed order, never negative
                 const float4 ab = wAcc[REC * lane + AB];
-                inst_absgrad[curRec] = make_float2(ddelx_dx * (kA * (ab.x + ab.y)), ddely_dy * (kA * (ab.z + ab.w)));
+                inst_absgrad[curRec] = make_float2(ddelx_dx * (GSR_KA * (ab.x + ab.y)), ddely_dy * (GSR_KA * (ab.z + ab.w)));
             }
             inst_valid[curRec] = 1;
         }
@@ -502,12 +535,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
     const size_t npix = (size_t)W * H;
     if (hdr->overflow) {
         if (chunk0) {
-            fwd_write_blank(g, W, H, out_color, final_T, n_contrib);
-            if (EXTRA && g.inside) {
-                const size_t q = (size_t)g.py * W + g.px;
-                if (out_depth) out_depth[q] = 0.f;
-                if (out_alpha) out_alpha[q] = 0.f;
-            }
+            fwd_write_blank<EXTRA>(g, W, H, out_color, final_T, n_contrib, out_depth, out_alpha);
         }
         if (g.inside) {
             const size_t q = (size_t)g.py * W + g.px;
@@ -527,7 +555,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
 #pragma unroll
     for (int k = 0; k < NF; k++) acc[k] = 0.f;
     uint32_t last = 0, last_rnd = 0;
-    typedef unsigned long long lanemask_t;
     lanemask_t active = __ballot(g.inside);
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r0), r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.r1);
 
@@ -536,9 +563,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
     float nF[NF];
     auto fetch = [&](uint32_t k) {  // list entry k: its 48-byte record and its NF features (0 past the last channel)
         const uint32_t id = point_list[k];
-        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-        nA = s[0]; nB = s[1]; nC = s[2].x;
-        if (EXTRA) nD = s[2].y;
+        const SplatRec r = load_record(splats, id);
+        nA = r.A; nB = r.B; nC = r.C.x;
+        if (EXTRA) nD = r.C.y;
         const float *f = fbase + (size_t)(row0 + id) * (size_t)F;
 #pragma unroll
         for (int c = 0; c < NF; c++) nF[c] = c < nc ? f[c] : 0.f;
@@ -549,10 +576,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
     for (uint32_t base = r0; base < r1; base += WAVE) {
         if (active == 0ull) break;
         wave_sync_lds();
-        wA[g.lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
-        wB[g.lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
-        wC[g.lane] = nC;
-        if (EXTRA) wD[g.lane] = nD;
+        stage_record<EXTRA>(wA, wB, wC, wD, g.lane, nA, nB, nC, nD);
 #pragma unroll
         for (int c = 0; c < NF; c += 4) *reinterpret_cast<float4 *>(wF + g.lane * FS + c) = make_float4(nF[c], nF[c + 1], nF[c + 2], nF[c + 3]);
         wave_sync_lds();
@@ -569,15 +593,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
                     const float4 a = wA[j];
                     const float4 b = wB[j];
                     const float c2 = wC[j];
-                    const float dx = a.x - pxf, dy = a.y - pyf;
-                    const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
-                    const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power));
-                    const lanemask_t valid = active & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
-                    const float test_T = __builtin_fmaf(-alpha, T, T);
-                    const lanemask_t sat = __ballot(test_T < 0.0001f);
-                    active &= ~(valid & sat);
-                    const bool use = __builtin_amdgcn_inverse_ballot_w64(valid & ~sat);
-                    const float w = use ? alpha * T : 0.f;
+                    const FwdPair p = fwd_pair(a, b, pxf, pyf, T, active);
+                    active = p.active;
+                    const float w = p.w;
                     C0 += b.z * w;
                     C1 += b.w * w;
                     C2 += c2 * w;
@@ -593,8 +611,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_fwd_feat(int W, int H,
                         acc[c + 2] += f.z * w;
                         acc[c + 3] += f.w * w;
                     }
-                    T = use ? test_T : T;
-                    last_rnd = use ? (uint32_t)(j + 1) : last_rnd;
+                    T = p.use ? p.test_T : T;
+                    last_rnd = p.use ? (uint32_t)(j + 1) : last_rnd;
                 }
             }
         }
@@ -692,14 +710,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H,
     const int bin_x = g.bin % bx, bin_y = g.bin / bx;
     auto stage = [&](uint32_t list_pos) {
         const uint32_t id = point_list[list_pos];
-        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-        nA = s[0]; nB = s[1];
-        const float4 c = s[2];
-        nC = c.x;
-        if (EXTRA) nD = c.y;
-        const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-        const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-        nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+        const SplatRec r = load_record(splats, id);
+        nA = r.A; nB = r.B; nC = r.C.x;
+        if (EXTRA) nD = r.C.y;
+        nRec = inst_slot(goff, gpart, id, r.C, bin_x, bin_y);
         nId = id;
         nHas = true;
     };
@@ -707,10 +721,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H,
     for (int64_t top = max_last - 1; top >= 0; top -= WAVE) {
         const int cnt = (int)min((int64_t)WAVE, top + 1);
         wave_sync_lds();
-        wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
-        wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
-        wC[lane] = nC;
-        if (EXTRA) wD[lane] = nD;
+        stage_record<EXTRA>(wA, wB, wC, wD, lane, nA, nB, nC, nD);
         {  // this round's feature rows (a slot without a splat: zeros)
             const float *f = features + (size_t)(row0 + nId) * (size_t)F;
 #pragma unroll
@@ -728,30 +739,18 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H,
         wave_sync_lds();
         const int64_t ntop = top - WAVE;
         if (ntop - lane >= 0) stage(g.r0 + (uint32_t)(ntop - lane));
-        unsigned long long touched = 0ull;
+        lanemask_t touched = 0ull;
         for (int j = 0; j < cnt; j++) {
             const uint32_t pos = (uint32_t)(top - j);
             const float4 a = wA[j];
             const float4 b = wB[j];
-            const float dx = a.x - pxf, dy = a.y - pyf;
-            const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
-            const float G = __builtin_amdgcn_exp2f(power);
-            const float alpha = fminf(0.99f, b.y * G);
-            const unsigned long long valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
-            if (valid_m == 0ull) continue;
-            const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
+            const BwdPair p = bwd_pair(a, b, pxf, pyf, pos, last);
+            if (p.valid_m == 0ull) continue;
+            const bool valid = __builtin_amdgcn_inverse_ballot_w64(p.valid_m);
             touched |= 1ull << j;
-            const float Ge = valid ? G : 0.f;
-            const float ae = valid ? alpha : 0.f;
-            const float om = 1.f - ae;
-            const float rcp = __builtin_amdgcn_rcpf(om);
-            T = T * rcp;
-            float cd = b.z * d0 + b.w * d1 + wC[j] * d2;
-            if (EXTRA) {
-#pragma clang fp contract(off)
-                const float zd = wD[j] * dd;
-                cd = cd + (zd + da);
-            }
+            const BwdStep s = bwd_step(valid, p.G, p.alpha, T);
+            T = s.T;
+            float cd = bwd_colour_dot<EXTRA>(b, wC, wD, j, d0, d1, d2, dd, da);
             float fd = 0.f;  // the features' share: sum_c f[c] dL/dfeat[c]
 #pragma unroll
             for (int c = 0; c < NG; c += 4) {
@@ -762,19 +761,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H,
                 fd += f.w * gf[c + 3];
             }
             cd = cd + fd;
-            const float w = ae * T;
-            const float dL_dalpha = (cd - A) * T + nTb * rcp;
-            A = ae * cd + om * A;
-            const float g_r = w * d0;
-            const float g_g = w * d1;
-            const float g_b = w * d2;
-            const float m_0 = (b.y * dL_dalpha) * Ge;
-            const float m_x = m_0 * dx;
-            const float m_y = m_0 * dy;
-            const float m_xx = m_x * dx;
-            const float m_xy = m_x * dy;
-            const float m_yy = m_y * dy;
-            const float red[9] = {g_r, g_g, g_b, m_x, m_y, m_xx, m_xy, m_yy, m_0};
+            const float w = s.ae * T;
+            const BwdAlpha r = bwd_alpha(cd, A, T, nTb, s.rcp, s.ae, s.om);
+            A = r.A;
+            const float g_r = w * d0, g_g = w * d1, g_b = w * d2;
+            const BwdMom mom = bwd_moments(b.y, r.dL_dalpha, s.Ge, p.dx, p.dy);
+            const float red[9] = {g_r, g_g, g_b, mom.m_x, mom.m_y, mom.m_xx, mom.m_xy, mom.m_yy, mom.m_0};
             const float out = wave_reduce_scatter9(red, (lane & 8) != 0);
             if (slot >= 0) wAccF[4 * REC * j + slot] = out;
             if (EXTRA) {
@@ -784,21 +776,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_feat(int W, int H,
         }
         wave_sync_lds();
         if ((touched >> lane) & 1ull) {
-            const float4 v0 = wAcc[REC * lane], v1 = wAcc[REC * lane + 1], rs = wAcc[REC * lane + 2];
-            const float4 sa = wA[lane], sb = wB[lane];
-            const float Sx = v0.w, Sy = v1.x, Sxx = v1.y, Sxy = v1.z, Syy = v1.w;
-            const float S0 = (rs.x + rs.y) + (rs.z + rs.w);
-            const float kA = 2.f / GSR_LOG2E, kB = 1.f / GSR_LOG2E;
-            const float g_mx = ddelx_dx * (kA * sa.z * Sx + kB * sa.w * Sy);
-            const float g_my = ddely_dy * (kA * sb.x * Sy + kB * sa.w * Sx);
-            float4 *dst = reinterpret_cast<float4 *>(inst_grad + curRec);
-            dst[0] = make_float4(v0.x, v0.y, v0.z, g_mx);
-            dst[1] = make_float4(g_my, -0.5f * Sxx, -0.5f * Sxy, -0.5f * Syy);
-            inst_dop[curRec] = S0 * __builtin_amdgcn_rcpf(sb.y);
-            if (EXTRA) {
-                const float4 rz = wAcc[REC * lane + 3];
-                inst_ddepth[curRec] = (rz.x + rz.y) + (rz.z + rz.w);
-            }
+            flush_record<EXTRA>(wAcc, REC, wA, wB, lane, ddelx_dx, ddely_dy, curRec, inst_grad, inst_dop, inst_ddepth);
             inst_valid[curRec] = 1;
         }
     }
@@ -850,40 +828,31 @@ __global__ __launch_bounds__(64 * WAVES) void k_composite_bwd_featgrad(int W, in
     const int bin_x = g.bin % bx, bin_y = g.bin / bx;
     auto stage = [&](uint32_t list_pos) {
         const uint32_t id = point_list[list_pos];
-        const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-        nA = s[0]; nB = s[1];
-        const float4 c = s[2];
-        const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-        const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-        nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+        const SplatRec r = load_record(splats, id);
+        nA = r.A; nB = r.B;
+        nRec = inst_slot(goff, gpart, id, r.C, bin_x, bin_y);
     };
     if ((int64_t)lane <= max_last - 1) stage(g.r0 + (uint32_t)(max_last - 1 - lane));
     for (int64_t top = max_last - 1; top >= 0; top -= WAVE) {
         const int cnt = (int)min((int64_t)WAVE, top + 1);
         wave_sync_lds();
-        wA[lane] = make_float4(nA.x, nA.y, -0.5f * GSR_LOG2E * nA.z, -GSR_LOG2E * nA.w);
-        wB[lane] = make_float4(-0.5f * GSR_LOG2E * nB.x, nB.y, nB.z, nB.w);
+        stage_record(wA, wB, lane, nA, nB);
         const uint32_t curRec = nRec;
         wave_sync_lds();
         const int64_t ntop = top - WAVE;
         if (ntop - lane >= 0) stage(g.r0 + (uint32_t)(ntop - lane));
-        unsigned long long touched = 0ull;
+        lanemask_t touched = 0ull;
         for (int j = 0; j < cnt; j++) {
             const uint32_t pos = (uint32_t)(top - j);
             const float4 a = wA[j];
             const float4 b = wB[j];
-            const float dx = a.x - pxf, dy = a.y - pyf;
-            const float power = gsr_power2(a.z, a.w, b.x, dx, dy);
-            const float G = __builtin_amdgcn_exp2f(power);
-            const float alpha = fminf(0.99f, b.y * G);
-            const unsigned long long valid_m = __ballot(pos < last) & ~(__ballot(power > 0.f) | __ballot(alpha < 1.f / 255.f));
-            if (valid_m == 0ull) continue;  // (its weights are never read: lane j only sums when touched)
-            const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
+            const BwdPair p = bwd_pair(a, b, pxf, pyf, pos, last);
+            if (p.valid_m == 0ull) continue;  // (its weights are never read: lane j only sums when touched)
+            const bool valid = __builtin_amdgcn_inverse_ballot_w64(p.valid_m);
             touched |= 1ull << j;
-            const float ae = valid ? alpha : 0.f;
-            const float rcp = __builtin_amdgcn_rcpf(1.f - ae);
-            T = T * rcp;
-            wW[lane * WS + j] = ae * T;
+            const BwdStep s = bwd_step(valid, p.G, p.alpha, T);
+            T = s.T;
+            wW[lane * WS + j] = s.ae * T;
         }
         wave_sync_lds();
         if ((touched >> lane) & 1ull) {

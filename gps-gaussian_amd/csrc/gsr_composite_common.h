@@ -1,13 +1,16 @@
 // gsr_composite_common.h -- helpers shared by the compositing kernels (gsr_composite.hip: VALU-only design of round 1,
-// gsr_composite_mfma.hip: the matrix-core design): bin geometry of a wave, XCD-aware work-list mapping, same-wave LDS hand-off.
+// gsr_composite_tiles.hip: the matrix-core design): bin geometry of a wave, XCD-aware work-list mapping, record fetch and instance slot, LDS hand-off.
 #pragma once
 #include "gsr_common.h"
 
 namespace {
 
-
 constexpr int WAVE = 64;
 constexpr int WAVES = GSR_BINS_PER_WG;  // 4
+
+// Per-lane predicates live as wave-uniform 64-bit masks in SGPRs and are combined on the scalar unit: one v_cmp per test, never a
+// second compare for the complement; __builtin_amdgcn_inverse_ballot_w64 hands a mask back to v_cndmask for free.
+typedef unsigned long long lanemask_t;
 
 struct WaveGeom {
     int bin, px, py, lane, wid;
@@ -63,14 +66,33 @@ __device__ __forceinline__ void clear_record_flags(uint8_t *__restrict__ inst_va
     }
 }
 
-// overflowed forward: this wave's pixels become a defined blank (zero colour, T = 1, no contributor)
-__device__ __forceinline__ void fwd_write_blank(const WaveGeom &g, int W, int H, float *__restrict__ out_color, float *__restrict__ final_T,
-                                                uint32_t *__restrict__ n_contrib) {
+// overflowed forward: this wave's pixels become a defined blank (zero colour, T = 1, no contributor; EXTRA: zero depth / alpha maps where asked for)
+template <bool EXTRA = false>
+__device__ __forceinline__ void fwd_write_blank(const WaveGeom &g, int W, int H, float *out_color, float *final_T, uint32_t *n_contrib,
+                                                float *out_depth = nullptr, float *out_alpha = nullptr) {
     if (!g.inside) return;
     const size_t npix = (size_t)W * H, q = (size_t)g.py * W + g.px;
     out_color[q] = 0.f; out_color[npix + q] = 0.f; out_color[2 * npix + q] = 0.f;
     final_T[q] = 1.f;
     n_contrib[q] = 0u;
+    if (EXTRA) {
+        if (out_depth) out_depth[q] = 0.f;
+        if (out_alpha) out_alpha[q] = 0.f;
+    }
+}
+
+// A lane's fetch of splat `id`: the 48-byte record as one gather of three float4 {x,y,A,B | C,op,r,g | b,z,bin rect}
+struct SplatRec { float4 A, B, C; };
+__device__ __forceinline__ SplatRec load_record(const GsrSplat *splats, uint32_t id) {
+    const float4 *s = reinterpret_cast<const float4 *>(splats + id);
+    return {s[0], s[1], s[2]};
+}
+
+// The slot of an instance (Gaussian id, cell (bin_x, bin_y) of its bin rect c.z, c.w): the index of all that is kept per instance, Gaussian-major (gsr_common.h)
+__device__ __forceinline__ uint32_t inst_slot(const uint32_t *goff, const uint32_t *gpart, uint32_t id, float4 c, int bin_x, int bin_y) {
+    const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
+    const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
+    return gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
 }
 
 // The exponent of a (pixel, splat) pair in log2 units, from a conic that was pre-scaled when the splat was staged
@@ -88,7 +110,6 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
 
 // ---- nine simultaneous wave64 sums as a butterfly REDUCE-SCATTER ------------------------------------------------------
 // Summing 9 values over 64 lanes one by one costs 9 x 6 = 54 DPP adds.  A reduce-scatter halves the number of live

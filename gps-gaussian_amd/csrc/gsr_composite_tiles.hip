@@ -18,8 +18,6 @@
 
 namespace {
 
-typedef unsigned long long lanemask_t;
-
 // Development aid (gsr_debug_set_wg_trace, tools/wg_trace.py): when set, lane 0 of every compositing workgroup that did work leaves
 // {wall clock at start, wall clock at end (100 MHz), shader cycles spent, HW_ID | XCC_ID << 32 | list length << 40} in row blockIdx.x
 // (forward) / gridDim.x + blockIdx.x (backward): which SIMD ran which bin when -- the per-SIMD timeline behind the tail / balance numbers
@@ -406,13 +404,9 @@ __global__ __launch_bounds__(64, CG ? 2 : GSR_BWD_NOCOLOR_WAVES) void k_composit
         nB.y = 0.f;  // a slot without a splat blends nothing (opacity 0)
         if (pos >= 0) {
             const uint32_t id = point_list[r0 + (uint32_t)pos];
-            const float4 *s = reinterpret_cast<const float4 *>(splats + id);
-            nA = s[0]; nB = s[1];
-            const float4 c = s[2];
-            nC = c.x;
-            const uint32_t lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-            const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-            nRec = gpart[id >> GSR_BIN_SHIFT] + goff[id] + (uint32_t)((bin_y - y0) * (x1 - x0) + (bin_x - x0));
+            const SplatRec r = load_record(splats, id);
+            nA = r.A; nB = r.B; nC = r.C.x;
+            nRec = inst_slot(goff, gpart, id, r.C, bin_x, bin_y);
         }
     };
     stage(max_last - 1 - lane);
