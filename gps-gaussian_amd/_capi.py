@@ -91,7 +91,7 @@ _BWD = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp
 _BWD_EX = _BWD + [C.POINTER(GsrViewExt)]
 _BWD_CAMERA = _BWD_EX + [vp, vp, vp, vp, sz]
 
-# name -> (restype, argtypes) of every symbol include/gpsgs.h declares, in the header's four sections.  lib() sets the prototypes from this table, so
+# name -> (restype, argtypes) of every symbol include/gpsgs.h declares, in the header's five sections.  lib() sets the prototypes from this table, so
 # a symbol cannot be listed without one (ctypes' default `int` conversion would truncate a 64-bit device pointer silently); tests/test_capi.py
 # cross-checks the first section's names against the header and that every name has its prototype set.
 _GSR = {
@@ -184,11 +184,8 @@ _C3 = {
     "c3_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "c3_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC}
-SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC)
-# (a table of its own: tests/test_capi.py pins PROTOTYPES to the four tuples above; lib() sets both)
-C3_PROTOTYPES = dict(_C3)
-C3_SYMBOLS = tuple(_C3)
+PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3}
+SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC), tuple(_C3)
 
 _lib = None
 
@@ -203,7 +200,7 @@ def lib():
             "gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gps-gaussian_amd/csrc`). There is no CPU fallback for this path." % LIB_PATH)
     l = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **C3_PROTOTYPES}.items():
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(l, name)
         fn.restype, fn.argtypes = restype, argtypes
     if l.gpsgs_abi_version() != 4:

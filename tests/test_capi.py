@@ -1,12 +1,10 @@
 """CPU: the C-ABI library builds/loads, exports every symbol include/gpsgs.h declares, and the host shims refuse to run
 without a GPU (there is no CPU fallback in the product path)."""
-import ctypes as C
 import os
 import re
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -14,30 +12,26 @@ from conftest import ROOT
 import gps_gaussian_amd
 from gps_gaussian_amd import _capi
 
-
-def _declared_symbols():
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(?:int|size_t|const char \*)\s*\*?\s*((?:gsr|cs|gpsgs|fl|up|cv|cu)_[a-z0-9_]+)\s*\(", src)))
+import capi_run
+from capi_run import call, pointers, spec
 
 
 def test_library_exports_every_declared_symbol():
-    gps_gaussian_amd.build()
-    declared = _declared_symbols()
+    lib = capi_run.lib()
+    declared = capi_run.declared("gsr_", "cs_", "gpsgs_", "fl_", "up_", "cv_", "cu_")
     assert len(declared) >= 9
     assert sorted(_capi.SYMBOLS) == declared
-    raw = C.CDLL(_capi.LIB_PATH)
+    raw = capi_run.raw()
     for name in declared:
         assert hasattr(raw, name), name
-    lib = _capi.lib()
     assert lib.gpsgs_abi_version() == 4
     assert b"gfx950" in lib.gpsgs_build_info()
 
 
 def test_every_listed_symbol_has_its_prototype():
-    """The prototype table and the four symbol tuples are one list, and lib() leaves no symbol on ctypes' default conversion (which would pass a
+    """The prototype table and the five symbol tuples are one list, and lib() leaves no symbol on ctypes' default conversion (which would pass a
     64-bit device pointer as a C int)."""
-    names = _capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS
+    names = _capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS + _capi.C3_SYMBOLS
     assert tuple(_capi.PROTOTYPES) == names
     lib = _capi.lib()
     assert [n for n in names if getattr(lib, n).argtypes is None] == []
@@ -46,7 +40,7 @@ def test_every_listed_symbol_has_its_prototype():
 def test_python_constants_mirror_the_header():
     """Every GSR_FLAG_* / GPSGS_E_* the ctypes shim uses has the value include/gpsgs.h gives it (a flag added on one side only would
     silently select a different kernel path)."""
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
+    src = capi_run.header()
     flags = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(GSR_FLAG_[A-Z_]+)\s+(\d+)u\b", src)}
     assert {"GSR_FLAG_DEBUG", "GSR_FLAG_TIMING", "GSR_FLAG_NO_LARGE_SORT", "GSR_FLAG_COMPOSITE_TILES", "GSR_FLAG_NO_COLOR_GRAD", "GSR_FLAG_WAVE_PRIORITY"} <= set(flags)
     for name, value in flags.items():
@@ -136,8 +130,9 @@ def test_workspace_bytes_ex_and_the_limits_of_direct_lists():
 
 def test_invalid_arguments_are_rejected_without_touching_the_gpu():
     lib = _capi.lib()
-    assert lib.gsr_forward(10, 0, 16, *([None] * 5), 1.0, 1.0, 1.0, *([None] * 6), 0, 0, 0, None) == _capi.GPSGS_E_INVALID
-    assert lib.gsr_forward(10, 16, 16, *([None] * 5), 1.0, 1.0, 1.0, *([None] * 6), 0, 0, 0, None) == _capi.GPSGS_E_INVALID
+    null = dict({k: None for k in pointers("gsr_forward")}, P=10, H=16, cap=0)  # every pointer NULL, no workspace
+    assert call(lib, "gsr_forward", spec("gsr_forward", W=0, **null)) == _capi.GPSGS_E_INVALID
+    assert call(lib, "gsr_forward", spec("gsr_forward", W=16, **null)) == _capi.GPSGS_E_INVALID
     assert lib.cs_forward(None, None, None, 1, 2, 3, 4, 4, 7, None) == _capi.GPSGS_E_INVALID
     assert lib.cs_forward(None, None, None, 0, 2, 3, 4, 4, 0, None) == _capi.GPSGS_OK  # empty batch: nothing to do
 
@@ -146,15 +141,14 @@ def test_no_cpu_fallback():
     import torch
     from gps_gaussian_amd import corr, rasterizer as RZ
 
-    rs = RZ.GaussianRasterizationSettings(16, 16, 1.0, 1.0, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3, torch.zeros(3), False, False)
+    rs, kw = capi_run.cpu_view()
     r = RZ.GaussianRasterizer(rs)
-    x = torch.zeros(4, 3)
     with pytest.raises(RuntimeError, match="GPU"):
-        r(means3D=x, means2D=x, opacities=torch.zeros(4, 1), colors_precomp=x, scales=x, rotations=torch.zeros(4, 4))
+        r(**kw)
     with pytest.raises(Exception, match="SHs or precomputed colors"):
-        r(means3D=x, means2D=x, opacities=torch.zeros(4, 1), scales=x, rotations=torch.zeros(4, 4))
+        r(**{k: v for k, v in kw.items() if k != "colors_precomp"})
     with pytest.raises(Exception, match="scale/rotation pair or precomputed 3D covariance"):
-        r(means3D=x, means2D=x, opacities=torch.zeros(4, 1), colors_precomp=x)
+        r(**{k: v for k, v in kw.items() if k not in ("scales", "rotations")})
     with pytest.raises(RuntimeError, match="GPU"):
         corr.forward(torch.zeros(1, 2, 3, 4), torch.zeros(1, 1, 2, 3), 4)
 

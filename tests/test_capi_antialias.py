@@ -1,23 +1,21 @@
 """CPU: the opt-in antialiasing of the rasteriser (include/gpsgs.h GSR_FLAG_ANTIALIAS) -- the flag, the library's answer to
 gsr_supported_flags(), the keyword on every entry point, the CPU-tensor refusal, and the fp64 statement of k the GPU tests use (tests/aa_ref.py)."""
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
 
 from aa_ref import H_DIL, RHO_MIN, aa_k, aa_partials
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_run
 
 
 def _flags():
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
+    src = capi_run.header()
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(GSR_FLAG_[A-Z_]+)\s+(\d+)u\b", src)}
 
 
@@ -30,8 +28,7 @@ def test_flag_value_mirror_and_no_overlap():
 
 
 def test_library_lists_the_flag():
-    gps_gaussian_amd.build()
-    lib = _capi.lib()
+    lib = capi_run.lib()
     sup = lib.gsr_supported_flags()
     assert sup & _capi.GSR_FLAG_ANTIALIAS
     for name, v in _flags().items():  # every flag the header defines is one the library honours
@@ -53,19 +50,14 @@ def test_keyword_defaults_are_off():
 
 def _cpu_call(use_settings_attr):
     from gps_gaussian_amd import rasterizer as RZ
-    P = 4
-    z = torch.zeros
-    rs = RZ.GaussianRasterizationSettings(8, 8, 0.5, 0.5, z(3), 1.0, torch.eye(4), torch.eye(4), 0, z(3), False, False)
-    kw = {}
+    rs, kw = capi_run.cpu_view()
     if use_settings_attr:
         from collections import namedtuple
         S = namedtuple("S", RZ.GaussianRasterizationSettings._fields + ("antialiasing",))
         rs = S(*rs, True)
     else:
         kw["antialiasing"] = True
-    m3 = torch.rand(P, 3)
-    return RZ.GaussianRasterizer(rs)(means3D=m3, means2D=torch.zeros_like(m3), opacities=torch.rand(P, 1), colors_precomp=torch.rand(P, 3),
-                                     scales=torch.rand(P, 3), rotations=torch.rand(P, 4), **kw)
+    return RZ.GaussianRasterizer(rs)(**kw)
 
 
 @pytest.mark.parametrize("how", ["keyword", "settings_attribute"])
@@ -76,11 +68,10 @@ def test_cpu_tensors_refused_like_any_call(how):
 
 def test_cpu_tensors_refused_through_rasterize_gaussians():
     from gps_gaussian_amd import rasterizer as RZ
-    z = torch.zeros
-    rs = RZ.GaussianRasterizationSettings(8, 8, 0.5, 0.5, z(3), 1.0, torch.eye(4), torch.eye(4), 0, z(3), False, False)
-    m3 = torch.rand(3, 3)
+    rs, kw = capi_run.cpu_view()
     with pytest.raises(RuntimeError, match="must live on a GPU"):
-        RZ.rasterize_gaussians(m3, z(3, 3), None, torch.rand(3, 3), torch.rand(3, 1), torch.rand(3, 3), torch.rand(3, 4), None, rs, antialiasing=True)
+        RZ.rasterize_gaussians(kw["means3D"], kw["means2D"], None, kw["colors_precomp"], kw["opacities"], kw["scales"], kw["rotations"], None, rs,
+                               antialiasing=True)
 
 
 def test_k_partials_match_finite_differences_and_closed_form():

@@ -1,23 +1,18 @@
 """CPU: the opt-in camera gradients (include/gpsgs.h gsr_backward_camera) -- declarations, exports, the Python keywords and their defaults."""
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gpsgs.h")
+import capi_run
+from capi_run import call, pointers, spec
+
 NEW = ("gsr_camera_grad_scratch_bytes", "gsr_backward_camera")
-
-
-def _header():
-    with open(HEADER) as f:
-        return f.read()
 
 
 def test_new_symbols_are_declared_exported_and_mirrored():
     from gps_gaussian_amd import _capi
-    src = _header()
+    src = capi_run.header()
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, src), name
         assert name in _capi.SYMBOLS, name
@@ -31,7 +26,7 @@ def test_new_symbols_are_declared_exported_and_mirrored():
 def test_abi_and_view_ext_are_unchanged():
     import ctypes as C
     from gps_gaussian_amd import _capi
-    assert re.search(r"#define GPSGS_ABI_VERSION 4\b", _header())
+    assert re.search(r"#define GPSGS_ABI_VERSION 4\b", capi_run.header())
     assert _capi.lib().gpsgs_abi_version() == 4
     assert C.sizeof(_capi.GsrViewExt) == 80
 
@@ -47,19 +42,14 @@ def test_scratch_size():
 
 
 def test_invalid_arguments_are_refused_without_a_device():
-    import ctypes as C
     from gps_gaussian_amd import _capi
     lib = _capi.lib()
-    ext = _capi.GsrViewExt()
-    null = [None] * 19
+    # every pointer NULL, a 16 x 16 image, no workspace, a zeroed GsrViewExt
+    null = dict({k: None for k in pointers("gsr_backward_camera")}, W=16, H=16, cap=0, ext=dict(bin_capacity=0))
     # negative P / sizes: GPSGS_E_INVALID before anything touches a device
-    rc = lib.gsr_backward_camera(-1, 16, 16, *null[:5], 1.0, 0.5, 0.5, *null[:3], None, *null[:7], None, 0, 0, 0, None, C.byref(ext),
-                                 None, None, None, None, 0)
-    assert rc == _capi.GPSGS_E_INVALID
+    assert call(lib, "gsr_backward_camera", spec("gsr_backward_camera", P=-1, **null)) == _capi.GPSGS_E_INVALID
     # misaligned output pointer
-    rc = lib.gsr_backward_camera(0, 16, 16, *null[:5], 1.0, 0.5, 0.5, *null[:3], None, *null[:7], None, 0, 0, 0, None, C.byref(ext),
-                                 2, None, None, None, 0)
-    assert rc == _capi.GPSGS_E_INVALID
+    assert call(lib, "gsr_backward_camera", spec("gsr_backward_camera", P=0, cam=dict(dL_dviewmatrix=2), **null)) == _capi.GPSGS_E_INVALID
 
 
 @pytest.mark.parametrize("where", ["rasterize_gaussians", "GaussianRasterizer.forward", "render", "render_ex", "pts2render"])
@@ -79,14 +69,7 @@ def test_settings_keep_twelve_fields():
 
 
 def test_cpu_tensors_are_refused():
-    import torch
     from gps_gaussian_amd import rasterizer as RZ
-    P = 4
-    view = torch.eye(4, requires_grad=True)
-    proj = torch.eye(4, requires_grad=True)
-    campos = torch.zeros(3, requires_grad=True)
-    rs = RZ.GaussianRasterizationSettings(16, 16, 0.5, 0.5, torch.zeros(3), 1.0, view, proj, 3, campos, False, False)
-    m3 = torch.zeros(P, 3, requires_grad=True)
+    rs, kw = capi_run.cpu_view(grad=True)
     with pytest.raises(RuntimeError, match="GPU"):
-        RZ.GaussianRasterizer(rs)(means3D=m3, means2D=torch.zeros(P, 3), opacities=torch.ones(P, 1), colors_precomp=torch.ones(P, 3),
-                                  scales=torch.ones(P, 3), rotations=torch.ones(P, 4), camera_grad=True)
+        RZ.GaussianRasterizer(rs)(**kw, camera_grad=True)

@@ -2,45 +2,28 @@
 takes; the tile; the scratch formula the header states; every bad-argument case refused before any HIP call (this machine has no GPU: a call that
 reached HIP would not return GPSGS_E_INVALID)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi, _ops
 
-
-def _lib():
-    gps_gaussian_amd.build()
-    return _capi.lib()
+import capi_run
+from capi_run import D
 
 
 def test_symbols_are_declared_exported_and_bound():
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(?:int|size_t)\s+(c3_[a-z0-9_]+)\s*\(", code)))
-    assert declared == sorted(_capi.C3_SYMBOLS) == ["c3_backward", "c3_forward", "c3_scratch_bytes", "c3_supported", "c3_tile"]
-    assert "c3_forward / c3_backward" in src.split("#ifndef GPSGS_H")[0]          # the list at the top of the header names them
-    lib = _lib()
-    raw = C.CDLL(_capi.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
-        assert name in _capi.C3_PROTOTYPES and name not in _capi.PROTOTYPES
+    # (with every name in PROTOTYPES and lib()'s argtypes / restype equal to the table's entry)
+    lib = capi_run.check_section("c3_", _capi.C3_SYMBOLS, ["c3_backward", "c3_forward", "c3_scratch_bytes", "c3_supported", "c3_tile"])
     # the header's argument lists and the ctypes prototypes agree in length
-    for name in declared:
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, code).group(1)
-        assert len([a for a in args.split(",") if a.strip()]) == len(getattr(lib, name).argtypes), name
+    for name in _capi.C3_SYMBOLS:
+        assert capi_run.declared_arg_count(name) == len(getattr(lib, name).argtypes), name
     assert len(lib.c3_forward.argtypes) == 10 and len(lib.c3_backward.argtypes) == 14
     assert lib.c3_scratch_bytes.restype is C.c_size_t
-    assert lib.gpsgs_abi_version() == 4
     assert not set(_capi.C3_SYMBOLS) & set(_capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS)
 
 
 def test_supported_is_exactly_the_table():
-    lib = _lib()
+    lib = capi_run.lib()
     for Ci in range(-8, 80):
         for Co in (-32, 0, 1, 8, 16, 31, 32, 33, 48, 64):
             want = int(Co == 32 and 4 <= Ci <= 64 and Ci % 4 == 0)
@@ -59,7 +42,7 @@ def _formula(N, Ci, H, W):
 
 
 def test_tile_and_the_scratch_formula():
-    lib = _lib()
+    lib = capi_run.lib()
     TH, TW = _tile(lib)
     assert TH > 0 and TW > 0
     assert lib.c3_tile(None, None) == _capi.GPSGS_E_INVALID
@@ -85,42 +68,40 @@ def test_tile_and_the_scratch_formula():
     assert f(1, 4, 65536, 65536) == 0 and f(2147483647, 4, 2147483647, 2147483647) == 0
 
 
-P = 0x10000   # a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
-
-
-def _fwd(lib, x=P, w=P, bias=P, N=2, Ci=52, H=16, W=16, relu=1, y=P):
+# D: a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
+def _fwd(lib, x=D, w=D, bias=D, N=2, Ci=52, H=16, W=16, relu=1, y=D):
     return lib.c3_forward(x, w, bias, N, Ci, H, W, relu, y, None)
 
 
-def _bwd(lib, x=P, w=P, y=P, dy=P, N=2, Ci=52, H=16, W=16, relu=1, dx=P, dw=P, dbias=P, scratch=P):
+def _bwd(lib, x=D, w=D, y=D, dy=D, N=2, Ci=52, H=16, W=16, relu=1, dx=D, dw=D, dbias=D, scratch=D):
     return lib.c3_backward(x, w, y, dy, N, Ci, H, W, relu, dx, dw, dbias, scratch, None)
 
 
 @pytest.mark.parametrize("call", [_fwd, _bwd], ids=["forward", "backward"])
 def test_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     E = _capi.GPSGS_E_INVALID
     assert call(lib, Ci=0) == E and call(lib, Ci=3) == E and call(lib, Ci=50) == E and call(lib, Ci=68) == E and call(lib, Ci=-4) == E
     assert call(lib, N=0) == E and call(lib, N=-1) == E and call(lib, H=0) == E and call(lib, W=0) == E and call(lib, H=-16) == E
     assert call(lib, relu=2) == E and call(lib, relu=-1) == E
     assert call(lib, x=None) == E and call(lib, w=None) == E
-    assert call(lib, x=P + 4) == E and call(lib, w=P + 2) == E                                     # misaligned
+    assert call(lib, x=D + 4) == E and call(lib, w=D + 2) == E                                     # misaligned
     assert call(lib, N=1, Ci=64, H=8192, W=4096) == E                                              # x: 2^31 elements
     assert call(lib, N=4, Ci=4, H=8192, W=8192) == E                                               # x fits (2^30), y: 2^33 elements
     assert call(lib, N=1, Ci=4, H=65536, W=65536) == E
     if call is _fwd:
         assert call(lib, bias=None) == E and call(lib, y=None) == E
-        assert call(lib, y=P + 8) == E and call(lib, bias=P + 1) == E
+        assert call(lib, y=D + 8) == E and call(lib, bias=D + 1) == E
     else:
         assert call(lib, dy=None) == E and call(lib, scratch=None) == E
         assert call(lib, y=None) == E                                                              # the ReLU form needs the saved output
         assert call(lib, dw=None) == E and call(lib, dbias=None) == E                              # one without the other
-        assert call(lib, dy=P + 4) == E and call(lib, y=P + 8) == E and call(lib, dx=P + 8) == E and call(lib, dw=P + 2) == E
-        assert call(lib, dbias=P + 1) == E and call(lib, scratch=P + 8) == E
+        assert call(lib, dy=D + 4) == E and call(lib, y=D + 8) == E and call(lib, dx=D + 8) == E and call(lib, dw=D + 2) == E
+        assert call(lib, dbias=D + 1) == E and call(lib, scratch=D + 8) == E
 
 
 def test_nothing_asked_for_launches_nothing():
-    lib = _lib()
+    lib = capi_run.lib()
     assert _bwd(lib, dx=None, dw=None, dbias=None, scratch=None) == 0
     assert _bwd(lib, dx=None, dw=None, dbias=None, scratch=None, relu=0, y=None) == 0              # without ReLU y may be NULL
     assert _bwd(lib, dx=None, dw=None, dbias=None, scratch=None, Ci=6) == _capi.GPSGS_E_INVALID    # the arguments are still checked

@@ -7,37 +7,34 @@ import ctypes as C
 
 import pytest
 
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
 
-P = 0x10000   # a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
+import capi_run
+from capi_run import D
+
+# D: a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
 E = _capi.GPSGS_E_INVALID
 OK = 0
 I31 = 2 ** 31 - 1
-
-
-def _lib():
-    gps_gaussian_amd.build()
-    return _capi.lib()
 
 
 def _levels(ptrs):
     return None if ptrs is None else (C.c_void_p * 4)(*ptrs)
 
 
-def _sfwd(lib, volume=P, coords=P, out=P, N=2, H1=3, W1=5, W2=8, r=4, dtype=0, **_):
+def _sfwd(lib, volume=D, coords=D, out=D, N=2, H1=3, W1=5, W2=8, r=4, dtype=0, **_):
     return lib.cs_forward(volume, coords, out, N, H1, W1, W2, r, dtype, None)
 
 
-def _sbwd(lib, coords=P, gout=P, gvol=P, N=2, H1=3, W1=5, W2=8, r=4, dtype=0, **_):
+def _sbwd(lib, coords=D, gout=D, gvol=D, N=2, H1=3, W1=5, W2=8, r=4, dtype=0, **_):
     return lib.cs_backward(coords, gout, gvol, N, H1, W1, W2, r, dtype, None)
 
 
-def _lfwd(lib, pyr=(P, P, P, P), coords=P, out=P, N=2, H1=3, W1=5, W2=8, levels=4, r=4, dtype=0, **_):
+def _lfwd(lib, pyr=(D, D, D, D), coords=D, out=D, N=2, H1=3, W1=5, W2=8, levels=4, r=4, dtype=0, **_):
     return lib.cs_lookup_forward(_levels(pyr), coords, out, N, H1, W1, W2, levels, r, dtype, None)
 
 
-def _lbwd(lib, coords=P, gout=P, pyr=(P, P, P, P), N=2, H1=3, W1=5, W2=8, levels=4, r=4, dtype=0, **_):
+def _lbwd(lib, coords=D, gout=D, pyr=(D, D, D, D), N=2, H1=3, W1=5, W2=8, levels=4, r=4, dtype=0, **_):
     return lib.cs_lookup_backward(coords, gout, _levels(pyr), N, H1, W1, W2, levels, r, dtype, None)
 
 
@@ -48,7 +45,7 @@ IDS = ["cs_forward", "cs_backward", "cs_lookup_forward", "cs_lookup_backward"]
 
 @pytest.mark.parametrize("call", CALLS, ids=IDS)
 def test_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, N=-1) == E and call(lib, H1=-3) == E and call(lib, W1=-5) == E and call(lib, W2=-8) == E
     assert call(lib, dtype=2) == E and call(lib, dtype=-1) == E
     assert call(lib, r=-1) == E and call(lib, r=-2 ** 31) == E
@@ -73,7 +70,7 @@ def test_bad_arguments_are_refused_before_hip(call):
 
 @pytest.mark.parametrize("call", CALLS, ids=IDS)
 def test_empty_tensors_return_ok_with_null_pointers(call):
-    lib = _lib()
+    lib = capi_run.lib()
     null = dict(volume=None, coords=None, out=None, gout=None, gvol=None, pyr=(None, None, None, None))
     for empty in (dict(N=0), dict(H1=0), dict(W1=0), dict(N=0, H1=0, W1=0, W2=0)):
         assert call(lib, **empty) == OK, empty
@@ -90,21 +87,21 @@ def test_null_level_is_accepted_exactly_where_the_level_is_empty(call):
     """W2 >> l == 0: the level has no element and torch hands out NULL for it.  Here: a NULL at every level that HAS elements is refused.  A call
     that passes this check goes on to launch, so the accepting side runs on the GPU with real buffers
     (tests/test_gpu_corr_lookup_edges.py::test_capi_null_pointers_of_empty_levels_are_accepted)."""
-    lib = _lib()
+    lib = capi_run.lib()
     for W2 in (1, 2, 3, 4, 7, 8, 9):
         for levels in (1, 2, 3, 4):
             for l in range(levels):
-                ptrs = [P] * 4
+                ptrs = [D] * 4
                 ptrs[l] = None
                 if (W2 >> l) > 0:
                     assert call(lib, pyr=tuple(ptrs), W2=W2, levels=levels) == E, (W2, levels, l)
     # levels beyond `levels` are never looked at
-    assert call(lib, pyr=(P, None, None, None), N=0, levels=1) == OK
+    assert call(lib, pyr=(D, None, None, None), N=0, levels=1) == OK
 
 
 @pytest.mark.parametrize("call", CALLS, ids=IDS)
 def test_more_rows_than_an_int_counts_are_refused(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, N=2, H1=2 ** 15, W1=2 ** 15) == E                # N*H1*W1 = 2^31
     assert call(lib, N=1, H1=2 ** 16, W1=2 ** 16) == E                # 2^32: an int product would wrap to 0
     assert call(lib, N=I31, H1=I31, W1=I31) == E                      # a product that does not fit 64 bits either
@@ -116,7 +113,7 @@ def test_more_rows_than_an_int_counts_are_refused(call):
 @pytest.mark.parametrize("call", [_sbwd, _lbwd], ids=[IDS[1], IDS[3]])
 def test_backward_block_counts_beyond_a_grid_are_refused(call):
     """One thread per gradient element (per quad: k_cs_bwd4) in blocks of 256; the count used to be cast to unsigned."""
-    lib = _lib()
+    lib = capi_run.lib()
     # 2^30 rows x 2^11 columns = 2^41 elements -> 2^33 blocks (the cast kept none of them); as quads 2^31 blocks
     assert call(lib, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 11) == E
     # I31 rows x 513 columns (odd: the scalar kernel in both): 2^31 + 2^23 + ... blocks (the cast kept a few million)
@@ -129,14 +126,14 @@ def test_backward_block_counts_beyond_a_grid_are_refused(call):
         # quads are counted where W2 % 4 == 0 and the pointer is 16-byte aligned: 2^30 x 2^11 / 4 = 2^39 quads = 2^31 blocks, one too many ...
         assert call(lib, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 11) == E
         # ... and the same elements through a misaligned pointer are 2^33 blocks of the scalar kernel
-        assert call(lib, gvol=P + 4, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 11) == E
+        assert call(lib, gvol=D + 4, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 11) == E
         # 2^40 elements: 2^30 blocks of quads would fit, 2^32 blocks of the scalar kernel (misaligned pointer) do not
-        assert call(lib, gvol=P + 4, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 10) == E
+        assert call(lib, gvol=D + 4, N=2 ** 10, H1=2 ** 10, W1=2 ** 10, W2=2 ** 10) == E
 
 
 @pytest.mark.parametrize("call", CALLS, ids=IDS)
 def test_a_radius_whose_window_overflows_an_int_is_refused(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, r=2 ** 30) == E and call(lib, r=I31) == E        # 2 r + 1 = 2^31 + 1
     assert call(lib, r=2 ** 30, N=0) == E                             # checked before the empty return
     assert call(lib, r=2 ** 30 - 1, N=0) == OK                        # 2 r + 1 = INT_MAX: the largest radius there is

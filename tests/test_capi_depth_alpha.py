@@ -1,28 +1,20 @@
 """CPU: the C-ABI of the opt-in depth / alpha maps -- GsrViewExt keeps its 80-byte layout (the maps take the former reserved words, ABI 4),
 the ctypes mirror matches the header, and the workspace of the depth / alpha backward is the default one plus one float per instance slot."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
+
+import capi_run
 
 
 def test_view_ext_layout_is_unchanged_and_mirrored(tmp_path):
     """The C compiler's offsets of the new fields equal the ctypes ones; the struct is still 80 bytes; forward outputs and backward gradients share
     their slots."""
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpsgs.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(GsrViewExt), '
-                   "offsetof(GsrViewExt, dL_dcov3D), offsetof(GsrViewExt, out_depth), offsetof(GsrViewExt, dL_ddepth), offsetof(GsrViewExt, out_alpha), "
-                   "offsetof(GsrViewExt, dL_dalpha)); return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    got = capi_run.c_values(tmp_path, ["sizeof(GsrViewExt)", "offsetof(GsrViewExt, dL_dcov3D)", "offsetof(GsrViewExt, out_depth)",
+                                       "offsetof(GsrViewExt, dL_ddepth)", "offsetof(GsrViewExt, out_alpha)", "offsetof(GsrViewExt, dL_dalpha)"])
     E = _capi.GsrViewExt
     assert got == [80, 56, 64, 64, 72, 72]
     assert [C.sizeof(E), E.dL_dcov3D.offset, E._depth.offset, E._alpha.offset] == [80, 56, 64, 72]
@@ -33,10 +25,10 @@ def test_view_ext_layout_is_unchanged_and_mirrored(tmp_path):
 
 
 def test_abi_version_and_symbols():
-    lib = _capi.lib()
+    lib = capi_run.lib()
     assert lib.gpsgs_abi_version() == 4
     assert "gsr_workspace_bytes_depth_alpha" in _capi.SYMBOLS
-    hdr = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
+    hdr = capi_run.header()
     assert re.search(r"size_t gsr_workspace_bytes_depth_alpha\(int P, int width, int height, int64_t instance_capacity, uint32_t bin_capacity, "
                      r"int forward_only\);", hdr)
 
@@ -44,7 +36,7 @@ def test_abi_version_and_symbols():
 @pytest.mark.parametrize("P,W,H,cap,bcap", [(30000, 256, 256, 1 << 20, 0), (600000, 1024, 1024, 5 << 20, 1024), (2400000, 2048, 2048, 30 << 20, 1024),
                                               (1, 8, 8, 1, 0), (0, 17, 9, 0, 0)])
 def test_workspace_sizes(P, W, H, cap, bcap):
-    lib = _capi.lib()
+    lib = capi_run.lib()
     plain = lib.gsr_workspace_bytes_ex(P, W, H, cap, bcap, 0)
     extra = lib.gsr_workspace_bytes_depth_alpha(P, W, H, cap, bcap, 0)
     assert plain > 0
@@ -58,28 +50,19 @@ def test_workspace_sizes(P, W, H, cap, bcap):
 
 def test_default_workspace_sizes_are_pinned():
     """The default layout did not move: the training workspace sizes of the parent commit, byte for byte."""
-    lib = _capi.lib()
-    assert lib.gsr_workspace_bytes(30000, 256, 256, 1 << 20) == PINNED[0]
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 0) == PINNED[1]
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 1) == PINNED[2]
-
-
-PINNED = (54450688, 454462464, 258065920)  # computed from the parent commit's gsr_layout()
+    capi_run.assert_default_sizes(capi_run.lib())
 
 
 def test_python_api_is_opt_in():
     """rasterize_gaussians / GaussianRasterizer.forward / render_api take the maps as keyword opt-ins; the default signatures still work as before
     (no GPU: the call is refused for CPU tensors before anything is launched)."""
     import inspect
-    import torch
     from gps_gaussian_amd import rasterizer as RZ
     from gps_gaussian_amd import render_api
     assert inspect.signature(RZ.rasterize_gaussians).parameters["return_depth_alpha"].default is False
     assert inspect.signature(RZ.GaussianRasterizer.forward).parameters["return_depth_alpha"].default is False
     assert inspect.signature(render_api.pts2render).parameters["with_depth_alpha"].default is False
     assert list(inspect.signature(render_api.render_ex).parameters)[:8] == ["data", "idx", "pts_xyz", "pts_rgb", "rotations", "scales", "opacity", "bg_color"]
-    rs = RZ.GaussianRasterizationSettings(8, 8, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3, torch.zeros(3), False, False)
-    x = torch.zeros(4, 3)
+    rs, kw = capi_run.cpu_view()
     with pytest.raises(RuntimeError, match="must live on a GPU"):
-        RZ.GaussianRasterizer(rs)(means3D=x, means2D=x, opacities=torch.ones(4, 1), colors_precomp=x, scales=x, rotations=torch.zeros(4, 4),
-                                  return_depth_alpha=True)
+        RZ.GaussianRasterizer(rs)(**kw, return_depth_alpha=True)

@@ -4,43 +4,38 @@ before it, the workspace asked for is the depth / alpha one (no new tail, no new
 keywords are opt-in, come last and refuse bad input before anything is launched."""
 import ctypes as C
 import inspect
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
+
+import capi_run
+from capi_run import D, call, need, spec
+
+FWD, BWD = "gsr_forward_distort", "gsr_backward_distort"
 
 
 def test_distort_struct_layout_is_mirrored(tmp_path):
     """The C compiler's offsets of GsrDistort equal the ctypes ones; the map pointers share their slot; GsrViewExt is still 80 bytes."""
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpsgs.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", '
-                   "sizeof(GsrDistort), offsetof(GsrDistort, out_distort), offsetof(GsrDistort, dL_ddistort), offsetof(GsrDistort, totals), "
-                   "offsetof(GsrDistort, reserved), sizeof(GsrViewExt)); return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
-    D = _capi.GsrDistort
-    assert got == [C.sizeof(D), D._map.offset + _capi._DistortSlot.out_distort.offset, D._map.offset + _capi._DistortSlot.dL_ddistort.offset,
-                   D.totals.offset, D.reserved.offset, C.sizeof(_capi.GsrViewExt)]
+    got = capi_run.c_values(tmp_path, ["sizeof(GsrDistort)", "offsetof(GsrDistort, out_distort)", "offsetof(GsrDistort, dL_ddistort)",
+                                       "offsetof(GsrDistort, totals)", "offsetof(GsrDistort, reserved)", "sizeof(GsrViewExt)"])
+    Ds = _capi.GsrDistort
+    assert got == [C.sizeof(Ds), Ds._map.offset + _capi._DistortSlot.out_distort.offset, Ds._map.offset + _capi._DistortSlot.dL_ddistort.offset,
+                   Ds.totals.offset, Ds.reserved.offset, C.sizeof(_capi.GsrViewExt)]
     assert got == [32, 0, 0, 8, 16, 80]
-    d = D()
+    d = Ds()
     assert d.out_distort is None and d.dL_ddistort is None and d.totals is None and list(d.reserved) == [None, None]  # zero-initialised = nothing wanted
     d.out_distort = 0x1000
     assert d.dL_ddistort == 0x1000  # one slot
 
 
 def test_abi_version_and_symbols():
-    lib = _capi.lib()
+    lib = capi_run.lib()
     assert lib.gpsgs_abi_version() == 4
-    hdr = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
+    hdr = capi_run.header()
     assert re.search(r"#define GPSGS_ABI_VERSION 4\b", hdr)
-    for name in ("gsr_forward_distort", "gsr_backward_distort"):
+    for name in (FWD, BWD):
         assert name in _capi.SYMBOLS
         assert hasattr(lib, name)
         assert re.search(r"\bint %s\(" % name, hdr)
@@ -53,76 +48,54 @@ def test_abi_version_and_symbols():
 
 
 def test_default_workspace_sizes_are_pinned():
-    """The layout did not move: the constants tests/test_capi_absgrad.py pins, and the tails behind the depth / alpha size."""
-    lib = _capi.lib()
-    assert lib.gsr_workspace_bytes(30000, 256, 256, 1 << 20) == 54450688
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 0) == 454462464
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 1) == 258065920
-    da = lib.gsr_workspace_bytes_depth_alpha(600000, 1024, 1024, 5 << 20, 1024, 0)
-    assert da == lib.gsr_workspace_bytes_features(600000, 1024, 1024, 5 << 20, 1024, 1, 0) - (5 << 20) * 4
-    assert da == lib.gsr_workspace_bytes_contrib(600000, 1024, 1024, 5 << 20, 1024, 0) - (5 << 20) * 16
-    assert da == lib.gsr_workspace_bytes_absgrad(600000, 1024, 1024, 5 << 20, 1024) - (5 << 20) * 8
+    """The layout did not move: the constants and the tails behind the depth / alpha size."""
+    capi_run.assert_default_sizes(capi_run.lib())
 
 
-# P = 1, an 8 x 8 image, every pointer set (never dereferenced: each call returns before anything is launched) and a workspace of 0 bytes: a VALID
-# GsrDistort gets as far as the workspace check (GPSGS_E_WORKSPACE), so GPSGS_E_INVALID can only come from its validation
-_D = 0x1000  # a 4-byte aligned dummy device address
+# spec(FWD) / spec(BWD): P = 1, an 8 x 8 image, every pointer set (never dereferenced: each call returns before anything is launched) and a workspace
+# of 0 bytes: a VALID GsrDistort gets as far as the workspace check (GPSGS_E_WORKSPACE), so GPSGS_E_INVALID can only come from its validation
+def _distort(lib, entry, ws=0, **opt):
+    """`map`: the entry point's own name of the shared slot, out_distort (forward) / dL_ddistort (backward)."""
+    if "map" in opt:
+        opt["out_distort" if entry == FWD else "dL_ddistort"] = opt.pop("map")
+    return call(lib, entry, spec(entry, ws=ws, opt=opt))
 
 
-def _fwd_args(ws_bytes=0):
-    # P W H | means3D colors opacities scales rotations | modifier tanfovx tanfovy | view proj bg out_color radii | workspace, bytes, capacity, flags,
-    # stream | host header, sequence | ext
-    return [1, 8, 8] + [_D] * 5 + [1.0, 0.5, 0.5] + [_D] * 5 + [_D, ws_bytes, 1024, 0, None] + [None, 0] + [None]
-
-
-def _bwd_args(ws_bytes=0):
-    # P W H | means3D colors opacities scales rotations | modifier tanfovx tanfovy | view proj bg radii dL_dpix | six gradient arrays | workspace,
-    # bytes, capacity, flags, stream, ext | three camera gradients, scratch, scratch bytes
-    return [1, 8, 8] + [_D] * 5 + [1.0, 0.5, 0.5] + [_D] * 5 + [_D] * 6 + [_D, ws_bytes, 1024, 0, None, None] + [None, None, None, None, 0]
-
-
-def _dis(p=_D, totals=_D + 0x1000, r0=None, r1=None):
-    d = _capi.GsrDistort()
-    d.out_distort, d.totals = p, totals
-    d.reserved[0], d.reserved[1] = r0, r1
-    return d
-
-
-_BAD = [dict(p=_D + 2), dict(p=_D + 1), dict(totals=_D + 0x1002), dict(totals=None), dict(r0=_D), dict(r1=_D), dict(p=None, r0=_D), dict(p=None, totals=_D + 1)]
+_BAD = [dict(map=D + 2), dict(map=D + 1), dict(totals=D + 0x1002), dict(totals=None), dict(reserved=(D, None)), dict(reserved=(None, D)),
+        dict(map=None, reserved=(D, None)), dict(map=None, totals=D + 1)]
 
 
 @pytest.mark.parametrize("bad", _BAD)
 def test_forward_validates_before_launch(bad):
-    lib = _capi.lib()
-    assert len(_fwd_args()) == len(lib.gsr_forward_ex.argtypes)
-    assert lib.gsr_forward_distort(*_fwd_args(), C.byref(_dis())) == _capi.GPSGS_E_WORKSPACE  # the valid control
-    assert lib.gsr_forward_distort(*_fwd_args(), C.byref(_dis(**bad))) == _capi.GPSGS_E_INVALID
+    lib = capi_run.lib()
+    assert _distort(lib, FWD) == _capi.GPSGS_E_WORKSPACE  # the valid control
+    assert _distort(lib, FWD, **bad) == _capi.GPSGS_E_INVALID
 
 
 @pytest.mark.parametrize("bad", _BAD)
 def test_backward_validates_before_launch(bad):
-    lib = _capi.lib()
-    assert len(_bwd_args()) == len(lib.gsr_backward_camera.argtypes)
-    assert lib.gsr_backward_distort(*_bwd_args(), C.byref(_dis())) == _capi.GPSGS_E_WORKSPACE  # the valid control
-    assert lib.gsr_backward_distort(*_bwd_args(), C.byref(_dis(**bad))) == _capi.GPSGS_E_INVALID
+    lib = capi_run.lib()
+    assert _distort(lib, BWD) == _capi.GPSGS_E_WORKSPACE  # the valid control
+    assert _distort(lib, BWD, **bad) == _capi.GPSGS_E_INVALID
 
 
 def test_the_depth_alpha_workspace_is_required():
     """With the map's gradient wanted the backward needs gsr_workspace_bytes_depth_alpha(..., 0) -- the plain size is too small, and so is one byte
     less; the forward needs the forward-only size; a NULL struct or a NULL map pointer asks for nothing more than the call without the option."""
-    lib = _capi.lib()
+    lib = capi_run.lib()
     dims = (1, 8, 8, 1024, 0)
     da, plain = lib.gsr_workspace_bytes_depth_alpha(*dims, 0), lib.gsr_workspace_bytes_ex(*dims, 0)
-    assert da > plain
+    assert da > plain and need(lib, BWD, spec(BWD)) == da
     for nbytes in (plain, da - 1):
-        assert lib.gsr_backward_distort(*_bwd_args(nbytes), C.byref(_dis())) == _capi.GPSGS_E_WORKSPACE
-    for d in (None, C.byref(_dis(p=None)), C.byref(_dis(p=None, totals=None))):
-        assert lib.gsr_backward_distort(*_bwd_args(plain - 1), d) == _capi.GPSGS_E_WORKSPACE
-        assert lib.gsr_backward_camera(*_bwd_args(plain - 1)) == _capi.GPSGS_E_WORKSPACE
+        assert _distort(lib, BWD, nbytes) == _capi.GPSGS_E_WORKSPACE
+    for opt in (None, dict(dL_ddistort=None), dict(dL_ddistort=None, totals=None)):
+        assert need(lib, BWD, spec(BWD, opt=opt)) == plain
+        assert call(lib, BWD, spec(BWD, ws=plain - 1, opt=opt)) == _capi.GPSGS_E_WORKSPACE
+        assert call(lib, "gsr_backward_camera", spec("gsr_backward_camera", ws=plain - 1)) == _capi.GPSGS_E_WORKSPACE
     fwd = lib.gsr_workspace_bytes_depth_alpha(*dims, 1)
-    assert fwd == lib.gsr_workspace_bytes_ex(*dims, 1)
-    assert lib.gsr_forward_distort(*_fwd_args(fwd - 1), C.byref(_dis())) == _capi.GPSGS_E_WORKSPACE
-    assert lib.gsr_forward_ex(*_fwd_args(fwd - 1)) == _capi.GPSGS_E_WORKSPACE
+    assert fwd == lib.gsr_workspace_bytes_ex(*dims, 1) == need(lib, FWD, spec(FWD))
+    assert _distort(lib, FWD, fwd - 1) == _capi.GPSGS_E_WORKSPACE
+    assert call(lib, "gsr_forward_ex", spec("gsr_forward_ex", ws=fwd - 1)) == _capi.GPSGS_E_WORKSPACE
 
 
 def test_python_api_is_opt_in():
@@ -139,9 +112,7 @@ def test_python_api_is_opt_in():
     assert list(inspect.signature(render_api.pts2render).parameters)[:2] == ["data", "bg_color"]
     assert RZ._ViewOptions._fields[-1] == "distortion" and RZ._DEFAULT_OPTIONS.distortion is False
     assert RZ._Outputs._fields[-1] == "distortion"
-    rs = RZ.GaussianRasterizationSettings(8, 8, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3, torch.zeros(3), False, False)
-    x = torch.zeros(4, 3)
-    kw = dict(means3D=x, means2D=x, opacities=torch.ones(4, 1), colors_precomp=x, scales=x, rotations=torch.zeros(4, 4))
+    rs, kw = capi_run.cpu_view()
     with pytest.raises(RuntimeError, match="must live on a GPU"):
         RZ.GaussianRasterizer(rs)(**kw, return_distortion=True)
     with pytest.raises(RuntimeError, match="return_distortion cannot be combined with features"):

@@ -3,29 +3,22 @@ are exported and mirrored at ABI 4, the feature workspace is the depth / alpha o
 move, and the Python keyword is opt-in and refuses bad input before anything is launched."""
 import ctypes as C
 import inspect
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
+
+import capi_run
+from capi_run import D, call, spec
 
 
 def test_features_struct_layout_is_mirrored(tmp_path):
     """The C compiler's offsets of GsrFeatures equal the ctypes ones; the forward output and the backward map gradient share their slot;
     GsrViewExt is still 80 bytes."""
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpsgs.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %d\\n", '
-                   "sizeof(GsrFeatures), offsetof(GsrFeatures, channels), offsetof(GsrFeatures, reserved0), offsetof(GsrFeatures, features), "
-                   "offsetof(GsrFeatures, out_features), offsetof(GsrFeatures, dL_dfeaturemap), offsetof(GsrFeatures, dL_dfeatures), sizeof(GsrViewExt), "
-                   "GSR_MAX_FEATURES); return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    got = capi_run.c_values(tmp_path, ["sizeof(GsrFeatures)", "offsetof(GsrFeatures, channels)", "offsetof(GsrFeatures, reserved0)",
+                                       "offsetof(GsrFeatures, features)", "offsetof(GsrFeatures, out_features)", "offsetof(GsrFeatures, dL_dfeaturemap)",
+                                       "offsetof(GsrFeatures, dL_dfeatures)", "sizeof(GsrViewExt)", "GSR_MAX_FEATURES"])
     Fs = _capi.GsrFeatures
     assert got == [C.sizeof(Fs), Fs.channels.offset, Fs.reserved0.offset, Fs.features.offset, Fs._map.offset, Fs._map.offset,
                    Fs.dL_dfeatures.offset, C.sizeof(_capi.GsrViewExt), _capi.GSR_MAX_FEATURES]
@@ -37,9 +30,9 @@ def test_features_struct_layout_is_mirrored(tmp_path):
 
 
 def test_abi_version_and_symbols():
-    lib = _capi.lib()
+    lib = capi_run.lib()
     assert lib.gpsgs_abi_version() == 4
-    hdr = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
+    hdr = capi_run.header()
     for name in ("gsr_workspace_bytes_features", "gsr_forward_features", "gsr_backward_features"):
         assert name in _capi.SYMBOLS
         assert hasattr(lib, name)
@@ -55,7 +48,7 @@ def test_abi_version_and_symbols():
 @pytest.mark.parametrize("P,W,H,cap,bcap", [(30000, 256, 256, 1 << 20, 0), (600000, 1024, 1024, 5 << 20, 1024), (1, 8, 8, 1, 0), (0, 17, 9, 0, 0)])
 @pytest.mark.parametrize("F", [1, 3, 17, 64])
 def test_workspace_sizes(P, W, H, cap, bcap, F):
-    lib = _capi.lib()
+    lib = capi_run.lib()
     da = lib.gsr_workspace_bytes_depth_alpha(P, W, H, cap, bcap, 0)
     feat = lib.gsr_workspace_bytes_features(P, W, H, cap, bcap, F, 0)
     assert feat >= da > 0
@@ -67,62 +60,50 @@ def test_workspace_sizes(P, W, H, cap, bcap, F):
 
 @pytest.mark.parametrize("F", [0, -1, 65, 1000])
 def test_workspace_size_rejects_channel_counts(F):
-    lib = _capi.lib()
+    lib = capi_run.lib()
     assert lib.gsr_workspace_bytes_features(30000, 256, 256, 1 << 20, 0, F, 0) == 0
     assert lib.gsr_workspace_bytes_features(30000, 256, 256, 1 << 20, 0, F, 1) == 0
 
 
 def test_default_workspace_sizes_are_pinned():
     """The default layout did not move (the parent commit's sizes, byte for byte)."""
-    lib = _capi.lib()
-    assert lib.gsr_workspace_bytes(30000, 256, 256, 1 << 20) == 54450688
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 0) == 454462464
-    assert lib.gsr_workspace_bytes_ex(600000, 1024, 1024, 5 << 20, 1024, 1) == 258065920
+    capi_run.assert_default_sizes(capi_run.lib())
 
 
-# P = 1, an 8 x 8 image, every pointer set (never dereferenced: each call returns before anything is launched) and a workspace of 0 bytes: a
-# VALID feature set gets as far as the workspace check (GPSGS_E_WORKSPACE), so GPSGS_E_INVALID can only come from the feature validation
-_D = 0x1000  # a 4-byte aligned dummy device address
+# spec("gsr_forward_features") / spec("gsr_backward_features"): P = 1, an 8 x 8 image, every pointer set (never dereferenced: each call returns
+# before anything is launched) and a workspace of 0 bytes: a VALID feature set of three channels gets as far as the workspace check
+# (GPSGS_E_WORKSPACE), so GPSGS_E_INVALID can only come from the feature validation
+def _features(lib, entry, ws=0, **opt):
+    """`map`: the entry point's own name of the shared slot, out_features (forward) / dL_dfeaturemap (backward)."""
+    if "map" in opt:
+        opt["out_features" if entry == "gsr_forward_features" else "dL_dfeaturemap"] = opt.pop("map")
+    return call(lib, entry, spec(entry, ws=ws, opt=opt))
 
 
-def _fwd_args(ws_bytes=0):
-    return [1, 8, 8] + [_D] * 5 + [1.0, 0.5, 0.5] + [_D] * 6 + [ws_bytes, 1024, 0, None, None, 0, None]
-
-
-def _bwd_args(ws_bytes=0):
-    return ([1, 8, 8] + [_D] * 5 + [1.0, 0.5, 0.5] + [_D] * 12 + [ws_bytes, 1024, 0, None, None] + [None, None, None, None, 0])
-
-
-def _feat(ch, features=_D, out=_D, dfeat=_D):
-    f = _capi.GsrFeatures()
-    f.channels, f.features, f.out_features, f.dL_dfeatures = ch, features, out, dfeat
-    return f
-
-
-@pytest.mark.parametrize("bad", [dict(ch=65), dict(ch=-1), dict(ch=3, features=None), dict(ch=3, features=_D + 2), dict(ch=3, out=_D + 1)])
+@pytest.mark.parametrize("bad", [dict(channels=65), dict(channels=-1), dict(features=None), dict(features=D + 2), dict(map=D + 1)])
 def test_forward_validates_before_launch(bad):
-    lib = _capi.lib()
-    assert lib.gsr_forward_features(*_fwd_args(), C.byref(_feat(3))) == _capi.GPSGS_E_WORKSPACE  # the valid control
-    assert lib.gsr_forward_features(*_fwd_args(), C.byref(_feat(**bad))) == _capi.GPSGS_E_INVALID
+    lib = capi_run.lib()
+    assert _features(lib, "gsr_forward_features") == _capi.GPSGS_E_WORKSPACE  # the valid control
+    assert _features(lib, "gsr_forward_features", **bad) == _capi.GPSGS_E_INVALID
 
 
-@pytest.mark.parametrize("bad", [dict(ch=65), dict(ch=-1), dict(ch=3, features=None), dict(ch=3, features=_D + 2), dict(ch=3, out=_D + 1),
-                                 dict(ch=3, dfeat=_D + 3)])
+@pytest.mark.parametrize("bad", [dict(channels=65), dict(channels=-1), dict(features=None), dict(features=D + 2), dict(map=D + 1),
+                                 dict(dL_dfeatures=D + 3)])
 def test_backward_validates_before_launch(bad):
-    lib = _capi.lib()
-    assert lib.gsr_backward_features(*_bwd_args(), C.byref(_feat(3))) == _capi.GPSGS_E_WORKSPACE
-    assert lib.gsr_backward_features(*_bwd_args(), C.byref(_feat(**bad))) == _capi.GPSGS_E_INVALID
+    lib = capi_run.lib()
+    assert _features(lib, "gsr_backward_features") == _capi.GPSGS_E_WORKSPACE
+    assert _features(lib, "gsr_backward_features", **bad) == _capi.GPSGS_E_INVALID
 
 
 def test_backward_needs_the_feature_tail():
     """With both feature gradients wanted, a workspace of the depth / alpha size (no feature tail) is too small; one byte short of the feature size
     is too small too."""
-    lib = _capi.lib()
+    lib = capi_run.lib()
     da = lib.gsr_workspace_bytes_depth_alpha(1, 8, 8, 1024, 0, 0)
     full = lib.gsr_workspace_bytes_features(1, 8, 8, 1024, 0, 3, 0)
     assert full > da
     for nbytes in (da, full - 1):
-        assert lib.gsr_backward_features(*_bwd_args(nbytes), C.byref(_feat(3))) == _capi.GPSGS_E_WORKSPACE
+        assert _features(lib, "gsr_backward_features", nbytes) == _capi.GPSGS_E_WORKSPACE
 
 
 def test_python_api_is_opt_in():
@@ -134,11 +115,9 @@ def test_python_api_is_opt_in():
     assert inspect.signature(RZ.GaussianRasterizer.forward).parameters["features"].default is None
     assert inspect.signature(render_api.render_ex).parameters["features"].default is None
     assert list(inspect.signature(render_api.render_ex).parameters)[:8] == ["data", "idx", "pts_xyz", "pts_rgb", "rotations", "scales", "opacity", "bg_color"]
-    rs = RZ.GaussianRasterizationSettings(8, 8, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3, torch.zeros(3), False, False)
-    x = torch.zeros(4, 3)
+    rs, kw = capi_run.cpu_view()
     with pytest.raises(RuntimeError, match="must live on a GPU"):
-        RZ.GaussianRasterizer(rs)(means3D=x, means2D=x, opacities=torch.ones(4, 1), colors_precomp=x, scales=x, rotations=torch.zeros(4, 4),
-                                  features=torch.zeros(4, 5))
+        RZ.GaussianRasterizer(rs)(**kw, features=torch.zeros(4, 5))
     dev = torch.device("cpu")
     with pytest.raises(RuntimeError, match=r"\(num_points, F\)"):
         RZ._features(torch.zeros(4, 65), 4, dev)

@@ -1,32 +1,15 @@
 """CPU: the GroupNorm entry points of the C-ABI (include/gpsgs.h, last section) -- declared, exported, bound; the scratch formula the header states;
 every bad-argument case refused before any HIP call (this machine has no GPU: a call that reached HIP would not return GPSGS_E_INVALID)."""
-import ctypes as C
-import os
-import re
-
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
 
-
-def _lib():
-    gps_gaussian_amd.build()
-    return _capi.lib()
+import capi_run
+from capi_run import D
 
 
 def test_symbols_are_declared_exported_and_bound():
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(?:int|size_t)\s+(gn_[a-z0-9_]+)\s*\(", code)))
-    assert declared == sorted(_capi.GN_SYMBOLS) == ["gn_backward", "gn_chunk_elems", "gn_forward", "gn_scratch_bytes"]
-    assert "gn_forward / gn_backward" in src.split("#ifndef GPSGS_H")[0]          # the list at the top of the header names them
-    lib = _lib()
-    raw = C.CDLL(_capi.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+    lib = capi_run.check_section("gn_", _capi.GN_SYMBOLS, ["gn_backward", "gn_chunk_elems", "gn_forward", "gn_scratch_bytes"])
     assert len(lib.gn_forward.argtypes) == 14 and len(lib.gn_backward.argtypes) == 15
 
 
@@ -36,7 +19,7 @@ def _formula(K, N, Cn, G, HW):
 
 
 def test_chunk_and_the_scratch_formula():
-    lib = _lib()
+    lib = capi_run.lib()
     K = lib.gn_chunk_elems()
     assert K > 0 and K % 8 == 0      # a chunk is whole 16-byte vectors of either dtype
     cdiv = lambda a, b: -(-a // b)
@@ -61,40 +44,38 @@ def test_chunk_and_the_scratch_formula():
     assert lib.gn_scratch_bytes(0, 8, 2, 16) == 0
 
 
-P = 0x10000   # a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
-
-
-def _fwd(lib, x=P, dtype=0, gamma=P, beta=P, N=2, Cn=8, G=2, HW=16, y=P, mean=P, rstd=P, scratch=P):
+# D: a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
+def _fwd(lib, x=D, dtype=0, gamma=D, beta=D, N=2, Cn=8, G=2, HW=16, y=D, mean=D, rstd=D, scratch=D):
     return lib.gn_forward(x, dtype, gamma, beta, N, Cn, G, HW, 1e-5, y, mean, rstd, scratch, None)
 
 
-def _bwd(lib, x=P, dtype=0, dy=P, gamma=P, mean=P, rstd=P, N=2, Cn=8, G=2, HW=16, dx=P, dgamma=P, dbeta=P, scratch=P):
+def _bwd(lib, x=D, dtype=0, dy=D, gamma=D, mean=D, rstd=D, N=2, Cn=8, G=2, HW=16, dx=D, dgamma=D, dbeta=D, scratch=D):
     return lib.gn_backward(x, dtype, dy, gamma, mean, rstd, N, Cn, G, HW, dx, dgamma, dbeta, scratch, None)
 
 
 @pytest.mark.parametrize("call", [_fwd, _bwd], ids=["forward", "backward"])
 def test_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     E = _capi.GPSGS_E_INVALID
     assert call(lib, G=0) == E and call(lib, G=-2) == E
     assert call(lib, G=3) == E                       # 8 % 3
     assert call(lib, dtype=2) == E and call(lib, dtype=-1) == E
     assert call(lib, N=-1) == E and call(lib, Cn=-8) == E and call(lib, HW=-1) == E
     assert call(lib, x=None) == E and call(lib, gamma=None) == E and call(lib, scratch=None) == E
-    assert call(lib, x=P + 4) == E                   # not 16-byte aligned
+    assert call(lib, x=D + 4) == E                   # not 16-byte aligned
     assert call(lib, Cn=2, G=1, HW=2 ** 30) == E     # a row of 2^31 elements
     if call is _fwd:
         assert call(lib, beta=None) == E and call(lib, y=None) == E and call(lib, mean=None) == E and call(lib, rstd=None) == E
-        assert call(lib, y=P + 8) == E
+        assert call(lib, y=D + 8) == E
     else:
         assert call(lib, dy=None) == E and call(lib, mean=None) == E and call(lib, rstd=None) == E
         assert call(lib, dgamma=None) == E and call(lib, dbeta=None) == E      # one without the other
         assert call(lib, dgamma=None, N=0) == E                               # ... even for an empty tensor
-        assert call(lib, dy=P + 4) == E and call(lib, dx=P + 8) == E
+        assert call(lib, dy=D + 4) == E and call(lib, dx=D + 8) == E
 
 
 def test_empty_tensors_return_ok_and_launch_nothing():
-    lib = _lib()
+    lib = capi_run.lib()
     for kw in (dict(N=0), dict(Cn=0), dict(HW=0)):
         assert _fwd(lib, **kw) == 0 and _bwd(lib, **kw) == 0
         assert _fwd(lib, x=None, y=None, scratch=None, **kw) == 0              # torch hands out NULL for an empty tensor

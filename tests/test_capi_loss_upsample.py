@@ -4,37 +4,34 @@ tensors return without a launch, and sizes a launch cannot hold -- more planes o
 block count beyond 0x7fffffff -- are refused instead of truncated."""
 import pytest
 
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
 
-P = 0x10000   # a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
+import capi_run
+from capi_run import D
+
+# D: a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
 E = _capi.GPSGS_E_INVALID
 OK = 0
 
 
-def _lib():
-    gps_gaussian_amd.build()
-    return _capi.lib()
-
-
-def _lfwd(lib, pred=P, gt=P, planes=6, H=20, W=45, m1=P, m2=P, m3=P, scratch=P, out2=P):
+def _lfwd(lib, pred=D, gt=D, planes=6, H=20, W=45, m1=D, m2=D, m3=D, scratch=D, out2=D):
     return lib.fl_l1_ssim_forward(pred, gt, planes, H, W, m1, m2, m3, scratch, out2, None)
 
 
-def _lbwd(lib, pred=P, gt=P, m1=P, m2=P, m3=P, planes=6, H=20, W=45, gout=P, d_pred=P):
+def _lbwd(lib, pred=D, gt=D, m1=D, m2=D, m3=D, planes=6, H=20, W=45, gout=D, d_pred=D):
     return lib.fl_l1_ssim_backward(pred, gt, m1, m2, m3, planes, H, W, gout, d_pred, None)
 
 
-def _ufwd(lib, flow=P, mask=P, out=P, N=2, C=2, H=3, W=65, f=4):
+def _ufwd(lib, flow=D, mask=D, out=D, N=2, C=2, H=3, W=65, f=4):
     return lib.cu_upsample_forward(flow, mask, out, N, C, H, W, f, None)
 
 
-def _ubwd(lib, flow=P, mask=P, gout=P, gflow=P, gmask=P, scratch=P, N=2, C=2, H=3, W=65, f=4):
+def _ubwd(lib, flow=D, mask=D, gout=D, gflow=D, gmask=D, scratch=D, N=2, C=2, H=3, W=65, f=4):
     return lib.cu_upsample_backward(flow, mask, gout, gflow, gmask, scratch, N, C, H, W, f, None)
 
 
 def test_loss_scratch_bytes():
-    lib = _lib()
+    lib = capi_run.lib()
     for planes, H, W in [(1, 1, 1), (6, 20, 45), (3, 32, 32), (3, 33, 32), (3, 32, 33), (2, 2048, 2048), (65535, 33, 71)]:
         tiles = planes * (-(-H // 32)) * (-(-W // 32))
         assert lib.fl_scratch_bytes(planes, H, W) == 8 * tiles + 16, (planes, H, W)
@@ -45,7 +42,7 @@ def test_loss_scratch_bytes():
 
 @pytest.mark.parametrize("call", [_lfwd, _lbwd], ids=["forward", "backward"])
 def test_loss_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, planes=-1) == E and call(lib, H=-1) == E and call(lib, W=-20) == E
     assert call(lib, pred=None) == E and call(lib, gt=None) == E
     if call is _lfwd:
@@ -65,7 +62,7 @@ def test_loss_bad_arguments_are_refused_before_hip(call):
 
 @pytest.mark.parametrize("call", [_lfwd, _lbwd], ids=["forward", "backward"])
 def test_loss_sizes_the_grid_cannot_hold_are_refused(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, planes=65536, H=1, W=1) == E                    # grid z
     assert call(lib, planes=1, H=65535 * 32 + 1, W=1) == E           # grid y: 65536 row tiles
     assert call(lib, planes=65535, H=65535 * 32, W=32) == E          # 65535 x 65535 x 1 tiles: more than an int counts
@@ -76,7 +73,7 @@ def test_loss_sizes_the_grid_cannot_hold_are_refused(call):
 
 @pytest.mark.parametrize("call", [_ufwd, _ubwd], ids=["forward", "backward"])
 def test_upsample_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     assert call(lib, N=-1) == E and call(lib, H=-3) == E and call(lib, W=-65) == E
     assert call(lib, C=0) == E and call(lib, C=-1) == E and call(lib, C=5) == E
     assert call(lib, f=0) == E and call(lib, f=-4) == E and call(lib, f=17) == E
@@ -97,7 +94,7 @@ def test_upsample_bad_arguments_are_refused_before_hip(call):
 
 
 def test_upsample_scratch_bytes():
-    lib = _lib()
+    lib = capi_run.lib()
     assert lib.cu_upsample_scratch_bytes(2, 2, 3, 65) == 2 * 9 * 2 * 3 * 65 * 4
     assert lib.cu_upsample_scratch_bytes(1, 1, 1, 1) == 36
     for bad in ((0, 2, 3, 65), (2, 0, 3, 65), (2, 2, 0, 65), (2, 2, 3, 0), (-2, 2, 3, 65), (2, -2, 3, 65), (2, 2, -3, 65), (2, 2, 3, -65)):
@@ -106,7 +103,7 @@ def test_upsample_scratch_bytes():
 
 def test_upsample_block_counts_beyond_a_grid_are_refused():
     """One thread per output pixel (forward) resp. per flow element (k_up_bwd_flow) in blocks of 256: the count used to be cast to unsigned."""
-    lib = _lib()
+    lib = capi_run.lib()
     # forward: N f H f W = 2^39 + 2^31 pixels -> 2^31 + 2^23 blocks (the cast kept 2^23 of them)
     assert _ufwd(lib, N=2 ** 15 + 2 ** 7, H=2 ** 10, W=2 ** 6, f=16) == E
     assert _ufwd(lib, N=1, H=2 ** 30, W=2 ** 9, f=1) == E             # exactly 2^31 blocks (the cast kept none)

@@ -9,87 +9,25 @@ and pairs of faults that pin which check comes first.  (The exported entry point
 of two tails in one call cannot be reached from here; the pairs with a workspace sized for ANOTHER option's tail stand in for it.)
 
 Re-record (only when a return code changes on purpose):  GPSGS_LIB=<library to record> python tests/test_capi_return_codes.py"""
-import ctypes as C
 import json
 import os
 
 from conftest import ROOT
 
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi
 
+# the by-name call builder, under the names the case generator below was written with
+from capi_run import BWD_PTRS, CAM_PTRS, FWD_PTRS, VIEW_PTRS, D as _D, call as _call, has_cam as _has_cam, has_ext as _has_ext, need as _need, spec as _spec
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "capi_return_codes.json")
-_D = 0x1000  # a 16-byte aligned dummy device address
 FORWARDS = ("gsr_forward", "gsr_forward_notify", "gsr_forward_ex", "gsr_forward_features", "gsr_forward_contrib")
 BACKWARDS = ("gsr_backward", "gsr_backward_ex", "gsr_backward_camera", "gsr_backward_features", "gsr_backward_absgrad")
-VIEW_PTRS = ("means3D", "colors", "opacities", "scales", "rotations", "viewmatrix", "projmatrix", "bg", "workspace")
-FWD_PTRS = ("out_color", "radii")
-BWD_PTRS = ("radii", "dL_dpix", "dL_dmeans3D", "dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dscales", "dL_drotations")
-CAM_PTRS = ("dL_dviewmatrix", "dL_dprojmatrix", "dL_dcampos", "scratch")
 EXT_PTRS = ("row_range", "shs", "campos", "cov3D_precomp", "dL_dsh", "dL_dcov3D", "out_depth", "out_alpha")  # (the map slots: dL_ddepth / dL_dalpha in a backward)
 OPT_PTRS = {"gsr_forward_features": ("features", "out_features"), "gsr_backward_features": ("features", "dL_dfeaturemap", "dL_dfeatures"),
             "gsr_forward_contrib": ("weight_sum", "weight_max", "pixel_count"), "gsr_backward_absgrad": ("absgrad",)}
 BAD_OPT = {"gsr_forward_features": dict(channels=65), "gsr_backward_features": dict(channels=65), "gsr_forward_contrib": dict(reserved=_D),
            "gsr_backward_absgrad": dict(reserved=_D)}  # an invalid option struct per entry point that takes one
 W_MAX = 65535 * 16
-
-
-def _has_ext(entry):
-    return entry not in ("gsr_forward", "gsr_forward_notify", "gsr_backward")
-
-
-def _has_cam(entry):
-    return entry in ("gsr_backward_camera", "gsr_backward_features", "gsr_backward_absgrad")
-
-
-def _spec(entry, **over):
-    """A valid call of `entry` with its own option switched on and a workspace of 0 bytes; `over` replaces fields (ext / opt / cam: merged)."""
-    s = dict(P=1, W=8, H=8, cap=1024, flags=0, ws=0, ext={}, cam={}, **{k: _D for k in VIEW_PTRS + (FWD_PTRS if entry in FORWARDS else BWD_PTRS)})
-    s["opt"] = {"gsr_forward_features": dict(channels=3, features=_D, out_features=_D), "gsr_forward_contrib": dict(weight_sum=_D, weight_max=_D, pixel_count=_D),
-                "gsr_backward_features": dict(channels=3, features=_D, dL_dfeaturemap=_D, dL_dfeatures=_D), "gsr_backward_absgrad": dict(absgrad=_D)}.get(entry, {})
-    for k, v in over.items():
-        if k in ("ext", "opt", "cam"):
-            s[k] = None if v is None else dict(s[k], **v)
-        else:
-            s[k] = v
-    return s
-
-
-def _struct(cls, fields):
-    if fields is None:
-        return None
-    x = cls()
-    for k, v in fields.items():
-        setattr(x, k, v)
-    return C.byref(x)
-
-
-def _call(lib, entry, s):
-    a = [s["P"], s["W"], s["H"]] + [s[k] for k in VIEW_PTRS[:5]] + [1.0, 0.5, 0.5] + [s[k] for k in VIEW_PTRS[5:8]]
-    a += [s[k] for k in (FWD_PTRS if entry in FORWARDS else BWD_PTRS)] + [s["workspace"], s["ws"], s["cap"], s["flags"], None]
-    if entry in FORWARDS and entry != "gsr_forward":
-        a += [None, 0]  # no host header
-    if _has_ext(entry):
-        a.append(_struct(_capi.GsrViewExt, s["ext"] or None))
-    if _has_cam(entry):
-        a += [s["cam"].get(k) for k in CAM_PTRS] + [s["cam"].get("scratch_bytes", 0)]
-    if entry in OPT_PTRS:
-        a.append(_struct({"features": _capi.GsrFeatures, "contrib": _capi.GsrContrib, "absgrad": _capi.GsrAbsGrad}[entry.rsplit("_", 1)[1]], s["opt"]))
-    return getattr(lib, entry)(*a)
-
-
-def _need(lib, entry, s):
-    """What the matching workspace query reports for the call `s` of `entry`."""
-    g = (s["P"], s["W"], s["H"], s["cap"], (s["ext"] or {}).get("bin_capacity", 0))
-    if entry in FORWARDS:
-        return lib.gsr_workspace_bytes_contrib(*g, 1) if entry == "gsr_forward_contrib" and s["opt"] else lib.gsr_workspace_bytes_ex(*g, 1)
-    if entry == "gsr_backward_absgrad" and s["opt"] and s["opt"].get("absgrad"):
-        return lib.gsr_workspace_bytes_absgrad(*g)
-    if entry == "gsr_backward_features" and s["opt"] and s["opt"].get("dL_dfeaturemap") and s["opt"].get("dL_dfeatures") and 1 <= s["opt"]["channels"] <= 64:
-        return lib.gsr_workspace_bytes_features(*g, s["opt"]["channels"], 0)
-    if (s["ext"] or {}).get("out_depth") or (s["ext"] or {}).get("out_alpha"):
-        return lib.gsr_workspace_bytes_depth_alpha(*g, 0)
-    return lib.gsr_workspace_bytes_ex(*g, 0)
 
 
 def _cases(lib):

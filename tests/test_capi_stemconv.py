@@ -1,40 +1,22 @@
 """CPU: the stem-convolution entry points of the C-ABI (include/gpsgs.h, last section) -- declared, exported, bound; the configurations sc_supported
 takes; the scratch formula the header states; every bad-argument case refused before any HIP call (this machine has no GPU: a call that reached HIP
 would not return GPSGS_E_INVALID)."""
-import ctypes as C
-import os
-import re
-
 import pytest
 
-from conftest import ROOT
-
-import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi, _ops
 
-
-def _lib():
-    gps_gaussian_amd.build()
-    return _capi.lib()
+import capi_run
+from capi_run import D
 
 
 def test_symbols_are_declared_exported_and_bound():
-    src = open(os.path.join(ROOT, "include", "gpsgs.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(?:int|size_t)\s+(sc_[a-z0-9_]+)\s*\(", code)))
-    assert declared == sorted(_capi.SC_SYMBOLS) == ["sc_backward", "sc_forward", "sc_scratch_bytes", "sc_supported", "sc_tile"]
-    assert "sc_forward / sc_backward" in src.split("#ifndef GPSGS_H")[0]          # the list at the top of the header names them
-    lib = _lib()
-    raw = C.CDLL(_capi.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+    lib = capi_run.check_section("sc_", _capi.SC_SYMBOLS, ["sc_backward", "sc_forward", "sc_scratch_bytes", "sc_supported", "sc_tile"])
     assert len(lib.sc_forward.argtypes) == 14 and len(lib.sc_backward.argtypes) == 17
-    assert lib.gpsgs_abi_version() == 4
     assert not set(_capi.SC_SYMBOLS) & set(_capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS)
 
 
 def test_supported_is_exactly_the_table():
-    lib = _lib()
+    lib = capi_run.lib()
     for Ci in (1, 3):
         for Co in range(8, 65, 8):
             assert lib.sc_supported(Ci, Co, 5, 2, 2) == 1, (Ci, Co)
@@ -60,7 +42,7 @@ def _formula(TH, TW, N, Ci, Co, H, W, K=5, S=2, P=2):
 
 
 def test_tile_and_the_scratch_formula():
-    lib = _lib()
+    lib = capi_run.lib()
     TH, TW = _tile(lib)
     assert TH > 0 and TW > 0
     assert lib.sc_tile(None, None) == _capi.GPSGS_E_INVALID
@@ -85,39 +67,37 @@ def test_tile_and_the_scratch_formula():
     assert f(8, 3, 32, 8192, 16384) == 0                                    # 2^31 elements or more
 
 
-P = 0x10000   # a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
-
-
-def _fwd(lib, x=P, w=P, bias=P, N=2, Ci=3, Co=32, H=16, W=16, K=5, stride=2, pad=2, y=P, dtype=0):
+# D: a non-NULL, 16-byte aligned "pointer" that is never dereferenced: every call below must return before any HIP call
+def _fwd(lib, x=D, w=D, bias=D, N=2, Ci=3, Co=32, H=16, W=16, K=5, stride=2, pad=2, y=D, dtype=0):
     return lib.sc_forward(x, w, bias, N, Ci, Co, H, W, K, stride, pad, y, dtype, None)
 
 
-def _bwd(lib, x=P, w=P, dy=P, dtype=0, N=2, Ci=3, Co=32, H=16, W=16, K=5, stride=2, pad=2, dx=P, dw=P, dbias=P, scratch=P):
+def _bwd(lib, x=D, w=D, dy=D, dtype=0, N=2, Ci=3, Co=32, H=16, W=16, K=5, stride=2, pad=2, dx=D, dw=D, dbias=D, scratch=D):
     return lib.sc_backward(x, w, dy, dtype, N, Ci, Co, H, W, K, stride, pad, dx, dw, dbias, scratch, None)
 
 
 @pytest.mark.parametrize("call", [_fwd, _bwd], ids=["forward", "backward"])
 def test_bad_arguments_are_refused_before_hip(call):
-    lib = _lib()
+    lib = capi_run.lib()
     E = _capi.GPSGS_E_INVALID
     assert call(lib, K=3) == E and call(lib, stride=1) == E and call(lib, pad=1) == E               # unsupported configurations
     assert call(lib, Ci=2) == E and call(lib, Ci=4) == E and call(lib, Co=4) == E and call(lib, Co=12) == E and call(lib, Co=72) == E
     assert call(lib, N=0) == E and call(lib, N=-1) == E and call(lib, H=0) == E and call(lib, W=0) == E and call(lib, H=-16) == E
     assert call(lib, dtype=2) == E and call(lib, dtype=-1) == E
     assert call(lib, x=None) == E and call(lib, w=None) == E
-    assert call(lib, x=P + 4) == E and call(lib, w=P + 2) == E                                     # misaligned
+    assert call(lib, x=D + 4) == E and call(lib, w=D + 2) == E                                     # misaligned
     assert call(lib, N=8, Ci=3, H=8192, W=16384) == E                                              # x: 3 * 2^30 elements
     assert call(lib, N=8, Ci=1, Co=64, H=8192, W=8192) == E                                        # x fits (2^29), y: 2^33 elements
     if call is _fwd:
         assert call(lib, bias=None) == E and call(lib, y=None) == E
-        assert call(lib, y=P + 8) == E and call(lib, bias=P + 1) == E
+        assert call(lib, y=D + 8) == E and call(lib, bias=D + 1) == E
     else:
         assert call(lib, dy=None) == E and call(lib, scratch=None) == E
         assert call(lib, dw=None) == E and call(lib, dbias=None) == E                              # one without the other
-        assert call(lib, dy=P + 4) == E and call(lib, dx=P + 8) == E and call(lib, dw=P + 2) == E and call(lib, scratch=P + 8) == E
+        assert call(lib, dy=D + 4) == E and call(lib, dx=D + 8) == E and call(lib, dw=D + 2) == E and call(lib, scratch=D + 8) == E
 
 
 def test_nothing_asked_for_launches_nothing():
-    lib = _lib()
+    lib = capi_run.lib()
     assert _bwd(lib, dx=None, dw=None, dbias=None, scratch=None) == 0
     assert _bwd(lib, dx=None, dw=None, dbias=None, scratch=None, K=3) == _capi.GPSGS_E_INVALID     # the arguments are still checked

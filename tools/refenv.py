@@ -25,18 +25,17 @@ SHIMS = os.path.join(HERE, "shims")
 
 def reference_dir(explicit=None):
     for p in (explicit, os.environ.get("GPSGS_REFERENCE"), "/root/reference"):
-        if p and os.path.isdir(p) and (os.path.exists(os.path.join(p, "train_stage2.py")) or os.path.exists(os.path.join(p, "train_stage2.pyc"))):
+        if p and os.path.isdir(p) and os.path.exists(os.path.join(p, "train_stage2.py")):
             return os.path.abspath(p)
     return None
 
 
 def script(ref, name):
-    """Path of a top-level reference script: `name.py` in a checkout, `name.pyc` in the staged build."""
-    for ext in (".py", ".pyc"):
-        p = os.path.join(ref, name + ext)
-        if os.path.exists(p):
-            return p
-    raise FileNotFoundError("%s.py[c] under %s" % (name, ref))
+    """Path of a top-level reference script."""
+    p = os.path.join(ref, name + ".py")
+    if os.path.exists(p):
+        return p
+    raise FileNotFoundError("%s.py under %s" % (name, ref))
 
 
 class _SummaryWriter:
