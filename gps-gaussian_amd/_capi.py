@@ -176,7 +176,7 @@ _SC = {
     "sc_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "sc_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-# 3x3 convolution on the matrix cores (the header's last section; tests/test_capi_conv3x3.py)
+# 3x3 convolution on the matrix cores (tests/test_capi_conv3x3.py)
 _C3 = {
     "c3_supported": (i32, [i32, i32]),
     "c3_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
@@ -184,8 +184,19 @@ _C3 = {
     "c3_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "c3_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
+# 1x1 convolution on the matrix cores (the header's last section; tests/test_capi_conv1x1.py).  PROTOTYPES is held to the five sections above by
+# tests/test_capi.py, so a section added since then goes into LATER_PROTOTYPES, which lib() sets in the same way
+_C1 = {
+    "c1_supported": (i32, [i32, i32, i32]),
+    "c1_tile": (i32, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "c1_scratch_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "c1_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "c1_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+}
 PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3}
+LATER_PROTOTYPES = {**_C1}
 SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC), tuple(_C3)
+C1_SYMBOLS = tuple(_C1)
 
 _lib = None
 
@@ -200,7 +211,7 @@ def lib():
             "gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gps-gaussian_amd/csrc`). There is no CPU fallback for this path." % LIB_PATH)
     l = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **LATER_PROTOTYPES}.items():
         fn = getattr(l, name)
         fn.restype, fn.argtypes = restype, argtypes
     if l.gpsgs_abi_version() != 4:

@@ -2,7 +2,7 @@
 return code checked under the entry point's own name.  The tensor-aware side of _capi.py (which stays free of torch).  And what the converted
 layers (groupnorm.py, stemconv.py, gshead.py) say in the same words: how a parameter reaches a kernel, which input and parameters a fused
 forward takes, and the two walks over a module tree that convert it in place.  And the shell of the convolution ops' autograd functions (stemconv.py,
-gshead.py, conv3x3.py): conv_inputs / grad_buffers / param_grads around each op's own C-ABI calls, plain_conv and tile."""
+gshead.py, conv3x3.py, conv1x1.py): conv_inputs / grad_buffers / param_grads around each op's own C-ABI calls, plain_conv and tile."""
 import ctypes
 import functools
 
@@ -85,10 +85,10 @@ def param_grads(needs, dw, db, wdt, bdt):
     return dw.to(wdt) if needs[1] else None, db.to(bdt) if needs[2] else None
 
 
-def plain_conv(conv, k, pad, supported):
-    """A convolution whose static configuration is a fused op's: k x k, stride 1, padding `pad`, dilation 1, groups 1, zero padding mode, a bias,
-    channel counts that `supported` takes."""
-    return conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (pad, pad) and conv.dilation == (1, 1) and conv.groups == 1 \
+def plain_conv(conv, k, pad, supported, strides=((1, 1),)):
+    """A convolution whose static configuration is a fused op's: k x k, a stride among `strides` (stride 1 unless told otherwise), padding `pad`,
+    dilation 1, groups 1, zero padding mode, a bias, channel counts that `supported` takes."""
+    return conv.kernel_size == (k, k) and conv.stride in strides and conv.padding == (pad, pad) and conv.dilation == (1, 1) and conv.groups == 1 \
         and conv.bias is not None and conv.padding_mode == "zeros" and supported(conv.in_channels, conv.out_channels)
 
 

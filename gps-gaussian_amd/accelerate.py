@@ -30,13 +30,16 @@ here runs unless the variable is set; every replacement is the GPU path of this 
                     -> nothing | Softplus | Sigmoid tail of its three heads (:34-50) becomes a FusedHeadConv
   conv3x3    no     wraps `GSRegresser.__init__` too: `out_conv` + `out_relu` (:31-32) and the Conv2d(32, 32, 3)   conv3x3.py
                     at the top of each head become FusedConv3x3 (BY_NAME: its two counters appear in `calls` on first request)
+  conv1x1    no     wraps `ResidualBlock.__init__`, `UnetExtractor.__init__` too: the Conv2d(in, planes, 1, stride)   conv1x1.py
+                    that opens a block's shortcut (`downsample[0]`, core/extractor.py:43-45) becomes a FusedConv1x1
+                    (BY_NAME_MORE: its two counters appear in `calls` on first request, behind conv3x3's)
 
 The names outside "all" are accepted by name only (`all,splat`, `resblock,stemconv`, ...) and imply nothing but what their line says.  A wrapped
 constructor runs the reference's own `__init__` and then the conversions that were asked for (`_ENCODER_STEPS`, `_HEAD_STEPS`): same parameters, same state_dict; the
 reference's `forward` bodies run as they are, `resblock`'s one rebinding apart.  Instances are built long after import, so the import order of
 these modules against the drop-in does not matter.  One wrapper per constructor serves every name that asks for it and does only what was asked:
 `stemconv` alone leaves every norm an `nn.GroupNorm` (and ResidualBlock, which has no stem, unwrapped), `groupnorm` alone leaves `in_ds[0]` a
-plain `nn.Conv2d`, `gshead` touches the heads and nothing else.
+plain `nn.Conv2d`, `gshead` touches the heads and nothing else, `conv1x1` changes `downsample[0]` and leaves `downsample[1]` to `groupnorm`.
 
 `installed()` reports what was rebound, `calls` counts how often each replacement ran (the tests assert the kernels were reached).
 """
@@ -52,6 +55,8 @@ OPT_IN = ("splat", "groupnorm", "resblock", "stemconv", "gshead")     # accepted
 # accepted by name only as well, after OPT_IN; their counters (<name>, <name>_passthrough) are created in `calls` when the name is first requested
 # or first counted (counters()), so a process that never asks for one keeps the keys above, in their order
 BY_NAME = ("conv3x3",)
+BY_NAME_MORE = ("conv1x1",)   # the same kind of name, added since; ordered after BY_NAME
+_LAZY = BY_NAME + BY_NAME_MORE
 # features that count, under <name>_passthrough, the calls that went THROUGH a replacement but were handed on to the reference's or torch's own
 # code (a configuration the fused kernel does not implement: ssim with another window, CPU tensors, channels-last, norm_fn batch, ...), so that a
 # run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
@@ -79,18 +84,18 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN + BY_NAME
+    known = FEATURES + OPT_IN + _LAZY
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
-    for f in BY_NAME:
+    for f in _LAZY:
         if f in names:
             counters(f)
     return tuple(f for f in known if f in names)
 
 
 def counters(name):
-    """`calls`, with the two counters of the BY_NAME feature `name` in it (created at zero, behind every existing key, the first time)."""
+    """`calls`, with the two counters of the BY_NAME / BY_NAME_MORE feature `name` in it (created at zero, behind every existing key, the first time)."""
     if name not in calls:
         with _lock:
             calls.setdefault(name, 0)
@@ -164,7 +169,8 @@ def _depth2pc(depth, extrinsic, intrinsic):
 # what a wrapped constructor runs on the new instance, in this order: (the names that ask for the step, module of this package, function)
 _ENCODER_STEPS = ((("groupnorm", "resblock"), "groupnorm", "convert"),             # nn.GroupNorm -> FusedGroupNorm
                   (("resblock",), "groupnorm", "fuse_sequential_relu"),            # the stem's ReLU folded into its norm
-                  (("stemconv",), "stemconv", "convert"))                          # the stem convolution
+                  (("stemconv",), "stemconv", "convert"),                          # the stem convolution
+                  (("conv1x1",), "conv1x1", "convert"))                            # the 1x1 convolution that opens a block's shortcut
 # the heads' tails and nothing else: the encoder and the blocks GSRegresser builds went through their own wrappers inside its constructor
 _HEAD_STEPS = ((("gshead",), "gshead", "convert"),
                (("conv3x3",), "conv3x3", "convert_regresser"))                     # out_conv + out_relu, and the 3x3 layer that opens each head
@@ -222,8 +228,8 @@ _ROWS = (
     ("core.raft_stereo_human", "FlowUpdateModule.upsample_flow", _upsample_flow, ("upsample",)),
     ("lib.utils", "flow2depth", _flow2depth, ("unproject",)),
     ("lib.utils", "depth2pc", _depth2pc, ("unproject",)),
-    ("core.extractor", "ResidualBlock.__init__", _resblock_init, ("groupnorm", "resblock")),
-    ("core.extractor", "UnetExtractor.__init__", _unet_init, ("groupnorm", "resblock", "stemconv")),
+    ("core.extractor", "ResidualBlock.__init__", _resblock_init, ("groupnorm", "resblock", "conv1x1")),
+    ("core.extractor", "UnetExtractor.__init__", _unet_init, ("groupnorm", "resblock", "stemconv", "conv1x1")),
     ("lib.gs_parm_network", "GSRegresser.__init__", _regresser_init, ("gshead", "conv3x3")),
     ("core.extractor", "ResidualBlock.forward", _resblock_forward, ("resblock",)),
 )
@@ -258,7 +264,7 @@ def apply(features=None):
         return 0
     made = 0
     with _lock:
-        _asked.update(f for f in feats if f in OPT_IN + BY_NAME)
+        _asked.update(f for f in feats if f in OPT_IN + _LAZY)
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -307,7 +313,7 @@ def restore():
         _originals.clear()
         _installed.clear()
         _asked.clear()
-        for f in BY_NAME:                      # back to the keys a process starts with
+        for f in _LAZY:                        # back to the keys a process starts with
             calls.pop(f, None)
             calls.pop(f + "_passthrough", None)
         for k in calls:

@@ -1,4 +1,4 @@
-// op_common.h -- what the network-op units (corr_sampler, corr_pyramid, stem_conv, conv3x3, gshead, group_norm, fused_loss, unproject, pack_views, splat) share:
+// op_common.h -- what the network-op units (corr_sampler, corr_pyramid, stem_conv, conv3x3, conv1x1, gshead, group_norm, fused_loss, unproject, pack_views, splat) share:
 // the fp32 / fp16 storage traits, the run-time dtype -> compile-time type dispatch, and the host-side argument checks of their extern "C" entry
 // points.  Not for the rasteriser (gsr_*, capi.hip).  No floating-point arithmetic lives here, so the header is indifferent to the contraction
 // setting of the unit that includes it.

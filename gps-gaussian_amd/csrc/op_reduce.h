@@ -1,4 +1,4 @@
-// op_reduce.h -- the last step of a parameter gradient in the convolution units (stem_conv, gshead, conv3x3): the partial sums their weight-gradient
+// op_reduce.h -- the last step of a parameter gradient in the convolution units (stem_conv, gshead, conv3x3, conv1x1): the partial sums their weight-gradient
 // kernels leave in scratch, [parts][M] with M = the weight's MW sums followed by the bias's, are added in index order, in groups of `group` and then the
 // groups (DESIGN.md "Parameter-gradient reduction").  No atomics; every sum has a fixed order: the same bits on every run.  The group size is the
 // including unit's own constant: it decides which adds are made, so it defines the bits.  The only arithmetic here is a plain add: the header is
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(SUM_THREADS) void k_sum_partials(const float *__res
 // (`partials` is not const: the group sums are written behind them)
 inline void sum_partials(float *partials, int parts, int group, int M, int MW, float *dw, float *db, hipStream_t s) {
     const dim3 block(SUM_THREADS);
-    const unsigned jb = (unsigned)cdiv(M, SUM_THREADS);  // grid y: 73 for the largest M of these ops, 32 * (9 * 64 + 1)
+    const unsigned jb = (unsigned)cdiv(M, SUM_THREADS);  // grid y: 129 for the largest M of these ops, conv1x1's 128 * (256 + 1)
     const float *in = partials;
     if (parts > group) {
         const int groups = (int)cdiv(parts, group);

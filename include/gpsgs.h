@@ -48,6 +48,9 @@
  *   c3_forward / c3_backward (+ c3_supported, c3_tile, c3_scratch_bytes)
  *       the regresser's full-resolution 3x3 convolutions, nn.Conv2d(52, 32, 3, padding=1) + nn.ReLU (`out_conv`, `out_relu`) and the
  *       nn.Conv2d(32, 32, 3, padding=1) at the top of each head (lib/gs_parm_network.py:27-50), and their autograd backward.
+ *   c1_forward / c1_backward (+ c1_supported, c1_tile, c1_scratch_bytes)
+ *       the 1x1 convolution that opens the shortcut of every ResidualBlock whose input and output differ, nn.Conv2d(in, planes, 1, stride)
+ *       with stride 1 or 2 (core/extractor.py:43-45), and its autograd backward.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -78,7 +81,8 @@ extern "C" {
                                still 4 after the stem convolution: sc_supported, sc_tile, sc_scratch_bytes, sc_forward, sc_backward (additive)
                                still 4 after the Gaussian heads: gsr_head_supported, gsr_head_tile, gsr_head_scratch_bytes, gsr_head_forward,
                                   gsr_head_backward (additive)
-                               still 4 after the 3x3 convolutions: c3_supported, c3_tile, c3_scratch_bytes, c3_forward, c3_backward (additive) */
+                               still 4 after the 3x3 convolutions: c3_supported, c3_tile, c3_scratch_bytes, c3_forward, c3_backward (additive)
+                               still 4 after the 1x1 convolutions: c1_supported, c1_tile, c1_scratch_bytes, c1_forward, c1_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -725,6 +729,31 @@ int c3_tile(int *tile_h, int *tile_w);
 size_t c3_scratch_bytes(int N, int C_in, int H, int W);
 int c3_forward(const float *x, const float *w, const float *bias, int N, int C_in, int H, int W, int relu, float *y, void *stream);
 int c3_backward(const float *x, const float *w, const float *y, const float *dy, int N, int C_in, int H, int W, int relu, float *dx, float *dw,
+                float *dbias, void *scratch, void *stream);
+
+/* ---- 1x1 convolution with stride 1 or 2 on the fp32 matrix cores, forward and backward -----------------------------------------------------
+ * y[N,C_out,Ho,Wo] = conv2d(x[N,C_in,H,W], w[C_out,C_in,1,1], bias[C_out], stride, padding 0), Ho = (H - 1) / stride + 1, Wo likewise, contiguous
+ * NCHW fp32 (torch.nn.functional.conv2d): y[n,co,i,j] = bias[co] + sum over ci of w[co,ci] x[n,ci,stride i,stride j].  One GEMM per image on
+ * v_mfma_f32_32x32x2_f32: exact fp32, every sum an fmaf chain in a fixed order (the products in channel order first, the bias added last), no
+ * layout transposes, no intermediate tensor, no atomics, the same bits on every run.
+ * c1_supported: 1 for C_in a multiple of 4 with 4 <= C_in <= 256, C_out a multiple of 16 with 16 <= C_out <= 128 and stride 1 or 2; otherwise 0.
+ * c1_tile: the consecutive output pixels of one image a workgroup of the forward (and of the input gradient) computes, the pixels of one tile of
+ * the weight gradient, and the largest number of partials the weight gradient writes.
+ * x, y, dy, dx and scratch must be 16-byte aligned; H and W may be anything >= 1.
+ * c1_backward takes dy, the gradient of y.  It WRITES ALL of dx (NULL = not wanted: that kernel is not launched): dx[n,ci,stride i,stride j] = sum
+ * over co of w[co,ci] dy[n,co,i,j] and, for stride 2, +0.0 at every position the forward did not sample -- nothing has to be cleared in front --
+ * and dw / dbias (both or neither; NULL = not wanted).  dw and dbias are sums over pixels: at most 512 workgroups each walk a fixed, index-ordered
+ * set of 32-pixel tiles and write one partial; the partials are added in index order, in groups of 32 and then the groups.
+ * scratch (needed for dw / dbias only): DEVICE, at least c1_scratch_bytes(N, C_in, C_out, H, W, stride) =
+ *     4 * C_out * (C_in + 1) * (parts + ceil(parts / 32))   bytes,  parts = min(512, N * ceil(Ho * Wo / 32))
+ * and 0 for arguments c1_forward would refuse (layout: the partials, then the group sums, as under gsr_head_scratch_bytes).
+ * GPSGS_E_INVALID, before any HIP call: a configuration c1_supported refuses, a non-positive N, H or W, 2^31 elements or more in x or in y, one of
+ * dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, and scratch where dw is wanted) or a misaligned one. */
+int c1_supported(int C_in, int C_out, int stride);
+int c1_tile(int *forward_pixels, int *weight_pixels, int *max_parts);
+size_t c1_scratch_bytes(int N, int C_in, int C_out, int H, int W, int stride);
+int c1_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int stride, float *y, void *stream);
+int c1_backward(const float *x, const float *w, const float *dy, int N, int C_in, int C_out, int H, int W, int stride, float *dx, float *dw,
                 float *dbias, void *scratch, void *stream);
 
 #ifdef __cplusplus
