@@ -91,9 +91,9 @@ _BWD = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp
 _BWD_EX = _BWD + [C.POINTER(GsrViewExt)]
 _BWD_CAMERA = _BWD_EX + [vp, vp, vp, vp, sz]
 
-# name -> (restype, argtypes) of every symbol include/gpsgs.h declares, in the header's five sections.  lib() sets the prototypes from this table, so
-# a symbol cannot be listed without one (ctypes' default `int` conversion would truncate a 64-bit device pointer silently); tests/test_capi.py
-# cross-checks the first section's names against the header and that every name has its prototype set.
+# name -> (restype, argtypes) of every symbol include/gpsgs.h declares, one dict per section of the header, in its order.  lib() sets the prototypes from
+# PROTOTYPES, their union, so a symbol cannot be listed without one (ctypes' default `int` conversion would truncate a 64-bit device pointer
+# silently); tests/test_capi.py holds the union to the header's declarations and to SECTIONS, and checks that every name has its prototype set.
 _GSR = {
     "gpsgs_abi_version": (i32, []),
     "gsr_supported_flags": (i32, []),
@@ -184,8 +184,7 @@ _C3 = {
     "c3_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "c3_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-# 1x1 convolution on the matrix cores (the header's last section; tests/test_capi_conv1x1.py).  PROTOTYPES is held to the five sections above by
-# tests/test_capi.py, so a section added since then goes into LATER_PROTOTYPES, which lib() sets in the same way
+# 1x1 convolution on the matrix cores (the header's last section; tests/test_capi_conv1x1.py)
 _C1 = {
     "c1_supported": (i32, [i32, i32, i32]),
     "c1_tile": (i32, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -193,10 +192,9 @@ _C1 = {
     "c1_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "c1_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3}
-LATER_PROTOTYPES = {**_C1}
-SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS = tuple(_GSR), tuple(_GN), tuple(_GNE), tuple(_SC), tuple(_C3)
-C1_SYMBOLS = tuple(_C1)
+PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3, **_C1}
+SECTIONS = tuple(tuple(s) for s in (_GSR, _GN, _GNE, _SC, _C3, _C1))     # each section's names, in header order
+SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS, C1_SYMBOLS = SECTIONS
 
 _lib = None
 
@@ -211,7 +209,7 @@ def lib():
             "gps_gaussian_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gps-gaussian_amd/csrc`). There is no CPU fallback for this path." % LIB_PATH)
     l = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **LATER_PROTOTYPES}.items():
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(l, name)
         fn.restype, fn.argtypes = restype, argtypes
     if l.gpsgs_abi_version() != 4:

@@ -29,12 +29,12 @@ here runs unless the variable is set; every replacement is the GPU path of this 
   gshead     no     wraps lib/gs_parm_network.py:8 `GSRegresser.__init__`: the ReLU -> Conv2d(32, 4|3|1, 1) gshead.py
                     -> nothing | Softplus | Sigmoid tail of its three heads (:34-50) becomes a FusedHeadConv
   conv3x3    no     wraps `GSRegresser.__init__` too: `out_conv` + `out_relu` (:31-32) and the Conv2d(32, 32, 3)   conv3x3.py
-                    at the top of each head become FusedConv3x3 (BY_NAME: its two counters appear in `calls` on first request)
+                    at the top of each head become FusedConv3x3
   conv1x1    no     wraps `ResidualBlock.__init__`, `UnetExtractor.__init__` too: the Conv2d(in, planes, 1, stride)   conv1x1.py
                     that opens a block's shortcut (`downsample[0]`, core/extractor.py:43-45) becomes a FusedConv1x1
-                    (BY_NAME_MORE: its two counters appear in `calls` on first request, behind conv3x3's)
 
-The names outside "all" are accepted by name only (`all,splat`, `resblock,stemconv`, ...) and imply nothing but what their line says.  A wrapped
+The names outside "all" are accepted by name only (`all,splat`, `resblock,stemconv`, ...) and imply nothing but what their line says; the counters
+of the last two (`BY_NAME`, from the table `NAMES`) appear in `calls` when the name is first requested, in the order asked for.  A wrapped
 constructor runs the reference's own `__init__` and then the conversions that were asked for (`_ENCODER_STEPS`, `_HEAD_STEPS`): same parameters, same state_dict; the
 reference's `forward` bodies run as they are, `resblock`'s one rebinding apart.  Instances are built long after import, so the import order of
 these modules against the drop-in does not matter.  One wrapper per constructor serves every name that asks for it and does only what was asked:
@@ -50,21 +50,39 @@ import os
 import sys
 import threading
 
-FEATURES = ("pack", "loss", "corr", "upsample", "unproject")          # what "all" means
-OPT_IN = ("splat", "groupnorm", "resblock", "stemconv", "gshead")     # accepted by name only, never implied by "all"
-# accepted by name only as well, after OPT_IN; their counters (<name>, <name>_passthrough) are created in `calls` when the name is first requested
-# or first counted (counters()), so a process that never asks for one keeps the keys above, in their order
-BY_NAME = ("conv3x3",)
-BY_NAME_MORE = ("conv1x1",)   # the same kind of name, added since; ordered after BY_NAME
-_LAZY = BY_NAME + BY_NAME_MORE
-# features that count, under <name>_passthrough, the calls that went THROUGH a replacement but were handed on to the reference's or torch's own
-# code (a configuration the fused kernel does not implement: ssim with another window, CPU tensors, channels-last, norm_fn batch, ...), so that a
-# run on the eager path for those calls leaves a trace; the full-pipeline runner prints them
-_PASSTHROUGH = ("loss", "unproject", "groupnorm", "resblock", "stemconv", "gshead")
+# Every name GPSGS_ACCELERATE accepts, in the order requested() answers in: name -> (implied by "all", has a <name>_passthrough counter, its
+# counters exist from import).  A passthrough counter counts the calls that went THROUGH a replacement but were handed on to the reference's or
+# torch's own code (a configuration the fused kernel does not implement: ssim with another window, CPU tensors, channels-last, norm_fn batch, ...),
+# so that a run on the eager path for those calls leaves a trace; the full-pipeline runner prints them.  The counters of a
+# name whose last column is False are created in `calls` when the name is first requested or first counted (counters()), behind every existing
+# key, so a process that never asks for one keeps the keys of the other names, in their order.  Everything below is derived from this table.
+NAMES = {
+    "pack":      (True,  False, True),
+    "loss":      (True,  True,  True),
+    "corr":      (True,  False, True),
+    "upsample":  (True,  False, True),
+    "unproject": (True,  True,  True),
+    "splat":     (False, False, True),
+    "groupnorm": (False, True,  True),
+    "resblock":  (False, True,  True),
+    "stemconv":  (False, True,  True),
+    "gshead":    (False, True,  True),
+    "conv3x3":   (False, True,  False),
+    "conv1x1":   (False, True,  False),
+}
+FEATURES = tuple(n for n, row in NAMES.items() if row[0])                       # what "all" means
+OPT_IN = tuple(n for n, row in NAMES.items() if not row[0] and row[2])          # accepted by name only, never implied by "all"
+BY_NAME = tuple(n for n, row in NAMES.items() if not row[0] and not row[2])     # by name only as well; counters on first request
 _PREFIXES = ("lib", "core", "gaussian_renderer", "config", "train_stage1", "train_stage2", "test_view_interp", "test_real_data")
 _SUBSTITUTES = {"lib.TaichiRender": "splat"}   # module served instead of the reference's file -> the opt-in name that asks for it
 
-calls = {k: 0 for k in FEATURES + OPT_IN + tuple(f + "_passthrough" for f in _PASSTHROUGH)}
+
+def _keys(*names):
+    """The counters of `names`: one per name, then the <name>_passthrough of those that have one."""
+    return names + tuple(n + "_passthrough" for n in names if NAMES[n][1])
+
+
+calls = dict.fromkeys(_keys(*FEATURES, *OPT_IN), 0)
 _asked = set()           # the opt-in names apply() has been given so far: what the constructor wrappers convert (_ENCODER_STEPS, _HEAD_STEPS)
 _installed = {}          # "module.attr" -> feature
 _originals = {}          # "module.attr" -> (holder, name, the reference's own object): restore(), original(), and the two pass-through cases below
@@ -84,22 +102,22 @@ def requested(value=None):
     names = tuple(x.strip() for x in v.replace(";", ",").split(",") if x.strip())
     if any(x in ("1", "all", "on", "true") for x in names):
         names += FEATURES
-    known = FEATURES + OPT_IN + _LAZY
+    known = tuple(NAMES)
     bad = [x for x in names if x not in known + ("1", "all", "on", "true")]
     if bad:
         raise ValueError("GPSGS_ACCELERATE: unknown feature(s) %s (known: %s)" % (bad, ", ".join(known)))
-    for f in _LAZY:
+    for f in BY_NAME:
         if f in names:
             counters(f)
     return tuple(f for f in known if f in names)
 
 
 def counters(name):
-    """`calls`, with the two counters of the BY_NAME / BY_NAME_MORE feature `name` in it (created at zero, behind every existing key, the first time)."""
+    """`calls`, with the counters of the BY_NAME feature `name` in it (created at zero, behind every existing key, the first time)."""
     if name not in calls:
         with _lock:
-            calls.setdefault(name, 0)
-            calls.setdefault(name + "_passthrough", 0)
+            for k in _keys(name):
+                calls.setdefault(k, 0)
     return calls
 
 
@@ -264,7 +282,7 @@ def apply(features=None):
         return 0
     made = 0
     with _lock:
-        _asked.update(f for f in feats if f in OPT_IN + _LAZY)
+        _asked.update(f for f in feats if f in OPT_IN + BY_NAME)
         for feat, rows in _table(feats).items():
             for modname, attr, repl in rows:
                 mod = _loaded(modname)
@@ -313,9 +331,8 @@ def restore():
         _originals.clear()
         _installed.clear()
         _asked.clear()
-        for f in _LAZY:                        # back to the keys a process starts with
-            calls.pop(f, None)
-            calls.pop(f + "_passthrough", None)
+        for k in _keys(*BY_NAME):              # back to the keys a process starts with
+            calls.pop(k, None)
         for k in calls:
             calls[k] = 0
 

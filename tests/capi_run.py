@@ -31,8 +31,8 @@ def header_code():
 
 
 def declared(*prefixes):
-    """Sorted names of the functions the header declares with one of the prefixes ("gn_", ...)."""
-    return sorted(set(re.findall(r"\b(?:int|size_t|const char \*)\s*\*?\s*((?:%s)[a-z0-9_]+)\s*\(" % "|".join(prefixes), header_code())))
+    """Sorted names of the functions the header declares with one of the prefixes ("gn_", ...); without a prefix, all of them."""
+    return sorted(set(re.findall(r"\b(?:int|size_t|const char \*)\s*\*?\s*((?:%s)[a-z0-9_]+)\s*\(" % "|".join(prefixes or ("[a-z0-9]+_",)), header_code())))
 
 
 def declared_arg_count(name):

@@ -29,10 +29,11 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_every_listed_symbol_has_its_prototype():
-    """The prototype table and the five symbol tuples are one list, and lib() leaves no symbol on ctypes' default conversion (which would pass a
-    64-bit device pointer as a C int)."""
-    names = _capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS + _capi.C3_SYMBOLS
+    """The prototype table is the sections' symbol tuples end to end and holds every function the header declares, whatever its section, and
+    lib() leaves no symbol on ctypes' default conversion (which would pass a 64-bit device pointer as a C int)."""
+    names = sum(_capi.SECTIONS, ())
     assert tuple(_capi.PROTOTYPES) == names
+    assert sorted(_capi.PROTOTYPES) == capi_run.declared()
     lib = _capi.lib()
     assert [n for n in names if getattr(lib, n).argtypes is None] == []
 

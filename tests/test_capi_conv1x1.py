@@ -15,18 +15,11 @@ NAMES = ["c1_backward", "c1_forward", "c1_scratch_bytes", "c1_supported", "c1_ti
 
 
 def test_symbols_are_declared_exported_and_bound():
-    """What capi_run.check_section holds the earlier sections to, against the table these symbols are in: _capi.PROTOTYPES is held to the earlier
-    sections by test_capi.py, so this one's prototypes are in _capi.LATER_PROTOTYPES, which lib() sets in the same way."""
-    assert capi_run.declared("c1_") == sorted(_capi.C1_SYMBOLS) == NAMES
-    assert "c1_forward / c1_backward" in capi_run.header().split("#ifndef GPSGS_H")[0]
-    assert tuple(_capi.LATER_PROTOTYPES) == _capi.C1_SYMBOLS and not set(_capi.LATER_PROTOTYPES) & set(_capi.PROTOTYPES)
-    lib, exported = capi_run.lib(), capi_run.raw()
+    # (with every name in PROTOTYPES and lib()'s argtypes / restype equal to the table's entry)
+    lib = capi_run.check_section("c1_", _capi.C1_SYMBOLS, NAMES)
+    # the header's argument lists and the ctypes prototypes agree in length
     for name in NAMES:
-        assert hasattr(exported, name), name
-        restype, argtypes = _capi.LATER_PROTOTYPES[name]
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype is restype, name
-        assert capi_run.declared_arg_count(name) == len(argtypes), name       # the header's argument lists and the ctypes prototypes agree in length
-    assert lib.gpsgs_abi_version() == 4
+        assert capi_run.declared_arg_count(name) == len(_capi.PROTOTYPES[name][1]), name
     assert len(lib.c1_forward.argtypes) == 11 and len(lib.c1_backward.argtypes) == 14
     assert lib.c1_scratch_bytes.restype is C.c_size_t
     assert not set(_capi.C1_SYMBOLS) & set(_capi.SYMBOLS + _capi.GN_SYMBOLS + _capi.GNE_SYMBOLS + _capi.SC_SYMBOLS + _capi.C3_SYMBOLS)

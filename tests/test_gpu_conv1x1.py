@@ -12,21 +12,20 @@ ATen's convolution runs on the GPU in two tests only: the pass-through cases (fo
 call twice) and the block test, whose unconverted block is what the converted one is compared with."""
 import copy
 import functools
-import json
 import zlib
 
 import pytest
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi, accelerate as A
 from gps_gaussian_amd import conv1x1 as C1
 
+import convop_run as R
+from convop_run import KEYS, gamma
+
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24
-KEYS = ("y", "dx", "dw", "db")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -36,30 +35,14 @@ def _counters():
     A.restore()      # the process's counter keys are what they were
 
 
-def _gamma(n):
-    return n * U / (1.0 - n * U)
-
-
-@functools.lru_cache(maxsize=None)
-def _tile():
-    import ctypes as C
-    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
-    assert _capi.lib().c1_tile(C.byref(a), C.byref(b), C.byref(c)) == 0
-    return a.value, b.value, c.value
+_tile = C1.tile
 
 
 @functools.lru_cache(maxsize=None)
 def _group():
-    """The reduction's group size G, read off c1_scratch_bytes: scratch = 4 M (parts + groups) with groups = ceil(parts / G), so the first tile
-    count whose scratch holds two group sums is G + 1."""
+    """The reduction's group size G, read off c1_scratch_bytes: 4 M (parts + groups) bytes for the M = C_out (C_in + 1) sums of [1,4,1,t WP] -> 16."""
     _, WP, PARTS = _tile()
-    M = 16 * (4 + 1)
-    for t in range(1, PARTS + 1):
-        extra = _capi.lib().c1_scratch_bytes(1, 4, 16, 1, t * WP, 1) // (4 * M) - t
-        assert extra in (1, 2)
-        if extra == 2:
-            return t - 1
-    raise AssertionError("no group boundary below the cap on the partial sums")
+    return R.group_size(lambda t: _capi.lib().c1_scratch_bytes(1, 4, 16, 1, t * WP, 1) // (4 * 16 * (4 + 1)), PARTS)
 
 
 def _factor(n):
@@ -93,71 +76,37 @@ CASES = ["one_pixel_s1", "one_pixel_s2", "tile_TP-1", "tile_TP", "tile_TP+1", "o
          "limits_256_128", "parts+1", "group+1", "two_tiles_odd_s2", "two_tiles_even_s2", "cin20_tail"]
 
 
-def _ref64(x, w, b, dy, stride):
-    """The fp64 convolution with its gradients, and the same sums over absolute values (what the bounds are made of)."""
-    out = {}
-    x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, b))
-    y = F.conv2d(x64, w64, b64, stride=stride)
-    y.backward(dy.double())
-    out.update(y=y.detach(), dx=x64.grad, dw=w64.grad, db=b64.grad)
-    xa, wa, ba = (t.double().abs().requires_grad_(True) for t in (x, w, b))
-    ya = F.conv2d(xa, wa, ba, stride=stride)
-    ya.backward(dy.double().abs())
-    out.update(abs_y=ya.detach(), abs_dx=xa.grad, abs_dw=wa.grad, abs_db=ba.grad)
-    return out
-
-
-def _bounds(ref, Ci, Co):
+def _bounds(ref, N, Ci, Co, H, W, s):
     P = ref["y"].numel() // Co                                     # N H_out W_out
-    return dict(y=_gamma(Ci + 1) * ref["abs_y"], dx=_gamma(Co) * ref["abs_dx"], dw=_gamma(P) * ref["abs_dw"], db=_gamma(P) * ref["abs_db"])
+    return dict(y=gamma(Ci + 1) * ref["abs_y"], dx=gamma(Co) * ref["abs_dx"], dw=gamma(P) * ref["abs_dw"], db=gamma(P) * ref["abs_db"])
 
 
 def _out_hw(H, W, s):
     return (H - 1) // s + 1, (W - 1) // s + 1
 
 
-def _inputs(name, N, Ci, Co, H, W, s):
-    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+def _inputs(gen, N, Ci, Co, H, W, s):
     x = torch.randn((N, Ci, H, W), generator=gen)
     w = torch.randn((Co, Ci, 1, 1), generator=gen) * 0.2
     b = torch.randn((Co,), generator=gen)
     w[Co // 2] = 0.0                    # one exact-zero filter
     dy = torch.randn((N, Co) + _out_hw(H, W, s), generator=gen)
-    ref = _ref64(x, w, b, dy, s)
-    return dict(dims=(N, Ci, Co, H, W, s), stride=s, x=x, w=w, b=b, dy=dy, ref=ref, bounds=_bounds(ref, Ci, Co))
+    return dict(x=x, w=w, b=b, dy=dy, conv=dict(stride=s))
 
 
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """Inputs, the fp64 reference and the bounds of one case: computed once, shared by every test that needs them, never modified."""
-    return _inputs(name, *_cases()[name])
+_case = R.case_cache(_cases, _inputs, _bounds)
 
 
-def _run(x, w, b, dy, stride, backward=True):
-    xg, wg, bg = (t.cuda().requires_grad_(backward) for t in (x, w, b))
-    y = C1.conv1x1(xg, wg, bg, stride)
-    if backward:
-        y.backward(dy.cuda())
-    torch.cuda.synchronize()
-    return dict(y=y.detach(), dx=xg.grad, dw=wg.grad, db=bg.grad)
+def _op(stride):
+    return lambda x, w, b: C1.conv1x1(x, w, b, stride)
 
 
-def _ratio(t, t64, bound):
-    """The worst error / bound; an error of zero is inside any bound (also a bound of zero), an error above a zero bound is infinite."""
-    d = (t.detach().double().cpu() - t64).abs()
-    r = torch.where(d == 0, torch.zeros_like(d), d / bound.clamp_min(1e-300))
-    return float(r.max())
+def _run(c):
+    return R.run_case(_op(c["conv"]["stride"]), c)
 
 
 def _check(test, name, got, c, who="fused"):
-    rec = dict(test=test, case=name, dims=list(c["dims"]), who=who, ratio={})
-    for k in KEYS:
-        assert got[k].shape == c["ref"][k].shape and got[k].dtype == torch.float32, k
-        rec["ratio"][k] = _ratio(got[k], c["ref"][k], c["bounds"][k])
-    print(json.dumps(rec))
-    for k in KEYS:
-        assert torch.isfinite(got[k]).all(), k
-        assert rec["ratio"][k] <= 1.0, "%s %s %s: error / bound = %.3f" % (who, name, k, rec["ratio"][k])
+    R.check(dict(test=test, case=name, dims=list(c["dims"]), who=who), "ratio", got, c["ref"], c["bounds"])
 
 
 def _unsampled(H, W, s):
@@ -179,7 +128,7 @@ def _assert_plus_zero_where_unsampled(dx, H, W, s):
 def test_forward_and_backward_within_the_bounds(name):
     c = _case(name)
     N, Ci, Co, H, W, s = c["dims"]
-    got = _run(c["x"], c["w"], c["b"], c["dy"], s)
+    got = _run(c)
     _check("fp32", name, got, c)
     if s == 2:
         _assert_plus_zero_where_unsampled(got["dx"], H, W, s)
@@ -191,7 +140,7 @@ def test_the_input_gradient_of_an_even_plane_is_plus_zero_where_nothing_was_samp
     c = _case("even_plane_s2")
     N, Ci, Co, H, W, s = c["dims"]
     assert (N, Ci, H, W, s) == (2, 48, 6, 8, 2)
-    got = _run(c["x"], c["w"], c["b"], c["dy"], s)
+    got = _run(c)
     assert _assert_plus_zero_where_unsampled(got["dx"], H, W, s) == N * Ci * (H * W - 3 * 4) == 3456
     m = _unsampled(H, W, s)
     assert bool(m[5].all()) and bool(m[:, 7].all()) and int((~m).sum()) == 12
@@ -206,72 +155,31 @@ def test_the_input_gradient_of_an_even_plane_is_plus_zero_where_nothing_was_samp
     assert torch.equal(dx, got["dx"])
 
 
-def _ints(shape, lo, hi, gen):
-    return torch.randint(lo, hi + 1, shape, generator=gen).float()
-
-
 @pytest.mark.parametrize("which", ["cin128_s1_tile+1", "cin48_s2_two_tiles", "cin32_s2_odd"])
 def test_small_integers_give_the_exact_answer(which):
-    """x in [-3, 3], w, b, dy in [-2, 2]: every product and partial sum is an integer far below 2^24, so y, dx, dw, db must EQUAL the fp64 result."""
     TP = _tile()[0]
     N, Ci, Co, H, W, s = {"cin128_s1_tile+1": (2, 128, 48) + _factor(TP + 1) + (1,), "cin48_s2_two_tiles": (1, 48, 96, 34, 36, 2),
                           "cin32_s2_odd": (3, 32, 64, 5, 7, 2)}[which]
-    gen = torch.Generator().manual_seed(zlib.crc32(which.encode()))
-    x, w, b = _ints((N, Ci, H, W), -3, 3, gen), _ints((Co, Ci, 1, 1), -2, 2, gen), _ints((Co,), -2, 2, gen)
-    dy = _ints((N, Co) + _out_hw(H, W, s), -2, 2, gen)
-    ref = _ref64(x, w, b, dy, s)
-    got = _run(x, w, b, dy, s)
-    for k in KEYS:
-        assert torch.equal(got[k].double().cpu(), ref[k]), k
+    got, _ = R.exact_integers(which, _op(s), ((N, Ci, H, W), (Co, Ci, 1, 1), (Co,), (N, Co) + _out_hw(H, W, s)), stride=s)
     if s == 2:
         _assert_plus_zero_where_unsampled(got["dx"], H, W, s)
 
 
 def test_two_runs_give_the_same_bits():
-    for name in ("two_tiles_odd_s2", "cin192_96", "group+1"):
-        c = _case(name)
-        a = _run(c["x"], c["w"], c["b"], c["dy"], c["stride"])
-        b = _run(c["x"], c["w"], c["b"], c["dy"], c["stride"])
-        for k in KEYS:
-            assert torch.equal(a[k], b[k]), (name, k)
+    R.two_runs(_run, [(name, _case(name)) for name in ("two_tiles_odd_s2", "cin192_96", "group+1")])
 
 
 @pytest.mark.parametrize("name", ["cin192_64", "two_tiles_even_s2"])
-def test_requires_grad_handling(name):
+def test_requires_grad_handling(name, monkeypatch):
     c = _case(name)
-    s = c["stride"]
-    full = _run(c["x"], c["w"], c["b"], c["dy"], s)
-    x, w, b, dy = (c[k].cuda() for k in ("x", "w", "b", "dy"))
-    # a frozen input: no input gradient, the same parameter gradients
-    wg, bg = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    y = C1.conv1x1(x, wg, bg, s)
-    y.backward(dy)
-    assert x.grad is None and torch.equal(y.detach(), full["y"]) and torch.equal(wg.grad, full["dw"]) and torch.equal(bg.grad, full["db"])
-    # frozen parameters: only the input gradient
-    xg = x.clone().requires_grad_(True)
-    C1.conv1x1(xg, w, b, s).backward(dy)
-    assert w.grad is None and b.grad is None and torch.equal(xg.grad, full["dx"])
-    # the bias only, then the weight only
-    bg = b.clone().requires_grad_(True)
-    C1.conv1x1(x, w, bg, s).backward(dy)
-    assert w.grad is None and x.grad is None and torch.equal(bg.grad, full["db"])
-    wg = w.clone().requires_grad_(True)
-    C1.conv1x1(x, wg, b, s).backward(dy)
-    assert b.grad is None and torch.equal(wg.grad, full["dw"])
-    with torch.no_grad():
-        y0 = C1.conv1x1(x, wg, bg, s)
-    assert y0.grad_fn is None and torch.equal(y0, full["y"])
-    # gradients in the parameters' dtypes and shapes
-    wd = w.double().requires_grad_(True)
-    C1.conv1x1(x, wd, b, s).backward(dy)
-    assert wd.grad.dtype == torch.float64 and wd.grad.shape == w.shape and torch.equal(wd.grad.float(), full["dw"])
+    R.requires_grad_matrix(monkeypatch, C1, "c1_backward", _op(c["conv"]["stride"]), c)
 
 
 @pytest.mark.parametrize("name", ["odd_plane_s2", "cin192_96"])
 def test_a_strided_or_misaligned_dy_gives_the_same_bits(name):
     c = _case(name)
-    s = c["stride"]
-    full = _run(c["x"], c["w"], c["b"], c["dy"], s)
+    s = c["conv"]["stride"]
+    full = _run(c)
     dy = c["dy"].cuda()
 
     def backward_with(g):
@@ -349,8 +257,8 @@ def test_a_converted_block_against_the_unconverted_block(dims):
         assert (A.calls["conv1x1"] - n0, A.calls["conv1x1_passthrough"] - p0) == ((1, 0) if who == "fused" else (0, 0))
         assert torch.equal(cap["x"], x)
         w, b = layer.weight.detach().cpu(), layer.bias.detach().cpu()
-        ref = _ref64(x.cpu(), w, b, cap["dy"].cpu(), s)
-        c = dict(dims=dims, ref=ref, bounds=_bounds(ref, Ci, Co))
+        ref = R.ref64(x, w, b, cap["dy"], stride=s)
+        c = dict(dims=dims, ref=ref, bounds=_bounds(ref, *dims))
         _check("block", "x".join(map(str, dims)), dict(y=cap["y"], dx=cap["dx"], dw=layer.weight.grad, db=layer.bias.grad), c, who=who)
         res[who] = (out.detach(), xin.grad)
     for a, b in zip(res["aten"], res["fused"]):
@@ -392,12 +300,7 @@ def test_what_the_op_does_not_take_goes_through_torch():
     plain, fused = plain[0], fused[0]
     x = torch.randn(2, 32, 20, 22, device="cuda")
 
-    def both(a, b, inp, **ac):
-        n0, p0 = A.calls["conv1x1"], A.calls["conv1x1_passthrough"]
-        with torch.autocast("cuda", enabled=bool(ac), **ac):
-            ya, yb = a(inp), b(inp)
-        assert A.calls["conv1x1"] == n0 and A.calls["conv1x1_passthrough"] == p0 + 1
-        assert ya.dtype == yb.dtype and ya.shape == yb.shape and ya.stride() == yb.stride() and torch.equal(ya, yb)
+    both = R.passthrough_pair(A.calls, "conv1x1")
 
     def forced(m):
         f = copy.deepcopy(m)

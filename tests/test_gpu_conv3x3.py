@@ -13,22 +13,21 @@ reference's: no error is excused by a flipped mask."""
 import copy
 import functools
 import json
-import zlib
 
 import pytest
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 import gps_gaussian_amd  # noqa: F401
-from gps_gaussian_amd import _capi, accelerate as A
+from gps_gaussian_amd import accelerate as A
 from gps_gaussian_amd import conv3x3 as C3
 from gps_gaussian_amd import gshead as GH
 
+import convop_run as R
+from convop_run import gamma
+
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24
 CO = 32
-KEYS = ("y", "dx", "dw", "db")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -38,16 +37,7 @@ def _counters():
     A.restore()      # the process's counter keys are what they were
 
 
-def _gamma(n):
-    return n * U / (1.0 - n * U)
-
-
-@functools.lru_cache(maxsize=None)
-def _tile():
-    import ctypes as C
-    th, tw = C.c_int(0), C.c_int(0)
-    assert _capi.lib().c3_tile(C.byref(th), C.byref(tw)) == 0
-    return th.value, tw.value
+_tile = C3.tile
 
 
 @functools.lru_cache(maxsize=None)
@@ -73,50 +63,23 @@ CASES = ["tile_%s_%s" % (t, k) for t in TILE_TAGS for k in ("52_relu", "32")] + 
         ["one_pixel", "tiny_3x8x2x3", "ragged_37x41", "cin_4", "cin_36", "cin_64", "ref_52_128", "ref_32_64x130"]
 
 
-def _ref64(x, w, b, dy, relu):
-    """The fp64 convolution (+ ReLU) with its gradients, the pre-activation z, and the same sums over absolute values (what the bounds are made of):
-    the absolute run takes |dy| masked by the REFERENCE's mask."""
-    out = {}
-    x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, b))
-    z = F.conv2d(x64, w64, b64, padding=1)
-    y = torch.relu(z) if relu else z
-    mask = (z.detach() > 0).double() if relu else torch.ones_like(z.detach())
-    y.backward(dy.double())
-    out.update(z=z.detach(), y=y.detach(), dx=x64.grad, dw=w64.grad, db=b64.grad)
-    xa, wa, ba = (t.double().abs().requires_grad_(True) for t in (x, w, b))
-    za = F.conv2d(xa, wa, ba, padding=1)
-    za.backward(dy.double().abs() * mask)
-    out.update(abs_y=za.detach(), abs_dx=xa.grad, abs_dw=wa.grad, abs_db=ba.grad)
-    return out
-
-
-def _bounds(ref, N, Ci, H, W):
-    return dict(y=_gamma(9 * Ci + 1) * ref["abs_y"], dx=_gamma(9 * CO) * ref["abs_dx"], dw=_gamma(N * H * W) * ref["abs_dw"],
-                db=_gamma(N * H * W) * ref["abs_db"])
+def _bounds(ref, N, Ci, H, W, relu):
+    return dict(y=gamma(9 * Ci + 1) * ref["abs_y"], dx=gamma(9 * CO) * ref["abs_dx"], dw=gamma(N * H * W) * ref["abs_dw"],
+                db=gamma(N * H * W) * ref["abs_db"])
 
 
 def _assert_no_preactivation_near_zero(c):
     """The ReLU cases: |z64| > B everywhere, so the sign of the fp32 pre-activation is the reference's (the inputs of _inputs() are built so)."""
-    if c["relu"]:
+    if c["conv"]["relu"]:
         margin = (c["ref"]["z"].abs() - c["bounds"]["y"]).min()
         assert margin > 0, "a pre-activation lies within its bound of zero: %.3e" % float(margin)
 
 
-def _run(x, w, b, dy, relu, backward=True):
-    xg, wg, bg = (t.cuda().requires_grad_(backward) for t in (x, w, b))
-    y = C3.conv3x3(xg, wg, bg, relu)
-    if backward:
-        y.backward(dy.cuda())
-    torch.cuda.synchronize()
-    return dict(y=y.detach(), dx=xg.grad, dw=wg.grad, db=bg.grad)
-
-
-def _inputs(name, N, Ci, H, W, relu):
+def _inputs(gen, N, Ci, H, W, relu):
     """Seeded random inputs.  Without ReLU: normal x, w (x 0.2), b, dy.  With ReLU no plain random tensor of these sizes keeps every pre-activation
     further than B ~ 4e-4 sigma(z) from zero, so the pre-activations sit near a lattice that misses zero: x = (multiples of 1/2) + d with
     |d| <= 2^-12 at full fp32 precision, w multiples of 1/16, b ODD multiples of 1/64 -- sum w x_lattice is a multiple of 1/32, so |z| >= 1/64 less
     the d terms (sigma ~ 1e-3), against B ~ 2e-3.  The x still carry full mantissas, so every product and sum rounds; dy is plain normal."""
-    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
     x = torch.randn((N, Ci, H, W), generator=gen)
     w = torch.randn((CO, Ci, 3, 3), generator=gen) * 0.2
     b = torch.randn((CO,), generator=gen)
@@ -127,102 +90,48 @@ def _inputs(name, N, Ci, H, W, relu):
     w[CO // 2] = 0.0                    # one exact-zero filter (its bias decides the sign)
     w[0] = -w[0].abs() - 1.0 / 16       # and a negative one
     dy = torch.randn((N, CO, H, W), generator=gen)
-    ref = _ref64(x, w, b, dy, relu)
-    return dict(dims=(N, Ci, H, W), relu=relu, x=x, w=w, b=b, dy=dy, ref=ref, bounds=_bounds(ref, N, Ci, H, W))
+    return dict(x=x, w=w, b=b, dy=dy, conv=dict(padding=1, relu=relu))
 
 
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """Inputs, the fp64 reference and the bounds of one case: computed once, shared by every test that needs them, never modified."""
-    return _inputs(name, *_cases()[name])
+_case = R.case_cache(_cases, _inputs, _bounds)
 
 
-def _ratio(t, t64, bound):
-    """The worst error / bound; an error of zero is inside any bound (also a bound of zero), an error above a zero bound is infinite."""
-    d = (t.detach().double().cpu() - t64).abs()
-    r = torch.where(d == 0, torch.zeros_like(d), d / bound.clamp_min(1e-300))
-    return float(r.max())
+def _op(relu):
+    return lambda x, w, b: C3.conv3x3(x, w, b, relu)
 
 
-def _check(test, name, got, c):
-    rec = dict(test=test, case=name, dims=list(c["dims"]), relu=c["relu"], fused={})
-    for k in KEYS:
-        assert got[k].shape == c["ref"][k].shape and got[k].dtype == torch.float32, k
-        rec["fused"][k] = _ratio(got[k], c["ref"][k], c["bounds"][k])
-    print(json.dumps(rec))
-    for k in KEYS:
-        assert torch.isfinite(got[k]).all(), k
-        assert rec["fused"][k] <= 1.0, "%s %s: error / bound = %.3f" % (name, k, rec["fused"][k])
+def _run(c):
+    return R.run_case(_op(c["conv"]["relu"]), c)
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_forward_and_backward_within_the_bounds(name):
     c = _case(name)
     _assert_no_preactivation_near_zero(c)
-    got = _run(c["x"], c["w"], c["b"], c["dy"], c["relu"])
-    _check("fp32", name, got, c)
-    if c["relu"]:                                                     # the mask is the reference's, element for element
+    got = _run(c)
+    R.check(dict(test="fp32", case=name, dims=list(c["dims"][:4]), relu=c["conv"]["relu"]), "fused", got, c["ref"], c["bounds"])
+    if c["conv"]["relu"]:                                             # the mask is the reference's, element for element
         assert torch.equal(got["y"].cpu() > 0, c["ref"]["z"] > 0)
-
-
-def _ints(shape, lo, hi, gen):
-    return torch.randint(lo, hi + 1, shape, generator=gen).float()
 
 
 @pytest.mark.parametrize("which", ["cin52_relu_2tile+1", "cin8_9x11"])
 def test_small_integers_give_the_exact_answer(which):
-    """x in [-3, 3], w, b, dy in [-2, 2]: every product and partial sum is an integer far below 2^24, so y, dx, dw, db must EQUAL the fp64 result.
-    Pre-activations of exactly zero occur; the gradient there is 0 ([z > 0]) in both."""
+    """Pre-activations of exactly zero occur; the gradient there is 0 ([z > 0]) in both."""
     TH, TW = _tile()
     N, Ci, H, W, relu = (2, 52, 2 * TH + 1, 2 * TW + 1, True) if which == "cin52_relu_2tile+1" else (2, 8, 9, 11, False)
-    gen = torch.Generator().manual_seed(zlib.crc32(which.encode()))
-    x, w, b, dy = _ints((N, Ci, H, W), -3, 3, gen), _ints((CO, Ci, 3, 3), -2, 2, gen), _ints((CO,), -2, 2, gen), _ints((N, CO, H, W), -2, 2, gen)
-    ref = _ref64(x, w, b, dy, relu)
+    _, ref = R.exact_integers(which, _op(relu), ((N, Ci, H, W), (CO, Ci, 3, 3), (CO,), (N, CO, H, W)), padding=1, relu=relu)
     if relu:
         assert int((ref["z"] == 0).sum()) > 0
-    got = _run(x, w, b, dy, relu)
-    for k in KEYS:
-        assert torch.equal(got[k].double().cpu(), ref[k]), k
 
 
 def test_two_runs_give_the_same_bits():
-    for name in ("tile_2T+1_T-1_52_relu", "ref_32_64x130"):
-        c = _case(name)
-        a = _run(c["x"], c["w"], c["b"], c["dy"], c["relu"])
-        b = _run(c["x"], c["w"], c["b"], c["dy"], c["relu"])
-        for k in KEYS:
-            assert torch.equal(a[k], b[k]), (name, k)
+    R.two_runs(_run, [(name, _case(name)) for name in ("tile_2T+1_T-1_52_relu", "ref_32_64x130")])
 
 
 @pytest.mark.parametrize("name", ["cin_64", "ref_32_64x130"])
-def test_requires_grad_handling(name):
+def test_requires_grad_handling(name, monkeypatch):
     c = _case(name)
-    relu = c["relu"]
-    full = _run(c["x"], c["w"], c["b"], c["dy"], relu)
-    x, w, b, dy = (c[k].cuda() for k in ("x", "w", "b", "dy"))
-    # x does not require grad: no input gradient, the same parameter gradients
-    wg, bg = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    y = C3.conv3x3(x, wg, bg, relu)
-    y.backward(dy)
-    assert x.grad is None and torch.equal(y.detach(), full["y"]) and torch.equal(wg.grad, full["dw"]) and torch.equal(bg.grad, full["db"])
-    # the weight frozen, then the bias frozen
-    xg, bg = x.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    C3.conv3x3(xg, w, bg, relu).backward(dy)
-    assert w.grad is None and torch.equal(xg.grad, full["dx"]) and torch.equal(bg.grad, full["db"])
-    wg = w.clone().requires_grad_(True)
-    C3.conv3x3(x, wg, b, relu).backward(dy)
-    assert b.grad is None and torch.equal(wg.grad, full["dw"])
-    # only x
-    xg = x.clone().requires_grad_(True)
-    C3.conv3x3(xg, w, b, relu).backward(dy)
-    assert torch.equal(xg.grad, full["dx"])
-    with torch.no_grad():
-        y0 = C3.conv3x3(x, wg, bg, relu)
-    assert y0.grad_fn is None and torch.equal(y0, full["y"])
-    # gradients in the parameters' dtypes and shapes
-    wd = w.double().requires_grad_(True)
-    C3.conv3x3(x, wd, b, relu).backward(dy)
-    assert wd.grad.dtype == torch.float64 and wd.grad.shape == w.shape and torch.equal(wd.grad.float(), full["dw"])
+    R.requires_grad_matrix(monkeypatch, C3, "c3_backward", _op(c["conv"]["relu"]), c)
 
 
 def test_cpu_tensors_are_an_error():
@@ -240,12 +149,7 @@ def test_what_the_op_does_not_take_goes_through_torch():
     plain, fused = plain[0], fused[0]
     x = torch.randn(2, 32, 20, 22, device="cuda")
 
-    def both(a, b, inp, **ac):
-        n0, p0 = A.calls["conv3x3"], A.calls["conv3x3_passthrough"]
-        with torch.autocast("cuda", enabled=bool(ac), **ac):
-            ya, yb = a(inp), b(inp)
-        assert A.calls["conv3x3"] == n0 and A.calls["conv3x3_passthrough"] == p0 + 1
-        assert ya.dtype == yb.dtype and ya.shape == yb.shape and ya.stride() == yb.stride() and torch.equal(ya, yb)
+    both = R.passthrough_pair(A.calls, "conv3x3")
 
     def forced(m, relu=False):
         f = copy.deepcopy(m)
@@ -300,10 +204,6 @@ def test_a_graphless_forward_of_a_ragged_plane_is_atens():
     assert counts(lambda: frozen(ragged.clone().requires_grad_(True)))[1:] == (1, 0)
 
 
-def _err(t, t64):
-    return float((t.detach().double().cpu() - t64).abs().max() / t64.abs().max().clamp_min(1e-300))
-
-
 def test_the_composed_head():
     """Conv3x3(32, 32) -> ReLU -> Conv1x1(32, 3) -> Softplus(100) with conv3x3.convert and gshead.convert applied in both orders: the same module
     classes, and output and parameter gradients under the criterion of test_gpu_stemconv.py::test_the_whole_stem -- err = max |t - t64| / max |t64|,
@@ -326,7 +226,7 @@ def test_the_composed_head():
     assert list(a.state_dict().keys()) == list(base.state_dict().keys()) == list(b.state_dict().keys())
     names = ["out"] + [n for n, _ in base.named_parameters()]
     refs = [out64.detach()] + [p.grad for p in ref.parameters()]
-    torch_err = [_err(t, t64) for t, t64 in zip([out32.detach()] + [p.grad for p in cpu32.parameters()], refs)]
+    torch_err = [R.rel_err(t, t64) for t, t64 in zip([out32.detach()] + [p.grad for p in cpu32.parameters()], refs)]
     n0, h0 = A.calls["conv3x3"], A.calls["gshead"]
     res = []
     for net in (a, b):
@@ -339,7 +239,7 @@ def test_the_composed_head():
         assert torch.equal(ta, tb)                                     # the same modules: the same bits
     rec = dict(test="composed_head", fused={}, torch_cpu={})
     for n, t64, te, tf in zip(names, refs, torch_err, res[0]):
-        rec["torch_cpu"][n], rec["fused"][n] = te, _err(tf, t64)
+        rec["torch_cpu"][n], rec["fused"][n] = te, R.rel_err(tf, t64)
     print(json.dumps(rec))
     for n in names:
         floor = 1e-6 if n == "out" else 1e-3

@@ -6,7 +6,6 @@ The reference is fp64 on the CPU everywhere, also for the converted Sequential. 
 is what the test there is about: the pass-through of a FusedHeadConv (forward only, under no_grad, on the smallest case)."""
 import copy
 import functools
-import json
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import _capi, accelerate as A
 from gps_gaussian_amd import gshead as GH
 
+import convop_run
 import gshead_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -51,12 +51,7 @@ def _run(c, need=("h", "w", "b"), op=None):
 
 
 def _check(name, got, ref, bnd, keys=R.KEYS):
-    q = {k: R.worst_ratio(got[k], ref[k], bnd[k]) for k in keys}
-    print(json.dumps(dict(case=name, error_over_bound=q)))
-    for k in keys:
-        assert got[k].shape == ref[k].shape and got[k].dtype == np.float32, k
-        assert np.isfinite(got[k]).all(), k
-        assert q[k] <= 1.0, "%s %s: error / bound = %.3f" % (name, k, q[k])
+    convop_run.check(dict(case=name), "error_over_bound", got, ref, bnd, keys=keys, ratio=R.worst_ratio)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -99,11 +94,8 @@ def test_small_integers_give_the_exact_answer(which):
 
 
 def test_two_runs_give_the_same_bits():
-    for name in ("multi_5T+3_k4_softplus", "c64_2x64x17x64_k4_sigmoid", "parts_65_k2_none"):
-        c, _, _ = _case(name)
-        a, b = _run(c), _run(c)
-        for k in R.KEYS:
-            assert np.array_equal(a[k], b[k]), (name, k)
+    names = ("multi_5T+3_k4_softplus", "c64_2x64x17x64_k4_sigmoid", "parts_65_k2_none")
+    convop_run.two_runs(_run, [(name, _case(name)[0]) for name in names], keys=R.KEYS)
 
 
 def test_only_the_gradients_asked_for_are_computed(monkeypatch):

@@ -18,7 +18,6 @@ import copy
 import functools
 import json
 import os
-import zlib
 
 import pytest
 import torch
@@ -30,14 +29,11 @@ from gps_gaussian_amd import _ops, accelerate as A
 from gps_gaussian_amd import groupnorm as GN
 from gps_gaussian_amd import stemconv as SC
 
+import convop_run as R
+from convop_run import KEYS, gamma
+
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24
 K, S, P = 5, 2, 2
-KEYS = ("y", "dx", "dw", "db")
-
-
-def _gamma(n):
-    return n * U / (1.0 - n * U)
 
 
 def _tile():
@@ -70,104 +66,71 @@ TILE_TAGS = ["T-1", "T", "T+1", "2T+1_T-1", "1_2T+1"]
 CASES = ["tile_%s_%s" % (t, p) for t in TILE_TAGS for p in ("even", "odd")] + \
         ["one_pixel", "tiny_3x1x2x3", "tiny_2x3x5x7", "ragged_37x41", "cout_8", "cout_40", "cout_64", "cin_1_64x130", "cin_3_64x130", "ref_cin_3", "ref_cin_1"]
 FP16_CASES = ["tile_T+1_odd", "ragged_37x41", "cout_40"]
+CONV = dict(stride=S, padding=P)
 
 
 def _out_hw(H, W):
     return (H + 2 * P - K) // S + 1, (W + 2 * P - K) // S + 1
 
 
-def _ref64(x, w, b, dy):
-    """The fp64 convolution with its gradients, and the same applied to absolute values (the sums the bounds are made of)."""
-    out = {}
-    for tag, f in (("", lambda t: t), ("abs_", torch.abs)):
-        x64, w64, b64 = (f(t.double().cpu()).requires_grad_(True) for t in (x, w, b))
-        y = F.conv2d(x64, w64, b64, stride=S, padding=P)
-        y.backward(f(dy.double().cpu()))
-        out.update({tag + "y": y.detach(), tag + "dx": x64.grad, tag + "dw": w64.grad, tag + "db": b64.grad})
-    return out
-
-
-def _bounds(ref, N, Ci, Co, H, W, y_half):
+def _bounds(ref, N, Ci, Co, H, W, y_half=False):
     Ho, Wo = _out_hw(H, W)
-    B = _gamma(Ci * K * K + 1) * ref["abs_y"]
+    B = gamma(Ci * K * K + 1) * ref["abs_y"]
     if y_half:
         B = B + 2.0 ** -11 * (ref["y"].abs() + B) + 2.0 ** -25
     taps = (-(-K // S)) ** 2
-    return dict(y=B, dx=_gamma(Co * taps) * ref["abs_dx"], dw=_gamma(N * Ho * Wo) * ref["abs_dw"], db=_gamma(N * Ho * Wo) * ref["abs_db"])
+    return dict(y=B, dx=gamma(Co * taps) * ref["abs_dx"], dw=gamma(N * Ho * Wo) * ref["abs_dw"], db=gamma(N * Ho * Wo) * ref["abs_db"])
 
 
-def _run(op, x, w, b, dy, autocast, backward=True):
-    """op(x, w, b) on the GPU -> y, dx, dw, db (as computed, dtypes included); backward=False: y alone."""
-    xg, wg, bg = (t.cuda().requires_grad_(backward) for t in (x, w, b))
-    with torch.autocast("cuda", torch.float16, enabled=autocast):
-        y = op(xg, wg, bg)
-    if backward:
-        y.backward(dy.cuda().to(y.dtype))
-    torch.cuda.synchronize()
-    return dict(y=y.detach(), dx=xg.grad, dw=wg.grad, db=bg.grad)
-
-
-def _aten(x, w, b):
-    return F.conv2d(x, w, b, stride=S, padding=P)
+def _aten(x, w, b, half=False):
+    with torch.autocast("cuda", torch.float16, enabled=half):
+        return F.conv2d(x, w, b, **CONV)
 
 
 def _fused(x, w, b):
-    half = torch.is_autocast_enabled()
-    return SC.conv2d(x, w, b, S, P, out_dtype=torch.float16 if half else torch.float32)
+    return SC.conv2d(x, w, b, S, P)
 
 
-@functools.lru_cache(maxsize=None)
-def _case(name, half=False):
-    """Inputs, the fp64 reference, the bounds and ATen's GPU result of one case: computed once, shared by every test that needs them, never modified."""
-    N, Ci, Co, H, W = _cases()[name]
-    Ho, Wo = _out_hw(H, W)
-    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) + int(half))
+def _inputs(gen, N, Ci, Co, H, W, half=False):
     x = torch.randn((N, Ci, H, W), generator=gen)
     w = torch.randn((Co, Ci, K, K), generator=gen) * 0.2
     b = torch.randn((Co,), generator=gen)
     w[Co // 2] = 0.0                    # one exact-zero filter
     w[0] = -w[0].abs() - 0.01           # and a negative one
-    dy = torch.randn((N, Co, Ho, Wo), generator=gen)
+    dy = torch.randn((N, Co) + _out_hw(H, W), generator=gen)
     if half:
         dy = dy.half()                  # the gradient of an fp16 output arrives in fp16; the reference starts from these values
-    ref = _ref64(x, w, b, dy)
-    return dict(dims=(N, Ci, Co, H, W), x=x, w=w, b=b, dy=dy, ref=ref, bounds=_bounds(ref, N, Ci, Co, H, W, half),
-                aten=_run(_aten, x, w, b, dy, half, backward=not half))   # ATen's fp16 backward is not run (see the top of the file)
+    return dict(x=x, w=w, b=b, dy=dy, conv=CONV)
 
 
-def _ratio(t, t64, bound):
-    """The worst error / bound; an error of zero is inside any bound (also a bound of zero), an error above a zero bound is infinite."""
-    d = (t.detach().double().cpu() - t64).abs()
-    r = torch.where(d == 0, torch.zeros_like(d), d / bound.clamp_min(1e-300))
-    return float(r.max())
+_inputs_ref_bounds = R.case_cache(_cases, _inputs, _bounds)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name, half=False):
+    """The shared case and ATen's GPU result for it, computed once as well; ATen's fp16 backward is not run (see the top of the file)."""
+    c = _inputs_ref_bounds(name, half)
+    return dict(c, aten=R.run_case(functools.partial(_aten, half=half), c, backward=not half))
 
 
 def _report(rec):
-    line = json.dumps(rec)
-    print(line)
+    R.emit(rec)
     out = os.environ.get("GPSGS_PARITY_DIR")
     if out and os.path.isdir(out):
         with open(os.path.join(out, "stemconv_parity.jsonl"), "a") as f:
-            f.write(line + "\n")
+            f.write(json.dumps(rec) + "\n")
 
 
 def _check(test, name, got, c, half=False):
-    rec = dict(test=test, case=name, dims=list(c["dims"]), y_dtype="fp16" if half else "fp32", fused={}, aten={})
-    for k in KEYS:
-        assert got[k].shape == c["ref"][k].shape, k
-        rec["fused"][k] = _ratio(got[k], c["ref"][k], c["bounds"][k])
-        rec["aten"][k] = _ratio(c["aten"][k], c["ref"][k], c["bounds"][k]) if c["aten"][k] is not None else None
-    _report(rec)
-    for k in KEYS:
-        assert torch.isfinite(got[k]).all(), k
-        assert rec["fused"][k] <= 1.0, "%s %s: error / bound = %.3f (ATen: %s)" % (name, k, rec["fused"][k], rec["aten"][k])
-    return rec
+    aten = {k: R.ratio(c["aten"][k], c["ref"][k], c["bounds"][k]) if c["aten"][k] is not None else None for k in KEYS}
+    return R.check(dict(test=test, case=name, dims=list(c["dims"]), y_dtype="fp16" if half else "fp32"), "fused", got, c["ref"], c["bounds"],
+                   dtype=None, more=dict(aten=aten), emit=_report)
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_fp32_forward_and_backward_within_the_bounds(name):
     c = _case(name)
-    got = _run(_fused, c["x"], c["w"], c["b"], c["dy"], False)
+    got = R.run_case(_fused, c)
     assert all(got[k].dtype == torch.float32 for k in KEYS)
     _check("fp32", name, got, c)
 
@@ -194,55 +157,19 @@ def test_fp16_autocast(name):
     _check("fp16_autocast", name, got, c, half=True)
 
 
-def _ints(shape, lo, hi, gen):
-    return torch.randint(lo, hi + 1, shape, generator=gen).float()
-
-
 @pytest.mark.parametrize("which", ["cin3_tile+1", "cin1_9x11"])
 def test_small_integers_give_the_exact_answer(which):
-    """x in [-3, 3], w, b, dy in [-2, 2]: every product and partial sum is an integer far below 2^24, so y, dx, dw, db must EQUAL the fp64 result."""
     TH, TW = _tile()
     N, Ci, Co, H, W = (2, 3, 32, 2 * TH + 1, 2 * TW + 1) if which == "cin3_tile+1" else (2, 1, 8, 9, 11)
-    Ho, Wo = _out_hw(H, W)
-    gen = torch.Generator().manual_seed(zlib.crc32(which.encode()))
-    x, w, b, dy = _ints((N, Ci, H, W), -3, 3, gen), _ints((Co, Ci, K, K), -2, 2, gen), _ints((Co,), -2, 2, gen), _ints((N, Co, Ho, Wo), -2, 2, gen)
-    ref = _ref64(x, w, b, dy)
-    got = _run(_fused, x, w, b, dy, False)
-    for k in KEYS:
-        assert torch.equal(got[k].double().cpu(), ref[k]), k
+    R.exact_integers(which, _fused, ((N, Ci, H, W), (Co, Ci, K, K), (Co,), (N, Co) + _out_hw(H, W)), **CONV)
 
 
 def test_two_runs_give_the_same_bits():
-    c = _case("tile_2T+1_T-1_odd")
-    a = _run(_fused, c["x"], c["w"], c["b"], c["dy"], False)
-    b = _run(_fused, c["x"], c["w"], c["b"], c["dy"], False)
-    for k in KEYS:
-        assert torch.equal(a[k], b[k]), k
+    R.two_runs(functools.partial(R.run_case, _fused), [("tile_2T+1_T-1_odd", _case("tile_2T+1_T-1_odd"))])
 
 
-def test_requires_grad_handling():
-    c = _case("cin_1_64x130")
-    full = _run(_fused, c["x"], c["w"], c["b"], c["dy"], False)
-    x, w, b, dy = (c[k].cuda() for k in ("x", "w", "b", "dy"))
-    # x does not require grad: no input gradient, the same parameter gradients
-    wg, bg = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    y = SC.conv2d(x, wg, bg, S, P)
-    y.backward(dy)
-    assert x.grad is None and torch.equal(y.detach(), full["y"]) and torch.equal(wg.grad, full["dw"]) and torch.equal(bg.grad, full["db"])
-    # the weight frozen, then the bias frozen
-    xg, bg = x.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    SC.conv2d(xg, w, bg, S, P).backward(dy)
-    assert w.grad is None and torch.equal(xg.grad, full["dx"]) and torch.equal(bg.grad, full["db"])
-    wg = w.clone().requires_grad_(True)
-    SC.conv2d(x, wg, b, S, P).backward(dy)
-    assert b.grad is None and torch.equal(wg.grad, full["dw"])
-    # only x
-    xg = x.clone().requires_grad_(True)
-    SC.conv2d(xg, w, b, S, P).backward(dy)
-    assert torch.equal(xg.grad, full["dx"])
-    with torch.no_grad():
-        y0 = SC.conv2d(x, wg, bg, S, P)
-    assert y0.grad_fn is None and torch.equal(y0, full["y"])
+def test_requires_grad_handling(monkeypatch):
+    R.requires_grad_matrix(monkeypatch, SC, "sc_backward", _fused, _case("cin_1_64x130"), double_weight=False)
 
 
 def test_what_the_op_does_not_take_goes_through_aten():
@@ -252,12 +179,7 @@ def test_what_the_op_does_not_take_goes_through_aten():
     assert SC.convert(fused) == 1
     x = torch.randn(2, 3, 20, 22, device="cuda")
 
-    def both(a, b, inp, **ac):
-        n0, p0 = A.calls["stemconv"], A.calls["stemconv_passthrough"]
-        with torch.autocast("cuda", enabled=bool(ac), **ac):
-            ya, yb = a(inp), b(inp)
-        assert A.calls["stemconv"] == n0 and A.calls["stemconv_passthrough"] == p0 + 1
-        assert ya.dtype == yb.dtype and ya.shape == yb.shape and ya.stride() == yb.stride() and torch.equal(ya, yb)
+    both = R.passthrough_pair(A.calls, "stemconv")
 
     both(plain, fused, x.to(memory_format=torch.channels_last))                                  # channels-last input
     both(copy.deepcopy(plain).half(), copy.deepcopy(fused).half(), x.half())                      # fp16 input outside autocast
@@ -275,10 +197,6 @@ def test_what_the_op_does_not_take_goes_through_aten():
     both(plain, fused, x[:0])                                                                     # an empty batch
     n0 = A.calls["stemconv"]
     assert fused(x).dtype == torch.float32 and A.calls["stemconv"] == n0 + 1                      # and the ordinary call is the fused one
-
-
-def _err(t, t64):
-    return float((t.detach().double().cpu() - t64).abs().max() / t64.abs().max().clamp_min(1e-300))
 
 
 def test_the_whole_stem():
@@ -310,7 +228,7 @@ def test_the_whole_stem():
     refs = [out64.detach()] + [p.grad for p in ref.parameters()]
     rec = dict(test="whole_stem", fused={}, aten={})
     for n, t64, ta, tf in zip(names, refs, res["aten"], res["fused"]):
-        rec["aten"][n], rec["fused"][n] = _err(ta, t64), _err(tf, t64)
+        rec["aten"][n], rec["fused"][n] = R.rel_err(ta, t64), R.rel_err(tf, t64)
     _report(rec)
     for n in names:
         floor = 1e-6 if n == "out" else 1e-3

@@ -15,6 +15,7 @@ from gps_gaussian_amd import accelerate as A
 from gps_gaussian_amd import groupnorm as GN
 
 import gn_epilogue_cases as E
+import hook_run
 
 
 def _run(net, x, g):
@@ -114,7 +115,7 @@ def test_the_op_itself_refuses_cpu_tensors_and_a_residual_without_relu():
 
 
 def test_resblock_is_accepted_by_name_only():
-    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
+    hook_run.assert_the_names(A)
     assert A.requested("resblock") == ("resblock",)
     assert A.requested("all") == A.FEATURES and "resblock" not in A.FEATURES
     assert A.requested("all,resblock") == A.FEATURES + ("resblock",)

@@ -12,6 +12,8 @@ import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import accelerate as A
 from gps_gaussian_amd import groupnorm as GN
 
+import hook_run
+
 
 class _Branch(nn.Module):
     def __init__(self, norm):
@@ -93,7 +95,7 @@ def test_the_op_itself_refuses_cpu_tensors():
 
 
 def test_groupnorm_is_accepted_by_name_only():
-    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
+    hook_run.assert_the_names(A)
     assert A.requested("groupnorm") == ("groupnorm",)
     assert A.requested("all") == A.FEATURES and "groupnorm" not in A.FEATURES
     assert A.requested("all,groupnorm,splat") == A.FEATURES + ("splat", "groupnorm")

@@ -10,6 +10,8 @@ import gps_gaussian_amd
 from gps_gaussian_amd import accelerate as A
 from gps_gaussian_amd import gshead as GH
 
+import hook_run
+
 
 @pytest.fixture(autouse=True)
 def _built():
@@ -107,7 +109,7 @@ def test_head_has_no_cpu_path():
 
 
 def test_the_opt_in_name():
-    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
+    hook_run.assert_the_names(A)
     assert "gshead" in A.calls and "gshead_passthrough" in A.calls
     assert A.requested("gshead") == ("gshead",)
     assert "gshead" not in A.requested("all") and A.requested("all") == A.FEATURES

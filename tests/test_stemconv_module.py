@@ -10,6 +10,8 @@ import gps_gaussian_amd  # noqa: F401
 from gps_gaussian_amd import accelerate as A
 from gps_gaussian_amd import stemconv as SC
 
+import hook_run
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _built():
@@ -68,7 +70,7 @@ def test_the_op_itself_raises_on_a_cpu_tensor():
 
 
 def test_the_stemconv_name():
-    assert A.OPT_IN == ("splat", "groupnorm", "resblock", "stemconv", "gshead")
+    hook_run.assert_the_names(A)
     assert A.requested("stemconv") == ("stemconv",)
     assert A.requested("all,stemconv") == A.FEATURES + ("stemconv",)
     assert "stemconv" not in A.requested("all") and A.requested("all") == A.FEATURES
