@@ -184,7 +184,7 @@ _C3 = {
     "c3_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "c3_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-# 1x1 convolution on the matrix cores (the header's last section; tests/test_capi_conv1x1.py)
+# 1x1 convolution on the matrix cores (tests/test_capi_conv1x1.py)
 _C1 = {
     "c1_supported": (i32, [i32, i32, i32]),
     "c1_tile": (i32, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -192,9 +192,16 @@ _C1 = {
     "c1_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "c1_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
-PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3, **_C1}
-SECTIONS = tuple(tuple(s) for s in (_GSR, _GN, _GNE, _SC, _C3, _C1))     # each section's names, in header order
-SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS, C1_SYMBOLS = SECTIONS
+# Decoder glue, bilinear 2x upsample + concatenation (the header's last section; tests/test_capi_upcat.py).  skips / skip_channels: host arrays
+_UC = {
+    "uc_supported": (i32, [i32, C.POINTER(i32)]),
+    "uc_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "uc_forward": (i32, [vp, pp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
+    "uc_backward": (i32, [vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
+}
+PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3, **_C1, **_UC}
+SECTIONS = tuple(tuple(s) for s in (_GSR, _GN, _GNE, _SC, _C3, _C1, _UC))     # each section's names, in header order
+SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS, C1_SYMBOLS, UC_SYMBOLS = SECTIONS
 
 _lib = None
 

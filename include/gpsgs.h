@@ -51,6 +51,10 @@
  *   c1_forward / c1_backward (+ c1_supported, c1_tile, c1_scratch_bytes)
  *       the 1x1 convolution that opens the shortcut of every ResidualBlock whose input and output differ, nn.Conv2d(in, planes, 1, stride)
  *       with stride 1 or 2 (core/extractor.py:43-45), and its autograd backward.
+ *   uc_forward / uc_backward (+ uc_supported, uc_tile)
+ *       the regresser's decoder glue, `self.up(...)` (nn.Upsample(scale_factor=2, mode="bilinear")) followed by torch.cat with the skip
+ *       tensors, three times in GSRegresser.forward (lib/gs_parm_network.py:56-67), and its autograd backward: ATen's upsample kernel, the
+ *       copies of the concatenations, and the atomics-based upsample backward.
  */
 #ifndef GPSGS_H
 #define GPSGS_H
@@ -82,7 +86,8 @@ extern "C" {
                                still 4 after the Gaussian heads: gsr_head_supported, gsr_head_tile, gsr_head_scratch_bytes, gsr_head_forward,
                                   gsr_head_backward (additive)
                                still 4 after the 3x3 convolutions: c3_supported, c3_tile, c3_scratch_bytes, c3_forward, c3_backward (additive)
-                               still 4 after the 1x1 convolutions: c1_supported, c1_tile, c1_scratch_bytes, c1_forward, c1_backward (additive) */
+                               still 4 after the 1x1 convolutions: c1_supported, c1_tile, c1_scratch_bytes, c1_forward, c1_backward (additive)
+                               still 4 after the decoder glue: uc_supported, uc_tile, uc_forward, uc_backward (additive) */
 
 enum {
     GPSGS_OK = 0,
@@ -755,6 +760,28 @@ size_t c1_scratch_bytes(int N, int C_in, int C_out, int H, int W, int stride);
 int c1_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int stride, float *y, void *stream);
 int c1_backward(const float *x, const float *w, const float *dy, int N, int C_in, int C_out, int H, int W, int stride, float *dx, float *dw,
                 float *dbias, void *scratch, void *stream);
+
+/* ---- Decoder glue: bilinear 2x upsample + channel concatenation in one pass, forward and backward ------------------------------------------
+ * out[N, Ca + C_0 + .. + C_{K-1}, 2h, 2w]: channels [0, Ca) are nn.Upsample(scale_factor=2, mode="bilinear") of a[N,Ca,h,w] (align_corners =
+ * False), the K skip tensors s_k[N,C_k,2h,2w] follow in order, copied bit for bit (torch.cat along dim 1).  0 <= K <= 3; everything contiguous NCHW
+ * fp32.  The upsample is separable with fixed taps per axis (n the axis' input length):
+ *     o[2i] = 0.25 a[max(i - 1, 0)] + 0.75 a[i]        o[2i + 1] = 0.75 a[i] + 0.25 a[min(i + 1, n - 1)]
+ * evaluated along x first, then along y, each tap pair as fmaf(0.75, near, 0.25 * far): exact fp32 in that order, two roundings on every path.
+ * skips, skip_channels: HOST arrays of K device pointers / K channel counts (read before the call returns; NULL allowed where K = 0).
+ * uc_supported: 1 for 0 <= K <= 3 with every channel count >= 1; otherwise 0.
+ * uc_tile: the output tile (rows, columns) one workgroup of the forward's upsampled part computes.
+ * Pointers need 4-byte alignment; with w even and out and every skip 16-byte aligned the forward stores and copies 16 bytes per lane.
+ * uc_backward takes dout, the gradient of out, [N, Ca + sum C_k, 2h, 2w], and WRITES ALL of da[N,Ca,h,w] (NULL = not wanted: nothing is launched,
+ * GPSGS_OK): da[i,j] = the sum over the taps of dout[:, :Ca] the forward scattered from a[i,j] -- rows 2i-1 .. 2i+2 and columns 2j-1 .. 2j+2, clamped
+ * to the plane (the clamp is the border element's folded tap), weights 0.25, 0.75, 0.75, 0.25 per axis -- along x first, then along y, each as
+ * fmaf(0.75, d1 + d2, 0.25 * (d0 + d3)).  A gather, one thread per element: no atomics, nothing to clear, the same bits on every run.  The skips'
+ * gradients are the slices dout[:, c0_k : c0_k + C_k]; no kernel computes them.
+ * GPSGS_E_INVALID, before any HIP call: a non-positive N, Ca, h or w, K outside 0..3, a skip channel count below 1 (or skip_channels NULL with
+ * K > 0), 2^31 elements or more in any tensor, a NULL pointer (a, out, skips or one of its entries; dout) or one aligned to less than 4 bytes. */
+int uc_supported(int K, const int *skip_channels);
+int uc_tile(int *tile_h, int *tile_w);
+int uc_forward(const float *a, const float *const *skips, const int *skip_channels, int K, int N, int Ca, int h, int w, float *out, void *stream);
+int uc_backward(const float *dout, const int *skip_channels, int K, int N, int Ca, int h, int w, float *da, void *stream);
 
 #ifdef __cplusplus
 }
