@@ -192,6 +192,14 @@ _C1 = {
     "c1_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "c1_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
+# Residual-block 3x3 convolution, C_in -> C_out, on the matrix cores (tests/test_capi_resconv.py)
+_RC = {
+    "rc_supported": (i32, [i32, i32]),
+    "rc_tile": (i32, [C.POINTER(i32), C.POINTER(i32)]),
+    "rc_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "rc_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "rc_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+}
 # Decoder glue, bilinear 2x upsample + concatenation (the header's last section; tests/test_capi_upcat.py).  skips / skip_channels: host arrays
 _UC = {
     "uc_supported": (i32, [i32, C.POINTER(i32)]),
@@ -199,9 +207,9 @@ _UC = {
     "uc_forward": (i32, [vp, pp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
     "uc_backward": (i32, [vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
 }
-PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3, **_C1, **_UC}
-SECTIONS = tuple(tuple(s) for s in (_GSR, _GN, _GNE, _SC, _C3, _C1, _UC))     # each section's names, in header order
-SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS, C1_SYMBOLS, UC_SYMBOLS = SECTIONS
+PROTOTYPES = {**_GSR, **_GN, **_GNE, **_SC, **_C3, **_C1, **_RC, **_UC}
+SECTIONS = tuple(tuple(s) for s in (_GSR, _GN, _GNE, _SC, _C3, _C1, _RC, _UC))     # each section's names, in header order
+SYMBOLS, GN_SYMBOLS, GNE_SYMBOLS, SC_SYMBOLS, C3_SYMBOLS, C1_SYMBOLS, RC_SYMBOLS, UC_SYMBOLS = SECTIONS
 
 _lib = None
 

@@ -51,6 +51,9 @@
  *   c1_forward / c1_backward (+ c1_supported, c1_tile, c1_scratch_bytes)
  *       the 1x1 convolution that opens the shortcut of every ResidualBlock whose input and output differ, nn.Conv2d(in, planes, 1, stride)
  *       with stride 1 or 2 (core/extractor.py:43-45), and its autograd backward.
+ *   rc_forward / rc_backward (+ rc_supported, rc_tile, rc_scratch_bytes)
+ *       the two stride-1 3x3 convolutions of a ResidualBlock, `conv1` and `conv2` = nn.Conv2d(in, planes, 3, padding=1) (core/extractor.py:10-11)
+ *       at the widths of the depth encoder and the regresser's decoders, and their autograd backward.
  *   uc_forward / uc_backward (+ uc_supported, uc_tile)
  *       the regresser's decoder glue, `self.up(...)` (nn.Upsample(scale_factor=2, mode="bilinear")) followed by torch.cat with the skip
  *       tensors, three times in GSRegresser.forward (lib/gs_parm_network.py:56-67), and its autograd backward: ATen's upsample kernel, the
@@ -87,6 +90,8 @@ extern "C" {
                                   gsr_head_backward (additive)
                                still 4 after the 3x3 convolutions: c3_supported, c3_tile, c3_scratch_bytes, c3_forward, c3_backward (additive)
                                still 4 after the 1x1 convolutions: c1_supported, c1_tile, c1_scratch_bytes, c1_forward, c1_backward (additive)
+                               still 4 after the residual-block 3x3 convolutions: rc_supported, rc_tile, rc_scratch_bytes, rc_forward, rc_backward
+                                  (additive)
                                still 4 after the decoder glue: uc_supported, uc_tile, uc_forward, uc_backward (additive) */
 
 enum {
@@ -760,6 +765,31 @@ size_t c1_scratch_bytes(int N, int C_in, int C_out, int H, int W, int stride);
 int c1_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, int stride, float *y, void *stream);
 int c1_backward(const float *x, const float *w, const float *dy, int N, int C_in, int C_out, int H, int W, int stride, float *dx, float *dw,
                 float *dbias, void *scratch, void *stream);
+
+/* ---- 3x3 convolution from C_in to C_out channels on the fp32 matrix cores, forward and backward (the residual blocks) ---------------------
+ * y[N,C_out,H,W] = conv2d(x[N,C_in,H,W], w[C_out,C_in,3,3], bias[C_out], stride 1, padding 1), zero padding, contiguous NCHW fp32
+ * (torch.nn.functional.conv2d).  Implicit GEMM on v_mfma_f32_32x32x2_f32: exact fp32, every sum an fmaf chain in a fixed order (the products in
+ * channel order first, the bias added last), no layout transposes, no atomics, nothing cleared in front, the same bits on every run.
+ * rc_supported: 1 for C_in a multiple of 4 with 4 <= C_in <= 192 and C_out a multiple of 16 with 16 <= C_out <= 96; otherwise 0.
+ * rc_tile: the output tile (rows, columns) one workgroup of the forward and of the input gradient computes (for 32 output channels).
+ * x, y, dy, dx and scratch must be 16-byte aligned; H and W may be anything >= 1, rows may start off 16-byte boundaries.
+ * rc_backward takes dy, the gradient of y.  It WRITES dx = conv(dy, w flipped and transposed) (NULL = not wanted: that kernel is not launched)
+ * and dw / dbias (both or neither; NULL = not wanted).  dw and dbias are sums over pixels: the 4 x 32 pixel tiles are dealt to `parts` partitions
+ * (tile t to partition t mod parts); one workgroup per (partition, block of 32 output channels, block of 64 input channels) walks its partition's
+ * tiles in index order and writes its block of that partition's partial; the partials are added in index order, in groups of 32 and then the groups.
+ * scratch (needed for dw / dbias only): DEVICE, at least rc_scratch_bytes(N, C_in, C_out, H, W) =
+ *     4 * C_out * (9 * C_in + 1) * (parts + ceil(parts / 32))   bytes,
+ *     parts = min(512 / (ceil(C_out / 32) * ceil(C_in / 64)) rounded down, N * ceil(H / 4) * ceil(W / 32))
+ * -- at most 39.0 MB for the supported widths -- and 0 for arguments rc_forward would refuse (layout: the partials, then the group sums, as under
+ * gsr_head_scratch_bytes).
+ * GPSGS_E_INVALID, before any HIP call: channel counts rc_supported refuses, a non-positive N, H or W, 2^31 elements or more in x or in y, one of
+ * dw / dbias without the other, a NULL required pointer (x, w, bias, y; x, w, dy, and scratch where dw is wanted) or a misaligned one. */
+int rc_supported(int C_in, int C_out);
+int rc_tile(int *tile_h, int *tile_w);
+size_t rc_scratch_bytes(int N, int C_in, int C_out, int H, int W);
+int rc_forward(const float *x, const float *w, const float *bias, int N, int C_in, int C_out, int H, int W, float *y, void *stream);
+int rc_backward(const float *x, const float *w, const float *dy, int N, int C_in, int C_out, int H, int W, float *dx, float *dw, float *dbias,
+                void *scratch, void *stream);
 
 /* ---- Decoder glue: bilinear 2x upsample + channel concatenation in one pass, forward and backward ------------------------------------------
  * out[N, Ca + C_0 + .. + C_{K-1}, 2h, 2w]: channels [0, Ca) are nn.Upsample(scale_factor=2, mode="bilinear") of a[N,Ca,h,w] (align_corners =
